@@ -5,14 +5,18 @@ configs[1] / `metric`: "pop=200 HoF=5 ... 1/2/4/8 GPU").  One "step" = one full 
 the device.  `--gpus N` shards THAT population over N ranks (strong scaling, the metric's own split; `--scaling weak`
 keeps 200 individuals per GPU instead).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see the contract in DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (see the contract in DESIGN.md "Measurement").  A plain run sets up, warms up, times the K
+steps and prints the line; `--full` adds what takes runs of its own (the cold reading, the CPU baselines, the other
+configs' legs in `extra`, weak scaling under --gpus N, the host-mode phase breakdowns).  `--dump-outputs DIR` writes
+what the last timed step computed as DIR/<name>.npy (ga workload, env on the device, one GPU).
 Synthetic data: random-init nets (torch default init, seed 0) and the env's own seeded reset stream.
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -148,7 +152,8 @@ def main():
                     "device has been under this workload for this long in total: a generation of the headline is 1.7 ms, and "
                     "the part needs ~100 ms of load before its clocks settle (W = 5: 573-590 generations/s, W = 60 or more: "
                     "600-605 on the same box; profiles/r05_experiments.md section 7).  0 = exactly W steps.  The line "
-                    "carries settle_steps")
+                    "carries settle_steps.  ga on one GPU (env on the device) settles on a second trainer of the same "
+                    "workload, so that the timed one always enters its K steps after W (+ K under --full) generations")
     ap.add_argument("--scaling", choices=["strong", "weak"], default=None, help="ga / es under --gpus N: strong (default) = "
                     "BASELINE's metric, ONE population (--pop, 200) sharded over the N ranks; weak = --pop-per-gpu "
                     "individuals on every GPU.  (dqn-ga / dqn-es are the per-GPU shards of configs[3] / [4]: always weak)")
@@ -162,7 +167,7 @@ def main():
     ap.add_argument("--elites", type=int, default=2)
     ap.add_argument("--limit", type=int, default=200)
     ap.add_argument("--env", default="device", choices=["device", "host"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-graph", action="store_true", help="enqueue every launch eagerly instead of replaying the "
                     "captured hipGraph of a generation's rollout")
     ap.add_argument("--no-overlap", action="store_true")
@@ -187,10 +192,17 @@ def main():
     ap.add_argument("--frames", default="device", choices=["device", "host"], help="dqn-ga / dqn-es: host = the env in host "
                     "memory (frames rendered by the host cores, copied up every agent-step, actions copied down): the "
                     "PCIe-inclusive form; device = frames synthesised in HBM (the measured form of cfg 4 / cfg 5)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short runs of the other configs carried in "
-                    "the headline JSON's `extra` block")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the short runs of the other configs carried "
+                    "in the headline JSON's `extra` block")
     ap.add_argument("--cohorts", type=int, default=None, help="independent game cohorts per rollout (default: the "
                     "engine's DEFAULT_COHORTS)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the cold reading "
+                    "(cold_gens_per_sec), the CPU baselines, the other configs' legs (`extra`), weak scaling under --gpus N "
+                    "and the host-mode phase breakdowns (host_env, host_frames); --no-extra / --no-cpu-baseline trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one "
+                    "computed (game rewards, fitness, elite ids, sigma, elite and hall-of-fame weights) as DIR/<name>.npy; "
+                    "the same arguments give the same inputs in every run.  The ga workload with the env on the device, "
+                    "one GPU")
     a = ap.parse_args()
     if a.scaling is None:
         a.scaling = "weak" if (a.pop_per_gpu is not None or a.es_pop_per_gpu is not None) else "strong"
@@ -198,6 +210,10 @@ def main():
         total = a.pop or (200 if a.workload == "ga" else 1000)
         if total % a.gpus:
             raise SystemExit(f"--scaling strong: population {total} is not divisible by --gpus {a.gpus}")
+    if a.dump_outputs and (a.workload != "ga" or a.env != "device" or a.gpus != 1 or a.shard_of):
+        # (elsewhere the settling steps run on the timed engine itself: how many generations precede the timed ones
+        # depends on the clocks)
+        raise SystemExit("--dump-outputs: the ga workload with the env on the device, on one GPU without --shard-of")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks as fresh child processes (one per GPU, torch.distributed.run)
@@ -230,7 +246,7 @@ def main():
     torch.manual_seed(0)
     np.random.seed(0)
     if a.workload == "ga":
-        out = run_ga(a, ctx, dev)
+        out = run_ga(a, ctx, dev, dump_dir=a.dump_outputs)
     elif a.workload == "es":
         out = run_es(a, ctx, dev)
     else:
@@ -256,16 +272,15 @@ def main():
         out["allgather_us"] = {"per_generation": float(np.sum(us)) / max(a.steps, 1), "calls_per_generation":
                                len(us) / max(a.steps, 1), "max_call": float(np.max(us)) if us else 0.0,
                                "transport": "rccl" if torch.distributed.get_backend() == "nccl" else "gloo (host-staged)"}
-    if real_world > 1 and a.workload in ("ga", "es") and scaling == "strong" and not a.no_extra:
+    if a.full and real_world > 1 and a.workload in ("ga", "es") and scaling == "strong" and not a.no_extra:
         # the other reading of "N GPUs": per-GPU work fixed (every rank takes part; short run)
-        import copy
         w = copy.copy(a)
         w.scaling, w.steps, w.warmup, w.no_cpu_baseline, w.pop_per_gpu, w.es_pop_per_gpu = "weak", 5, 2, True, None, None
         r = run_ga(w, ctx, dev) if a.workload == "ga" else run_es(w, ctx, dev)
         out["weak_scaling"] = {"population": r["config"]["population"], "gens_per_sec": r["gens_per_sec"],
                                "value": r["value"], "ms_per_step": r["ms_per_step"]}
     if ctx.rank == 0:
-        if a.workload == "ga" and ctx.world == 1 and not a.no_extra and not a.shard_of:
+        if a.full and a.workload == "ga" and ctx.world == 1 and not a.no_extra and not a.shard_of:
             out["extra"] = extras(a, ctx, dev)
         print(json.dumps(compact(out)), flush=True)
     ctx.shutdown()
@@ -274,11 +289,14 @@ def main():
 MAX_SETTLE_STEPS = 256
 
 
-def _warm_up(step, a, ctx, dev, cold_probe=False):
+def _warm_up(step, a, ctx, dev, cold_probe=False, settler=None):
     """the W untimed warm-up steps, then - untimed as well - as many more as it takes until the device has been under this
     workload for --settle-ms in total (every rank runs the same number: it comes from times reduced over the ranks).
     -> the number of extra steps.  cold_probe: the first K of them are timed on the side, bracketed like the real region
-    (a.cold_gens_per_sec = what `--settle-ms 0` would have reported, for the record; they count as settling steps)"""
+    (a.cold_gens_per_sec = what `--settle-ms 0` would have reported, for the record; they count as settling steps).
+    settler: () -> the step function the settling steps take instead of `step`, called once after the warm-up (its own
+    set-up is not settling time): run_ga settles the clocks on a second trainer of the same workload, so that the timed one
+    enters its K steps after a fixed number of generations and computes the same outputs in every run"""
     t0 = time.perf_counter()
     for _ in range(a.warmup):
         step()
@@ -296,16 +314,21 @@ def _warm_up(step, a, ctx, dev, cold_probe=False):
         a.cold_gens_per_sec = a.steps / ctx.max_over_ranks(time.perf_counter() - tc, dev)
         extra = a.steps
     if want > 0 and a.warmup > 0:
-        for _ in range(4):   # (the warm-up steps hold graph captures: their mean overestimates a step)
+        behind = a.warmup + extra   # steps the clock below has seen
+        if settler is not None:
+            step = settler()
+            torch.cuda.synchronize()
+            t0, behind = time.perf_counter(), 0
+        for _ in range(5):   # (the warm-up steps hold graph captures: their mean overestimates a step)
             torch.cuda.synchronize()
             done = ctx.max_over_ranks(time.perf_counter() - t0, dev)
             if done >= want or extra >= MAX_SETTLE_STEPS:
                 break
-            per = done / (a.warmup + extra)
-            n = int(min(MAX_SETTLE_STEPS - extra, max(1, np.ceil((want - done) / per))))
+            n = 1 if behind == 0 else int(min(MAX_SETTLE_STEPS - extra, max(1, np.ceil((want - done) / (done / behind)))))
             for _ in range(n):
                 step()
             extra += n
+            behind += n
     a.settle_steps = extra
     return extra
 
@@ -405,7 +428,7 @@ def run_dqn(a, ctx, dev, algo, pop_per_gpu=None, T=None):
     dt = _timed_steps(tr.step, a, ctx, dev, before_timed=lambda: (torch.cuda.synchronize(), eng.ro.reset_timing()))
     conv_ms, fc1_ms = eng.ro.times_ms(0), eng.ro.times_ms(1)
     frame_phase = None
-    if host_frames:   # one more generation with HIP events around every cohort-step's copies and forward
+    if a.full and host_frames:   # one more generation with HIP events around every cohort-step's copies and forward
         eng.ro.phase_us = np.zeros(5)
         tr.step()
         torch.cuda.synchronize()
@@ -560,7 +583,7 @@ def extras(a, ctx, dev):
     # (profiles/r04_experiments.md); `python bench.py --env host` is how the mode is run anyway.
     def host_leg(*more):
         import subprocess
-        cmd = [sys.executable, os.path.abspath(__file__), "--env", "host", "--no-extra", "--no-cpu-baseline"] + list(more)
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--env", "host", "--no-extra", "--no-cpu-baseline"] + list(more)
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300, check=True)
         return json.loads(p.stdout.decode().strip().splitlines()[-1])
     leg("cfg2_host_env", lambda: host_leg("--steps", "40", "--warmup", "3"))
@@ -594,7 +617,42 @@ def extras(a, ctx, dev):
     return ex
 
 
-def run_ga(a, ctx, dev):
+def dump_ga_outputs(tr, out_dir, max_bytes=48 << 20):
+    """--dump-outputs: what the last timed generation computed, as a caller of GATrainer.step finds it on the device, one
+    DIR/<name>.npy each (float64 / float32): the play_game triples of its games and of the previous generation's ten
+    evaluation games, fitness, diversity, elite ids, the sigma rule's state and histories, and the weights of every role's
+    elites and hall of fame (11 MB at the headline's shape; beyond max_bytes a fixed, seeded sample of the parameters)"""
+    from coevonet_amd.genetic_algorithm import ROLES, SIGMA_ATTR
+    eng = tr.eng
+    torch.cuda.synchronize()
+    rewards = np.asarray(eng.rewards_host(), dtype=np.float64)
+    arrays = {"game_rewards": rewards[:eng.n_main], "eval_game_rewards": rewards[eng.n_main:],
+              "fitness": np.stack([eng.fitness[r].cpu().numpy() for r in ROLES]),
+              "diversity": np.concatenate([eng.div[r].cpu().numpy() for r in ROLES]),
+              "elite_ids": np.stack([eng.order[r][:eng.E].cpu().numpy() for r in ROLES]).astype(np.float64)}
+    if getattr(eng, "sigma64", None) is not None:   # the device-resident loops keep the sigma rule on the device
+        arrays["sigma"] = eng.sigma64.cpu().numpy()
+        arrays["eval_reward_history"] = eng.hist[:, :tr.gen].cpu().numpy()
+        arrays["sigma_history"] = eng.sig_hist[:, :tr.gen].cpu().numpy()
+    else:
+        arrays["sigma"] = np.array([getattr(tr.args, SIGMA_ATTR[r]) for r in ROLES], dtype=np.float64)
+    weights = {}
+    for r in ROLES:
+        weights[f"elite_weights_{r}"] = eng.download(r, "elite", 0, eng.E)
+        weights[f"hof_weights_{r}"] = eng.download(r, "hof", 0, eng.hof)
+    total = sum(w.nbytes for w in weights.values())
+    if total > max_bytes:
+        g = np.random.default_rng(0)
+        for k, w in weights.items():
+            keep = max(1, int(w.shape[1] * max_bytes / total))
+            weights[k] = w[:, np.sort(g.choice(w.shape[1], keep, replace=False))]
+    arrays.update(weights)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+
+
+def run_ga(a, ctx, dev, dump_dir=None):
     from coevonet_amd import lib as L
     from coevonet_amd.game_logic import initialize_env
     from coevonet_amd.genetic_algorithm import GATrainer
@@ -613,17 +671,33 @@ def run_ga(a, ctx, dev):
         args.coevo_device_loop = False
     if a.sharded_path:
         args.coevo_force_sharded_loop = True
-    env = initialize_env(args)
-    env.max_cycles = a.max_cycles
-    tr = GATrainer(env, args, rng="device_philox", env_mode=a.env, collect=False, dist_ctx=ctx)
-    eng = tr.eng
-
     timed = a.env == "device"
-    if timed:
-        eng.ro.use_graph = not a.no_graph
-        eng.ro.overlap = not a.no_overlap
-        eng.ro.time_light = True  # before the warm-up, so the (timed) graph is captured outside the timed region
-    _warm_up(tr.step, a, ctx, dev, cold_probe=True)
+
+    def trainer():
+        env = initialize_env(args)
+        env.max_cycles = a.max_cycles
+        t = GATrainer(env, copy.copy(args), rng="device_philox", env_mode=a.env, collect=False, dist_ctx=ctx)
+        if timed:
+            t.eng.ro.use_graph = not a.no_graph
+            t.eng.ro.overlap = not a.no_overlap
+            t.eng.ro.time_light = True  # before the warm-up, so the (timed) graph is captured outside the timed region
+        return t
+
+    tr = trainer()
+    eng = tr.eng
+    settlers = []
+
+    def settler():
+        """the settling steps' own trainer (one process, env on the device): made after the timed trainer's warm-up, so
+        that the streams it creates come after the timed trainer's and its first graph launch, as every later engine's
+        do; its initial population from a forked generator leaves the torch RNG stream of what follows untouched"""
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(1)
+            settlers.append(trainer())
+        settlers[0].step()   # (graph captures)
+        return settlers[0].step
+
+    _warm_up(tr.step, a, ctx, dev, cold_probe=a.full, settler=settler if (ctx.world == 1 and timed) else None)
     if timed:  # duration of every launch of the dominant kernel in the timed region from here on
         torch.cuda.synchronize()
         eng.ro.collect_stamps()
@@ -643,11 +717,14 @@ def run_ga(a, ctx, dev):
     torch.cuda.synchronize()
     ctx.barrier()
     dt = ctx.max_over_ranks(time.perf_counter() - t0, dev)
+    settlers.clear()
     light_ms = eng.ro.light_times_ms() if timed else []
     if timed:
         eng.ro.time_light = False
+    if dump_dir:
+        dump_ga_outputs(tr, dump_dir)
     host_phase = None
-    if a.env == "host" and getattr(eng.ro, "ctx", None):
+    if a.full and a.env == "host" and getattr(eng.ro, "ctx", None):
         # two more generations with HIP events around every cohort-cycle's copies and launch + host clocks around the
         # waits and the env (outside the timed region: the events cost a few microseconds per cycle)
         eng.ro.phase_us = np.zeros(6)
@@ -798,7 +875,7 @@ def run_ga(a, ctx, dev):
             gen_bytes = cycle_bytes * eng.n_cycles
             out["roofline"]["generation"] = {"algorithmic_bytes": gen_bytes, "achieved": gen_bytes * gens_per_s / 1e9,
                                              "frac": gen_bytes * gens_per_s / 1e9 / HBM_PEAK_GBS}
-        if not a.no_cpu_baseline and ctx.world == 1:
+        if a.full and not a.no_cpu_baseline and ctx.world == 1:
             out["cpu_baseline"] = cpu_baseline(pop, a.hof, a.limit)
             try:
                 workers = host_cores()["usable"]   # one process per core this box gives us (count in `cores`)

@@ -593,6 +593,53 @@ def test_bench_settling_steps_are_untimed_and_the_same_on_every_rank(monkeypatch
     assert bench._warm_up(lambda: calls.append(1), a, Ctx(), None) == bench.MAX_SETTLE_STEPS
 
 
+def test_bench_settling_steps_can_run_on_a_second_engine(monkeypatch):
+    """with a settler the W warm-up steps are the timed engine's and every settling step goes to the settler's engine (made
+    once, its set-up not counted as settling time): the timed engine then enters its K steps after exactly W generations"""
+    import sys
+    import time
+    import types
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, repo)
+    import bench
+    monkeypatch.setattr(bench.torch.cuda, "synchronize", lambda *a, **k: None)
+    timed, settled, made = [], [], []
+
+    def settler():
+        made.append(1)
+        time.sleep(0.05)   # a set-up longer than the settling time itself
+
+        def step():
+            settled.append(1)
+            time.sleep(0.002)
+        return step
+
+    class Ctx:
+        world = 1
+
+        def max_over_ranks(self, s, dev):
+            return s
+
+    a = types.SimpleNamespace(warmup=3, settle_ms=40.0)
+    n = bench._warm_up(lambda: timed.append(1), a, Ctx(), None, settler=settler)
+    assert len(timed) == 3 and made == [1] and n == a.settle_steps == len(settled) and 5 <= n <= 30
+    a = types.SimpleNamespace(warmup=3, settle_ms=0.0)
+    assert bench._warm_up(lambda: timed.append(1), a, Ctx(), None, settler=settler) == 0 and made == [1]
+
+
+def test_bench_dump_outputs_is_refused_where_the_run_is_not_reproducible():
+    """--dump-outputs needs the timed generations to follow a fixed number of others (ga, env on the device, one GPU):
+    other forms are refused before anything touches a GPU"""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for more in (["--workload", "es"], ["--env", "host"], ["--shard-of", "4"], ["--gpus", "2"]):
+        p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--dump-outputs", "unused"] + more, cwd=repo,
+                           capture_output=True, text=True, timeout=120)
+        assert p.returncode != 0 and "--dump-outputs" in (p.stderr + p.stdout), more
+        assert not os.path.exists(os.path.join(repo, "unused"))
+
+
 def test_host_rollout_entry_points_refuse_bad_descriptors():
     """argument errors of the host-side rollouts are COEVO_ERR_ARG before any GPU call (the error convention of the boundary:
     return codes, no exceptions, nothing dereferenced that was not checked)"""
@@ -687,9 +734,23 @@ def test_host_placement_is_a_pure_function_of_mask_and_sysfs_strings():
     assert _choose("garbage", "", "", "", 0, 1)[2] == 0
 
 
+def _gpu_numa_node():
+    """the NUMA node sysfs gives for device 0's PCI function; -1 without a GPU or where the node is not known"""
+    if not torch.cuda.is_available():
+        return -1
+    p = torch.cuda.get_device_properties(0)
+    path = f"/sys/bus/pci/devices/{p.pci_domain_id:04x}:{p.pci_bus_id:02x}:{p.pci_device_id:02x}.0/numa_node"
+    try:
+        with open(path) as f:
+            return max(-1, int(f.read().strip()))
+    except (OSError, ValueError):
+        return -1
+
+
 def test_host_placement_of_a_context_on_this_machine():
-    """coevo_host_rollout_placement without a GPU: the node of the device is unknown (-1), so the context takes the caller's
-    own node; its CPUs lie inside the affinity mask, the caller's own CPU stays allowed afterwards (the pin is per rollout)"""
+    """coevo_host_rollout_placement: the node of the device is the one sysfs gives for its PCI function (without a GPU it
+    is unknown, -1, and the context takes the caller's own node); its CPUs lie inside the affinity mask, the caller's own
+    CPU stays allowed afterwards (the pin is per rollout)"""
     from coevonet_amd import lib as L
     lib = L.load()
     before = os.sched_getaffinity(0)
@@ -697,7 +758,7 @@ def test_host_placement_of_a_context_on_this_machine():
     assert ctx
     try:
         pl = L.host_placement(ctx)
-        assert pl["gpu_numa_node"] == -1
+        assert pl["gpu_numa_node"] == _gpu_numa_node()
         if len(before) >= 2:
             assert pl["pinned"] and len(pl["cpus"]) == 2 and set(pl["cpus"]) <= before and len(set(pl["cpus"])) == 2
         assert os.sched_getaffinity(0) == before
