@@ -4,7 +4,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .fcnetwork import FCNetwork
+from .fcnetwork import FCNetwork, FCNetworkHalf
 
 
 class Agent:
@@ -15,7 +15,8 @@ class Agent:
 
     def mutate(self, noise_std):
         """GA mutation: every parameter (LayerNorm affine included) += N(0, noise_std), drawn with the global torch
-        generator in parameters() order, exactly as agent.py:25-29 does (host_reference RNG mode)."""
+        generator in parameters() order, exactly as agent.py:25-29 does (host_reference RNG mode).  On a float16 net the
+        Linear tensors are half: torch adds the fp32 noise in fp32 and rounds the sum once to half, as in the reference."""
         for param in self.model.parameters():
             noise = torch.normal(0, noise_std, size=param.size())
             param.data += noise
@@ -46,7 +47,9 @@ class MPEAgent(Agent):
     def __init__(self, env, args, role):
         self.input_channels = env.observation_space(role).shape[-1]
         self.n_actions = env.action_space(role).n
-        self.model = FCNetwork(self.input_channels, self.n_actions, args.precision)
+        # MPE/fcnetwork.py:13: precision "float16" makes fc1 / fc2 / output half (FCNetwork here is float32-only)
+        net = FCNetworkHalf if args.precision == "float16" else FCNetwork
+        self.model = net(self.input_channels, self.n_actions, args.precision)
         # the reference builds an Adam optimizer here (MPE/mpe_agent.py:20) that nothing ever steps; it draws no
         # random numbers, so leaving it out changes no result and saves ~15 ms per agent
         self.optimizer = None

@@ -288,6 +288,10 @@ def _linear_mask(D):
 
 class ESTrainer:
     def __init__(self, env, args, rng=None, env_mode=None, collect=True, dist_ctx=None):
+        if getattr(args, "precision", "float32") != "float32":
+            # the reference runs Co-ES in float16 too (evolutionary_strategy.py:11-20); its fp16 ES kernels are not built
+            raise ValueError(f"Co-ES with precision {args.precision} is not supported (float16 covers Co-GA nets and "
+                             "play_game only)")
         self.env, self.args, self.collect = env, args, collect
         self.rng = rng or getattr(args, "coevo_rng", "host_reference")
         env_mode = env_mode or getattr(args, "coevo_env", "device")

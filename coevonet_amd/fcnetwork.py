@@ -178,3 +178,108 @@ class FCNetwork:
 
     def set_perturbable_weights(self, weights_to_set, args):
         self.set_weights_ES(weights_to_set, args, self.get_perturbable_layers())
+
+
+LINEAR_KEYS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias", "output.weight", "output.bias")
+
+
+class FCNetworkHalf(FCNetwork):
+    """``FCNetwork(input_channels, n_actions, "float16")`` of the reference (MPE/fcnetwork.py:13-22): fc1 / fc2 / output
+    hold float16 tensors, the two LayerNorms stay float32.  ``FCNetwork`` itself is float32-only, so the half net is this
+    sibling with the same surface; ``MPEAgent`` builds it when ``args.precision == "float16"``.
+
+    Each parameter is its own torch-CPU tensor of the reference's dtype, so ``param.data += noise`` (Agent.mutate) is the
+    reference's own half-precision update (computed in fp32, rounded once to half).  ``flat()`` is the fp32 image in
+    parameters() order (fp16 values are exact in fp32); the forward runs in libcoevo's fp16 kernel
+    (coevo_fc16_forward_argmax), never on the CPU."""
+
+    def __init__(self, input_channels, n_actions, precision="float16"):
+        if precision != "float16":
+            raise ValueError(f"FCNetworkHalf is the float16 net, not {precision}")
+        # the fp32 init consumes the global generator exactly like the reference's nn.Linear(...) constructions; the
+        # reference then converts the Linear layers with .to(float16) (round to nearest even)
+        full = FCNetwork(input_channels, n_actions, "float32")
+        self.dtype = torch.float16
+        self.precision = precision
+        self.input_channels, self.n_actions = full.input_channels, full.n_actions
+        self._params = OrderedDict(
+            (k, v.detach().to(torch.float16 if k in LINEAR_KEYS else torch.float32).clone())
+            for k, v in full._params.items())
+        p = self._params
+        self.fc1 = _Layer("fc1", p["fc1.weight"], p["fc1.bias"], False)
+        self.ln1 = _Layer("ln1", p["ln1.weight"], p["ln1.bias"], True)
+        self.fc2 = _Layer("fc2", p["fc2.weight"], p["fc2.bias"], False)
+        self.ln2 = _Layer("ln2", p["ln2.weight"], p["ln2.bias"], True)
+        self.output = _Layer("output", p["output.weight"], p["output.bias"], False)
+        self.layers = [self.fc1, self.fc2, self.output]
+
+    def load_state_dict(self, sd, strict=True):
+        for k, v in self._params.items():
+            if k in sd:
+                v.copy_(torch.as_tensor(sd[k]).to(v.dtype))
+            elif strict:
+                raise KeyError(f"Missing key in state_dict: {k}")
+
+    def flat(self) -> np.ndarray:
+        """the whole net in parameters() order as float32 (a copy: the parameters have two dtypes)"""
+        return np.concatenate([v.detach().to(torch.float32).numpy().ravel() for v in self._params.values()])
+
+    def set_flat(self, flat):
+        flat = torch.as_tensor(np.asarray(flat, dtype=np.float32))
+        off = 0
+        for v in self._params.values():
+            n = v.numel()
+            v.copy_(flat[off:off + n].view(v.shape).to(v.dtype))
+            off += n
+
+    def set_weights_ES(self, flat_weights, args, layers=None):
+        if layers is None:
+            layers = self.get_perturbable_layers()
+        i = 0
+        for l in layers:
+            for t in (l.weight, l.bias):
+                n = t.numel()
+                t.copy_(torch.as_tensor(np.asarray(flat_weights[i:i + n])).reshape(tuple(t.shape)).to(t.dtype))
+                i += n
+
+    def _device_forward(self, x):
+        return HalfPolicySet([self]).forward(0, x)
+
+
+class HalfPolicySet:
+    """Float16 nets packed ONCE into one device fp16 slab, with the launch buffers of a one-row forward kept: what a game
+    (play_game over an AEC env) needs per agent-step is then an observation copy, one coevo_fc16_forward_argmax launch and
+    the action read back.  The nets must not change while the set is in use (a game never mutates them)."""
+
+    def __init__(self, nets, device="cuda"):
+        self.nets = list(nets)
+        self.dev = device
+        strides = [L.fc16_slab_stride(n.input_channels) for n in self.nets]
+        offs = np.concatenate([[0], np.cumsum(strides)[:-1]]).astype(np.int64)
+        self.slab = torch.zeros(int(sum(strides)), dtype=torch.int32, device=device)
+        self.tasks = []
+        for n, off in zip(self.nets, offs):
+            D = n.input_channels
+            flat = torch.from_numpy(n.flat()).to(device)
+            L.call("coevo_fc16_pack", L._p(flat), self.slab.data_ptr() + 4 * int(off), 1, D)
+            t = np.zeros(1, dtype=L.TASK_DTYPE)
+            t[0] = (int(off), 0, 1, D, 0)
+            self.tasks.append(L.tasks_to_device(t, device))
+        self.obs = torch.zeros(1, L.OBS_STRIDE, dtype=torch.float32, device=device)
+        self.actions = torch.zeros(1, dtype=torch.int32, device=device)
+        self.logits = torch.zeros(1, L.LOGIT_STRIDE, dtype=torch.float32, device=device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def forward(self, i, x):
+        """(fp16 logits on the CPU, first-max action) of net i on one observation; ValueError like MPE/fcnetwork.py:39-90"""
+        net = self.nets[i]
+        D = net.input_channels
+        x = torch.as_tensor(x).to(torch.float32).reshape(-1)   # fp16 values are exact in fp32; the kernel rounds to fp16
+        if x.numel() != D:
+            raise ValueError(f"expected an observation of width {D}, got {x.numel()}")
+        self.obs[0, :D] = x.to(self.dev)
+        self.status.zero_()
+        L.call("coevo_fc16_forward_argmax", L._p(self.slab), L._p(self.tasks[i]), 1, 1, L._p(self.obs), L._p(self.actions),
+               L._p(self.logits), L._p(self.status))
+        L.raise_on_status(self.status)
+        return self.logits[0, :net.n_actions].cpu().to(torch.float16), int(self.actions.item())

@@ -43,9 +43,12 @@ def create_agent(env, args, role=None):
 
 
 def preprocess_observation(obs, args):
+    """utils/game_logic_functions.py:69-80 for the MPE observation: float16 or float32 as args.precision says"""
     obs = torch.from_numpy(obs)
     if args.precision == "float16":
-        raise ValueError("Unsupported precision: float16")
+        return obs.to(torch.float16)
+    if args.precision != "float32":
+        raise ValueError(f"Unsupported precision: {args.precision}")
     return obs.to(torch.float32)
 
 
@@ -59,16 +62,25 @@ def diversity_penalty(individual_weights, population_weights, args, sigma=None):
 
 
 def _play_mpe_aec(env, player1, player2, adversary, args, eval):
-    """play_MPE (:123-212) over a foreign AEC env; forwards on the GPU one step at a time."""
+    """play_MPE (:123-212) over a foreign AEC env; forwards on the GPU one step at a time.  Float16 nets are packed once
+    per game (HalfPolicySet), so an agent-step moves an observation and an action, not a net."""
+    from .fcnetwork import FCNetworkHalf, HalfPolicySet
     rewards = {"agent_0": 0, "agent_1": 0, "adversary_0": 0}
     models = {"agent_0": player1, "agent_1": player2, "adversary_0": adversary}
+    half = None
+    if all(isinstance(m, FCNetworkHalf) for m in models.values()):
+        half = HalfPolicySet(list(models.values()))
+        slot_of = {name: i for i, name in enumerate(models)}
     timesteps = 0
     limit = args.max_evaluation_steps if eval else args.max_timesteps_per_episode
     for agent in env.agent_iter():
         if agent not in models:
             raise ValueError(f"Unknown Agent during play_game: {agent}")
         obs = preprocess_observation(env.observe(agent), args)
-        action = models[agent].determine_action(obs, args)
+        if half is not None:
+            action = half.forward(slot_of[agent], obs)[1]   # FCNetworkHalf.determine_action, net already on the device
+        else:
+            action = models[agent].determine_action(obs, args)
         if action > 4:
             raise ValueError(f"ERROR: the action {action} is greater than 4")
         env.step(action)
@@ -150,10 +162,13 @@ def _play_atari_device(env, player1, player2, args, eval):
 
 def play_MPE(env, player1, player2, adversary, args, eval):
     """utils/game_logic_functions.py:123-212 - one episode on an ALREADY RESET env (play_game resets): the whole episode
-    on the device when env and policies are this package's, else the AEC loop with one device forward per agent-step"""
-    from .fcnetwork import FCNetwork
+    on the device when env and policies are this package's, else the AEC loop with one device forward per agent-step.
+    float16 nets always take the AEC loop (their forward is coevo_fc16_forward_argmax; the device rollout's cycle kernels
+    read fp32 slabs only)."""
+    from .fcnetwork import FCNetwork, FCNetworkHalf
+    models = (player1, player2, adversary)
     ours = isinstance(env, SimpleAdversaryAEC) and env.seed_value is not None and \
-        all(isinstance(m, FCNetwork) for m in (player1, player2, adversary))
+        all(isinstance(m, FCNetwork) and not isinstance(m, FCNetworkHalf) for m in models)
     if ours:
         return _play_mpe_device(env, player1, player2, adversary, args, eval)
     return _play_mpe_aec(env, player1, player2, adversary, args, eval)

@@ -907,6 +907,11 @@ class GATrainer:
     exactly these steps)."""
 
     def __init__(self, env, args, rng=None, env_mode=None, collect=True, dist_ctx=None):
+        if getattr(args, "precision", "float32") != "float32":
+            # float16 nets have their forward (coevo_fc16_forward_argmax) and play_game; the population engine's fp16
+            # rollout, breeding and selection kernels are not built, so the trainer refuses before touching the GPU
+            raise ValueError(f"Co-GA training with precision {args.precision} is not supported (float16 covers the nets, "
+                             "create_agent / mutate / clone, checkpoints and play_game)")
         self.env, self.args, self.collect = env, args, collect
         self.rng = rng or getattr(args, "coevo_rng", "host_reference")
         env_mode = env_mode or getattr(args, "coevo_env", "device")

@@ -22,7 +22,8 @@ STAMP_SLOTS = 32
 ST_NAMES = {1: "input contains inf or NaN", 2: "output contains inf or NaN after fc1",
             4: "output contains inf or NaN after fc2", 8: "output contains inf or NaN",
             16: "no action selected (current_best_position = -1)",
-            32: "persistent rollout: a workgroup timed out waiting for the other rows of its games (COEVO_ST_SYNC_TIMEOUT)"}
+            32: "persistent rollout: a workgroup timed out waiting for the other rows of its games (COEVO_ST_SYNC_TIMEOUT)",
+            64: "fp16 forward: a task with a bad width, row count or unaligned net offset was skipped (COEVO_ST_BAD_TASK)"}
 
 DQN_LOGIT_STRIDE = 32
 DQN_FC1_TILED = 0x100   # COEVO_DQN_FC1_TILED: or-ed into the channel argument of the layout-dependent DeepQN entry points
@@ -139,6 +140,11 @@ _SIGS = {
     "coevo_fc_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "coevo_fc_forward_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "coevo_fc16_slab_stride": (C.c_int64, [C.c_int]),
+    "coevo_fc16_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "coevo_fc16_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "coevo_fc16_forward_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "coevo_fc_forward_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "coevo_mpe_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, PCG64State, C.c_uint64, C.c_void_p]),
@@ -341,6 +347,10 @@ def fc_param_count(D):
 
 def fc_slab_stride(D):
     return int(load().coevo_fc_slab_stride(D))
+
+
+def fc16_slab_stride(D):
+    return int(load().coevo_fc16_slab_stride(D))
 
 
 def host_tensor(ctx, shape, dtype):

@@ -26,7 +26,8 @@
 extern "C" {
 #endif
 
-#define COEVO_VERSION 103   /* 103: coevo_mpe_rollout_persistent, coevo_rollout_desc.sync_words / .pack (192 bytes), coevo_final_pack; 102: host-cores placement (coevo_host_placement_choose, coevo_host_rollout_placement / _alloc),
+#define COEVO_VERSION 103   /* 103 (still): + the float16 nets (coevo_fc16_*, COEVO_ST_BAD_TASK), additions only - a checkpoint's
+                             * coevo_version does not tell a build with them from one without; 103: coevo_mpe_rollout_persistent, coevo_rollout_desc.sync_words / .pack (192 bytes), coevo_final_pack; 102: host-cores placement (coevo_host_placement_choose, coevo_host_rollout_placement / _alloc),
                              * wide small-shard cycle kernel; 101: offspring noise = Philox4x32-7 (100: -10; other numbers for the same seed), host-cores
                              * rollout entry points, coevo_noise_rounds */
 
@@ -43,6 +44,8 @@ extern "C" {
 #define COEVO_ST_NO_ACTION 16
 #define COEVO_ST_SYNC_TIMEOUT 32 /* coevo_mpe_rollout_persistent: a workgroup waited too long for the other rows of its games (no
                                   * reference counterpart: more such launches side by side than the device holds at once) */
+#define COEVO_ST_BAD_TASK 64     /* coevo_fc16_forward_argmax: a task with D not 8 / 10, n_rows outside 1 .. COEVO_FC_MAX_ROWS or a
+                                  * net_off that is not a multiple of 4 words was skipped (its rows are not written) */
 
 /* FCNetwork geometry (MPE/fcnetwork.py:14-22) */
 #define COEVO_FC_H1 512
@@ -98,6 +101,22 @@ int coevo_fc_forward_argmax(const float *slab, const coevo_fc_task *tasks, int n
 int coevo_fc_forward_merged(const float *slab, const coevo_fc_task *heavy_tasks, int n_heavy, int heavy_max_rows,
                             const coevo_fc_task *light_tasks, int n_light, int light_max_rows, const float *obs,
                             int32_t *actions, float *logits, int32_t *status, void *stream);
+
+/* ---------------------------------------------------------------- float16 nets ----------------------------- */
+/* FCNetwork with args.precision == "float16" (MPE/fcnetwork.py:13: fc1 / fc2 / output in half, LayerNorm in fp32).
+ * The fp16 slab stores the Linear weights as 2-byte values (W2h [64][256][8]: 16-byte pieces of 8 k of one column;
+ * W1h [D][512]; W3h [5][256]), biases upcast to fp32 and the LayerNorm affine in fp32: about half the bytes of the fp32
+ * slab.  Strides and coevo_fc_task.net_off count 32-bit words, as for the fp32 slab.  Arithmetic: DESIGN.md
+ * "float16 nets" - the canonical fp32 chains on fp16 values, rounded to fp16 after every Linear and LayerNorm. */
+int64_t coevo_fc16_slab_stride(int D);   /* 32-bit words between consecutive nets in an fp16 slab */
+/* flat[n][P] fp32 (canonical order; Linear entries rounded to fp16 to nearest even, exact for fp16 values) <-> slab */
+int coevo_fc16_pack(const float *flat, void *slab, int n, int D, void *stream);
+int coevo_fc16_unpack(const void *slab, float *flat, int n, int D, void *stream);
+/* coevo_fc_forward_argmax for fp16 slabs: logits are fp16 values (stored as fp32), actions the first maximum.  net_off must
+ * be a multiple of 4 words (every net of a slab packed at a multiple of coevo_fc16_slab_stride is); a task that breaks
+ * this or the D / n_rows rules is skipped with COEVO_ST_BAD_TASK. */
+int coevo_fc16_forward_argmax(const void *slab, const coevo_fc_task *tasks, int n_tasks, int max_rows_per_task,
+                              const float *obs, int32_t *actions, float *logits, int32_t *status, void *stream);
 
 /* ---------------------------------------------------------------- device-side MPE simple_adversary ---------- */
 /* Replaces env.reset/observe/step/last of play_MPE (utils/game_logic_functions.py:123-212, :217) for E env
