@@ -727,7 +727,7 @@ class GAEngine:
         segs = [(ph * per_phase, per_phase, base + ph * self.pop * self.hof + self.lo * self.hof) for ph in range(3)]
         if gen > 0:
             segs.append((self.n_main, N_EVAL, self._ordinal_base(gen - 1) + M))
-        ro.reset_segments(segs, arm=(0, self.n_cycles))   # one launch (three phases + the evaluation games + clock stamps)
+        ro.reset_segments(segs, arm=(None, self.n_cycles))   # one launch (three phases + evaluation games + every cohort's arm)
         if self._packed_exchange():   # (the closing step + this rank's all-gather record: in the persistent launch, if it is one)
             ro.enqueue(self.n_cycles, armed=True, pack=self._pack_args())
         else:

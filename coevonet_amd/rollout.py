@@ -224,6 +224,8 @@ class DeviceRollout:
         self.overlap = True
         self.use_graph = True
         self._graphs = {}
+        # what the last arming reset launch cleared and nobody has run on since: {cohort: (n_cycles, stamps re-armed?)}
+        self._armed = {}
         self._timed_ms = []
         self._span_ms, self._span_cycles = [], 0
         self.ctx = L.load().coevo_rollout_ctx_create(int(timing_pairs))
@@ -277,22 +279,45 @@ class DeviceRollout:
                int(first_ordinal))
 
     def reset_segments(self, segs, arm=None):
-        """several (game_first, n_games, first_ordinal) resets in ONE launch (<= 4 segments).  arm = (cohort k, n_cycles):
-        the launch also re-arms the clock stamps of that cohort's timed chain (time_light) and zeroes the sync words of its
-        persistent rollout launch, which then need no launch of their own - the caller passes armed=True to the enqueue that
-        follows"""
+        """several (game_first, n_games, first_ordinal) resets in ONE launch (<= 4 segments).  arm = (k, n_cycles), k a cohort
+        or None for all of them: the launch also re-arms the clock stamps of those cohorts' timed chains (time_light) and zeroes
+        the sync words of their persistent rollout launches, which then need no launch of their own - the caller passes
+        armed=True to the enqueue / enqueue_cohort that follows.  Cohort k's sync words and its n_cycles * STAMP_SLOTS stamp
+        pairs (laid out for this n_cycles) are one range each, and so are all K cohorts' together."""
         arr = (L.ResetSeg * len(segs))(*[L.ResetSeg(int(a), int(b), int(c)) for a, b, c in segs])
-        if arm is not None and (self.time_light or self.sync_words is not None):
-            # ... and, in the same launch, zeroes the sync words of that cohort's persistent rollout launch (which then needs no
-            # clearing launch of its own either: desc.sync_cleared, set by the enqueue that is passed armed=True)
+        if arm is not None:
             k, n_cycles = arm
-            stamps = (self.stamps.data_ptr() + 16 * L.STAMP_SLOTS * int(k) * int(n_cycles)) if self.time_light else None
-            sync = (self.sync_words.data_ptr() + 4 * int(k) * self.sync_words_per_cohort) if self.sync_words is not None else None
-            L.call("coevo_mpe_reset_multi_prep", L._p(self.state), self.plan.n_games, _ct.cast(arr, _ct.c_void_p), len(segs),
-                   self.rng, stamps, int(n_cycles) * L.STAMP_SLOTS if stamps else 0, sync,
-                   self.sync_words_per_cohort if sync else 0)
+            n_cycles = int(n_cycles)
+            if k is not None and not 0 <= int(k) < self.n_cohorts:
+                raise ValueError(f"arm: cohort {k} of a rollout with {self.n_cohorts}")
+            if not 0 < n_cycles <= self.stamp_cycles:
+                raise ValueError(f"arm: {n_cycles} cycles (1 .. {self.stamp_cycles})")
+            first, count = (0, self.n_cohorts) if k is None else (int(k), 1)
+            stamps = (self.stamps.data_ptr() + 16 * L.STAMP_SLOTS * first * n_cycles) if self.time_light else None
+            sync = (self.sync_words.data_ptr() + 4 * first * self.sync_words_per_cohort) if self.sync_words is not None else None
+            if stamps or sync:
+                L.call("coevo_mpe_reset_multi_prep", L._p(self.state), self.plan.n_games, _ct.cast(arr, _ct.c_void_p), len(segs),
+                       self.rng, stamps, count * n_cycles * L.STAMP_SLOTS if stamps else 0, sync,
+                       count * self.sync_words_per_cohort if sync else 0)
+            else:
+                L.call("coevo_mpe_reset_multi", L._p(self.state), self.plan.n_games, _ct.cast(arr, _ct.c_void_p), len(segs),
+                       self.rng)
+            for c in range(first, first + count):
+                self._armed[c] = (n_cycles, bool(self.time_light))
             return
         L.call("coevo_mpe_reset_multi", L._p(self.state), self.plan.n_games, _ct.cast(arr, _ct.c_void_p), len(segs), self.rng)
+
+    def _take_arm(self, cohorts, n_cycles, armed):
+        """armed=True holds only if the last arming reset covered every cohort of this call for this n_cycles (and, timed, its
+        stamps); the call then consumes the arm - its rollout leaves tags and stamps behind"""
+        if armed:
+            for c in cohorts:
+                if self._armed.get(c) != (int(n_cycles), bool(self.time_light)):
+                    raise ValueError(f"armed=True, but cohort {c} was not armed for {n_cycles} cycles"
+                                     f"{' with timed stamps' if self.time_light else ''} by reset_segments(arm=...) since its "
+                                     f"last rollout (armed: {self._armed})")
+        for c in cohorts:
+            self._armed.pop(c, None)
 
     def run(self, n_cycles):
         """enqueue n_cycles world cycles + the rewards kernel.  With use_graph the enqueue is captured once per
@@ -300,6 +325,7 @@ class DeviceRollout:
         graph edge instead of a cross-stream event round trip (316 vs 266 generations/s on cfg2)."""
         n_cycles = int(n_cycles)
         assert n_cycles <= self.stamp_cycles
+        self._take_arm(range(self.n_cohorts), n_cycles, False)
         ctx = self.ctx if (self.overlap or self.n_cohorts > 1) else None
         timed = bool(self.time_light)
         if self.use_graph:
@@ -327,7 +353,9 @@ class DeviceRollout:
         final=False: without the closing step (the caller runs enqueue_final_step itself);
         pack (with final=True; see enqueue_final_step): the closing step also writes this rank's all-gather record - inside the
         persistent launch when the rollout is one (coevo_rollout_desc.pack);
-        armed: the reset launch in front of it re-armed the clock stamps (reset_segments(arm=...))"""
+        armed: the reset launch in front of it re-armed the clock stamps and zeroed the sync words of EVERY cohort for this
+        n_cycles (reset_segments(arm=(None, n_cycles)), or arm=(0, n_cycles) with one cohort); raises ValueError otherwise"""
+        self._take_arm(range(self.n_cohorts), n_cycles, armed)
         self.desc.light_stamps = L._p(self.stamps) if self.time_light else None
         self.desc.n_cycles = int(n_cycles)
         self.desc.stamps_armed = 1 if (armed and self.time_light) else 0
@@ -353,8 +381,10 @@ class DeviceRollout:
 
     def enqueue_cohort(self, k, n_cycles, stream, armed=False):
         """the cycle chain of cohort k alone on `stream` (a torch stream), without the closing step: callers that breed
-        and reset cohort by cohort run one such call per cohort on its own stream, then enqueue_final_step() once"""
+        and reset cohort by cohort run one such call per cohort on its own stream, then enqueue_final_step() once.
+        armed: reset_segments(arm=(k, n_cycles)) (or arm=(None, n_cycles)) ran in front of it; raises ValueError otherwise"""
         assert self.n_cohorts > 1 and self.desc.merged
+        self._take_arm((int(k),), n_cycles, armed)
         p = self.plan
         hb, he = int(p.heavy_begin_np[k]), int(p.heavy_begin_np[k + 1])
         lb, le = int(p.light_begin_np[k]), int(p.light_begin_np[k + 1])
