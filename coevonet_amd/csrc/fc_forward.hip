@@ -523,10 +523,15 @@ __device__ __forceinline__ void fmac_block16(float (&acc)[R], const float (&xv)[
 #undef COEVO_FMAC_K
 }
 
-template <int R, int MODE, int FC2 = FC2_MFMA>
+// RES (FC2_MFMA only): the task's net is one of the population's cache-resident nets (COEVO_TASK_RESIDENT): its W2 stream
+// uses plain loads, which keep the lines in the Infinity Cache for the next env-cycle's read; every other net streams with nt
+// loads, which do not evict them (profiles/r06_mall_residency.md).  A template argument, dispatched once per workgroup: the
+// cache policy is an immediate of the load instruction.
+template <int R, int MODE, int FC2 = FC2_MFMA, bool RES = false>
 __device__ __forceinline__ void fc_policy_body_c(const FcArgs &a, FcSmemC<R> &sm, const coevo_fc_task *tasks, int first,
                                                  int n_tasks)
 {
+    static_assert(!RES || FC2 == FC2_MFMA, "the vector-ALU form streams with plain loads already");
     static_assert((MODE == MODE_FUSED || MODE == MODE_OBS) && R * NACT <= 64 && R <= 8, "the lean merged cycle kernel");
     typedef float f32x4_acc __attribute__((ext_vector_type(4)));
     constexpr int NG = FcSmemC<R>::NG;
@@ -710,7 +715,7 @@ __device__ __forceinline__ void fc_policy_body_c(const FcArgs &a, FcSmemC<R> &sm
         float4 bufA[U], bufB[U];
         auto issue = [&](float4 (&buf)[U], int kq) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) buf[u] = load_stream16(wp + (size_t)(kq + u) * 64);
+            for (int u = 0; u < U; ++u) buf[u] = RES ? wp[(size_t)(kq + u) * 64] : load_stream16(wp + (size_t)(kq + u) * 64);
         };
         auto consume = [&](const float4 (&buf)[U], int kq) {
 #pragma unroll
@@ -1526,7 +1531,14 @@ __global__ __launch_bounds__(256, 4) void fc_cycle16_kernel(FcArgs a)
         fc_policy_mfma16_body<MODE>(a, sm.heavy, a.tasks[blockIdx.x]);
     else
 #if COEVO_COMPACT
-        fc_policy_body_c<R, MODE>(a, sm.light, a.light_tasks, (int)blockIdx.x - a.n_heavy, a.n_light);
+    {
+        const int li = (int)blockIdx.x - a.n_heavy;
+        // the device-env launch only: a resident net is read with plain loads (workgroup-uniform, once per workgroup)
+        if (MODE == MODE_FUSED && li < a.n_light && (a.light_tasks[li].reserved & COEVO_TASK_RESIDENT))
+            fc_policy_body_c<R, MODE, FC2_MFMA, MODE == MODE_FUSED>(a, sm.light, a.light_tasks, li, a.n_light);
+        else
+            fc_policy_body_c<R, MODE>(a, sm.light, a.light_tasks, li, a.n_light);
+    }
 #else
         fc_policy_body<R, MODE, 1>(a, sm.light, a.light_tasks, (int)blockIdx.x - a.n_heavy, a.n_light);
 #endif

@@ -112,6 +112,40 @@ def cohort_partition(n_local, K):
     return bounds, np.searchsorted(bounds[1:], np.arange(n_local), side="right").astype(np.int32)
 
 
+# Nets of the population kept resident in the Infinity Cache (256 MiB) across the env-cycles of a rollout, in MB (COEVO_RESIDENT_MB;
+# "all" = every net, 0 = none).  A cycle of the full launch re-reads all 600 per-individual nets (336 MB) in the same order: under
+# any LRU-like policy nothing survives to the next cycle.  A fixed prefix of every cohort's individuals is read with plain loads
+# instead (COEVO_TASK_RESIDENT) and stays in the cache; the rest streams from HBM with nt loads, which do not evict it
+# (profiles/r06_mall_residency.md: the budget sweep).  The Hall of Fame, elite and stale nets count against the budget.
+RESIDENT_MB_DEFAULT = 224
+
+
+def resident_budget_bytes():
+    v = os.environ.get("COEVO_RESIDENT_MB", "").strip().lower()
+    if v == "all":
+        return float("inf")
+    return (float(v) if v else RESIDENT_MB_DEFAULT) * 1e6
+
+
+def resident_enabled(env, heavy_rows, n_local, pop):
+    """cache-resident nets for the lean device-env launch of the whole population only (16-row shared-opponent tasks, every
+    individual on this GPU); the host env, the small / persistent shard forms and the 32-row tiles keep every flag clear"""
+    return env == "device" and heavy_rows == 16 and n_local >= pop
+
+
+def resident_prefix(budget_bytes, fixed_bytes, individual_bytes, bounds):
+    """-> how many individuals of each cohort (the first ones of its range [bounds[k], bounds[k+1])) keep their nets of every
+    role resident: the budget left after `fixed_bytes`, split evenly over the cohorts, in whole individuals (all roles)"""
+    K = len(bounds) - 1
+    sizes = np.diff(np.asarray(bounds, dtype=np.int64))
+    left = budget_bytes - fixed_bytes
+    if left <= 0 or K <= 0:
+        return np.zeros(K, dtype=np.int64)
+    if left == float("inf"):
+        return sizes
+    return np.minimum(sizes, int(left // (K * individual_bytes)))
+
+
 DEFAULT_COHORTS = 1       # independent game cohorts per rollout (rollout.RolloutPlan._assign_cohorts); see DESIGN.md
 DEVICE_LOOP_COHORTS = 2   # ... in the host-free loop, where their launches are enqueued eagerly and do overlap
 SMALL_SHARD = 80          # ... unless a rank holds fewer individuals per role than this: then one chain
@@ -204,14 +238,25 @@ class GAEngine:
             # cohort whose [bounds[k], bounds[k+1]) holds it
             per_ind = np.repeat(cohort_partition(self.n_local, self.K)[1], self.hof)
             game_cohort = np.concatenate([per_ind, per_ind, per_ind, np.full(N_EVAL, self.K - 1)]).astype(np.int32)
+        resident = resident_enabled(env, heavy_rows, self.n_local, pop)
+
+        def resident_nets():
+            if not resident:
+                return ()
+            ind_bytes = sum(4 * self.stride[r] for r in ROLES)
+            n = resident_prefix(resident_budget_bytes(), (hof + elites + 1) * ind_bytes, ind_bytes, self.cohort_bounds)
+            return [ids[("pop", r, self.lo + i)] for r in ROLES for k in range(self.K)
+                    for i in range(int(self.cohort_bounds[k]), int(self.cohort_bounds[k]) + int(n[k]))]
+
         try:
             self.plan = RolloutPlan(np.array(games), net_off, net_D, device=device, heavy_rows=heavy_rows,
-                                    n_cohorts=self.K, game_cohort=game_cohort, row_order=row_order)
+                                    n_cohorts=self.K, game_cohort=game_cohort, row_order=row_order,
+                                    resident_nets=resident_nets())
         except ValueError:  # tiny populations: the shared opponents have so few rows that they tie all games together
             self.K = 1
             self._set_cohort_bounds()
             self.plan = RolloutPlan(np.array(games), net_off, net_D, device=device, heavy_rows=heavy_rows,
-                                    row_order=row_order)
+                                    row_order=row_order, resident_nets=resident_nets())
         if env == "device":
             self.ro = DeviceRollout(self.plan, self.slab, env_seed=env_seed, timing_pairs=timing_pairs)
         else:

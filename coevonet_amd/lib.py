@@ -33,6 +33,7 @@ DQN_TASK_DTYPE = np.dtype([("net_off", "<i8"), ("row_begin", "<i4"), ("n_rows", 
 # numpy view of coevo_fc_task
 TASK_DTYPE = np.dtype([("net_off", "<i8"), ("row_begin", "<i4"), ("n_rows", "<i4"), ("D", "<i4"),
                        ("reserved", "<i4")])
+TASK_RESIDENT = 1   # coevo_fc_task.reserved bit COEVO_TASK_RESIDENT (include/coevo.h)
 
 
 class PCG64State(C.Structure):

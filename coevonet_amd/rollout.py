@@ -31,10 +31,12 @@ HEAVY_ROWS = 32     # larger row sets (shared opponents) are cut into chunks of 
 
 class RolloutPlan:
     """game_nets: int array [n_games][3] of net ids for env slots (adversary_0, agent_0, agent_1);
-    net_off / net_D: per net id, float offset inside the slab and observation width."""
+    net_off / net_D: per net id, float offset inside the slab and observation width.
+    resident_nets: net ids whose per-individual (light) tasks carry COEVO_TASK_RESIDENT - the lean device-env cycle launch
+    reads them with plain loads so that they stay in the Infinity Cache across env-cycles (cache policy only)."""
 
     def __init__(self, game_nets, net_off, net_D, device="cuda", heavy_rows=HEAVY_ROWS, n_cohorts=1,
-                 game_cohort=None, split_rows=None, row_order="class"):
+                 game_cohort=None, split_rows=None, row_order="class", resident_nets=()):
         game_nets = np.asarray(game_nets, dtype=np.int64)
         self.n_games = int(game_nets.shape[0])
         by_net = {}
@@ -88,9 +90,12 @@ class RolloutPlan:
         tasks = {"heavy": [[] for _ in range(self.n_cohorts)], "light": [[] for _ in range(self.n_cohorts)]}
         cohort_rows = np.zeros(self.n_cohorts + 1, dtype=np.int64)
 
+        resident_nets = frozenset(int(n) for n in resident_nets)
+
         def number(name, k):
             for net, rows in (heavy if name == "heavy" else light)[k]:
-                tasks[name][k].append((int(net_off[net]), len(row_game), len(rows), int(net_D[net]), 0))
+                flags = L.TASK_RESIDENT if (name == "light" and net in resident_nets) else 0
+                tasks[name][k].append((int(net_off[net]), len(row_game), len(rows), int(net_D[net]), flags))
                 for g, slot in rows:
                     row_game.append(g)
                     row_slot.append(slot)

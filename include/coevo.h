@@ -85,8 +85,12 @@ typedef struct {
     int32_t row_begin;
     int32_t n_rows;    /* 1 .. COEVO_FC_MAX_ROWS */
     int32_t D;         /* 8 or 10 */
-    int32_t reserved;
+    int32_t reserved;  /* COEVO_TASK_* bits; 0 = none */
 } coevo_fc_task;
+/* coevo_fc_task.reserved bit: the net is one of the population's cache-resident nets - a per-individual task of the lean
+ * device-env cycle launch streams it with plain loads instead of non-temporal ones, so that it stays in the Infinity Cache
+ * from one env-cycle to the next.  Cache policy only: results do not depend on it.  Every other launch ignores it. */
+#define COEVO_TASK_RESIDENT 1
 
 /* FCNetwork.forward + determine_action (MPE/fcnetwork.py:37-90) for every row of every task, one launch.
  *   obs      [rows][COEVO_OBS_STRIDE] fp32          actions [rows] int32 (first index of the maximum logit)
