@@ -171,7 +171,18 @@ def fc_forward(flat, D, obs):
 
 
 def play_game(stream, net_a0, net_a1, net_adv, limit=None, max_cycles=25, ordinal=None):
-    """-> dict(rewards=(agent_0, agent_1, adversary_0), steps, actions, min_margin, status)."""
+    """-> dict(rewards=(agent_0, agent_1, adversary_0), steps, actions, min_margin, ordinal); ValueError on a forward fault
+    (NaN / inf / no action), as the reference raises it."""
+    g = play_game_status(stream, net_a0, net_a1, net_adv, limit, max_cycles, ordinal)
+    st = g.pop("status")
+    if st:
+        raise ValueError(f"oracle forward status {st} (NaN/inf or no action)")
+    return g
+
+
+def play_game_status(stream, net_a0, net_a1, net_adv, limit=None, max_cycles=25, ordinal=None):
+    """play_game that does not raise: the dict also carries "status", the OR of oracle_fc_forward's status word over every
+    agent-step of the game (a seat without an action plays 0, as oracle_play_game does)."""
     o = stream.next_ordinal() if ordinal is None else ordinal
     rewards = (C.c_double * 3)()
     actions = np.zeros(3 * max_cycles + 3, dtype=np.int32)
@@ -180,10 +191,59 @@ def play_game(stream, net_a0, net_a1, net_adv, limit=None, max_cycles=25, ordina
     steps = lib().oracle_play_game(_fp(net_adv), _fp(net_a0), _fp(net_a1), *stream.st, o,
                                    -1 if limit is None else int(limit), max_cycles, rewards, _ip(actions),
                                    C.byref(mm), C.byref(st))
-    if st.value:
-        raise ValueError(f"oracle forward status {st.value} (NaN/inf or no action)")
     return {"rewards": [rewards[0], rewards[1], rewards[2]], "steps": steps,
-            "actions": actions[:steps].tolist(), "min_margin": float(mm.value), "ordinal": o}
+            "actions": actions[:steps].tolist(), "min_margin": float(mm.value), "ordinal": o, "status": st.value}
+
+
+class MpeState(C.Structure):
+    """mpe_state of oracle/coevo_oracle.c, for oracle_mpe_reset / _observe / _world_step"""
+    _fields_ = [("ppos", C.c_double * 2 * 3), ("pvel", C.c_double * 2 * 3), ("lm", C.c_double * 2 * 2), ("goal", C.c_int)]
+
+
+def play_game_steps(stream, net_a0, net_a1, net_adv, limit=None, max_cycles=25, ordinal=None, choose=None, poke=None):
+    """oracle_play_game's loop in Python on the oracle's own pieces (oracle_mpe_reset / _observe / _world_step,
+    oracle_fc_forward), for tests that must change one thing about a game: poke(state) edits the MpeState after the reset,
+    choose(slot, logits, first_max) -> action replaces the first-maximum rule (slot 0 adversary_0, 1 agent_0, 2 agent_1).
+    With neither it returns play_game_status's rewards, steps, actions and status bit for bit."""
+    o = stream.next_ordinal() if ordinal is None else ordinal
+    L = lib()
+    nets = [np.ascontiguousarray(n, dtype=np.float32) for n in (net_adv, net_a0, net_a1)]
+    s = MpeState()
+    L.oracle_mpe_reset(*stream.st, o, C.byref(s))
+    if poke is not None:
+        poke(s)
+    cum, rew, acc, act = [0.0] * 3, [0.0] * 3, [0.0] * 3, (C.c_int * 3)(0, 0, 0)
+    sel = world_steps = timesteps = status = 0
+    trunc, actions = False, []
+    obs, logits, st = np.zeros(10, dtype=np.float32), np.zeros(NACT, dtype=np.float32), C.c_int(0)
+    rg, ra = C.c_double(0), C.c_double(0)
+    while True:
+        agent = sel
+        L.oracle_mpe_observe(C.byref(s), agent, _fp(obs))
+        st.value = 0
+        a = L.oracle_fc_forward(_fp(nets[agent]), 8 if agent == 0 else 10, _fp(obs), _fp(logits), C.byref(st))
+        status |= st.value
+        if choose is not None:
+            a = choose(agent, logits, a)
+        if a < 0:
+            a = 0
+        actions.append(int(a))
+        sel = (agent + 1) % 3
+        act[agent] = int(a)
+        if sel == 0:
+            L.oracle_mpe_world_step(C.byref(s), act, C.byref(rg), C.byref(ra))
+            rew = [ra.value, rg.value, rg.value]
+            world_steps += 1
+            trunc = world_steps >= max_cycles
+        else:
+            rew = [0.0, 0.0, 0.0]
+        cum[agent] = 0.0
+        cum = [c + r for c, r in zip(cum, rew)]
+        acc[agent] += cum[sel]
+        timesteps += 1
+        if (limit is not None and timesteps >= limit) or trunc:
+            break
+    return {"rewards": [acc[1], acc[2], acc[0]], "steps": timesteps, "actions": actions, "ordinal": o, "status": status}
 
 
 def diversity(individual_es, population_es):
