@@ -286,4 +286,79 @@ extern "C" int coevo_mpe_rollout(const coevo_rollout_desc *d, void *ctx, int tim
     return COEVO_OK;
 }
 
+namespace coevo {
+// csrc/fc16_rollout.hip: both task tables of one cohort's env-cycle in ONE launch of the fp16 cycle kernel
+int launch_fc16_cycle(const void *slab, const coevo_fc_task *heavy, int n_heavy, const coevo_fc_task *light, int n_light,
+                      const double *state_prev, double *state_next, int n_games, const int32_t *row_game,
+                      const int32_t *row_slot, const int32_t *act_prev, int32_t *act_cur, const int32_t *game_limit, int cycle,
+                      int pos_first, int32_t *status, uint64_t *stamps, hipStream_t s);
+}
+
+// coevo_mpe_rollout for an fp16 slab: the fused env step only, one launch per env-cycle and cohort, no persistent form
+extern "C" int coevo_mpe16_rollout(const coevo_rollout_desc *d, void *ctx, int time_light, void *stream)
+{
+    if (!d || !d->slab || !d->state || !d->row_game || !d->row_slot || !d->status) return COEVO_ERR_ARG;
+    if (!d->state_alt || !d->actions_by_game) return COEVO_ERR_ARG;
+    if (d->n_games <= 0 || d->n_cycles < 0 || d->n_heavy < 0 || d->n_light < 0) return COEVO_ERR_ARG;
+    if ((d->n_heavy > 0 && !d->heavy) || (d->n_light > 0 && !d->light)) return COEVO_ERR_ARG;
+    if (d->sync_words) return COEVO_ERR_UNSUPPORTED;
+    auto *c = static_cast<coevo_rollout_ctx *>(ctx);
+    hipStream_t main_s = (hipStream_t)stream;
+    const int K = d->n_cohorts > 1 ? d->n_cohorts : 1;
+    if (d->light_stamps && d->n_cycles > 0 && !d->stamps_armed) {
+        hipLaunchKernelGGL(stamps_init_kernel, dim3(1), dim3(256), 0, main_s, d->light_stamps,
+                           K * d->n_cycles * COEVO_STAMP_SLOTS);
+        COEVO_HIP_CHECK(hipGetLastError());
+    }
+    if (K > 1) {
+        if (!c || !d->heavy_begin || !d->light_begin || K > COEVO_MAX_COHORTS) return COEVO_ERR_ARG;
+        if (d->heavy_begin[0] != 0 || d->light_begin[0] != 0 || d->heavy_begin[K] != d->n_heavy ||
+            d->light_begin[K] != d->n_light)
+            return COEVO_ERR_ARG;
+        for (int k = 0; k < K; ++k)
+            if (d->heavy_begin[k + 1] < d->heavy_begin[k] || d->light_begin[k + 1] < d->light_begin[k]) return COEVO_ERR_ARG;
+        if ((int)c->lanes.size() < K - 1) return COEVO_ERR_ARG;   // streams cannot be created while a graph is captured
+        // one stream per cohort, forked from / joined to the caller's stream only (see coevo_mpe_rollout)
+        COEVO_HIP_CHECK(hipEventRecord(c->start, main_s));
+        for (int k = 1; k < K; ++k) COEVO_HIP_CHECK(hipStreamWaitEvent(c->lanes[k - 1].s, c->start, 0));
+    }
+    const size_t act_stride = 3 * (size_t)d->n_games;
+    for (int k = 0; k < K; ++k) {   // enqueue order = cohort by cohort; the chains only meet again at the `done` events
+        const int hb = K > 1 ? d->heavy_begin[k] : 0, he = K > 1 ? d->heavy_begin[k + 1] : d->n_heavy;
+        const int lb = K > 1 ? d->light_begin[k] : 0, le = K > 1 ? d->light_begin[k + 1] : d->n_light;
+        hipStream_t ks = k ? c->lanes[k - 1].s : main_s;
+        for (int cyc = 0; cyc < d->n_cycles; ++cyc) {
+            // cycle c reads the state of cycle c-1 (buffer (c-1)&1; buffer 0 holds the reset state) and its actions
+            const double *st_prev = (cyc == 0) ? d->state : (((cyc - 1) & 1) ? d->state_alt : d->state);
+            double *st_next = (cyc & 1) ? d->state_alt : d->state;
+            if (cyc == 0) st_next = d->state_alt;   // never written in cycle 0; only has to differ from st_prev
+            const bool timed = K == 1 && time_light && c && (size_t)(2 * c->pairs_used + 1) < c->timing.size();
+            if (timed) COEVO_HIP_CHECK(hipEventRecord(c->timing[2 * c->pairs_used], main_s));
+            const int rc = coevo::launch_fc16_cycle(
+                d->slab, d->heavy ? d->heavy + hb : nullptr, he - hb, d->light ? d->light + lb : nullptr, le - lb, st_prev,
+                st_next, d->n_games, d->row_game, d->row_slot, d->actions_by_game + (size_t)((cyc + 1) & 1) * act_stride,
+                d->actions_by_game + (size_t)(cyc & 1) * act_stride, d->game_limit, cyc, d->pos_first, d->status,
+                d->light_stamps ? d->light_stamps + 2 * COEVO_STAMP_SLOTS * ((size_t)k * d->n_cycles + cyc) : nullptr, ks);
+            if (rc) return rc;
+            if (timed) {
+                COEVO_HIP_CHECK(hipEventRecord(c->timing[2 * c->pairs_used + 1], main_s));
+                ++c->pairs_used;
+            }
+        }
+    }
+    for (int k = 1; k < K; ++k) {
+        COEVO_HIP_CHECK(hipEventRecord(c->lanes[k - 1].done, c->lanes[k - 1].s));
+        COEVO_HIP_CHECK(hipStreamWaitEvent(main_s, c->lanes[k - 1].done, 0));
+    }
+    if (!d->rewards) return COEVO_OK;   // the caller closes the rollout itself (coevo_mpe_final_step)
+    const int last = d->n_cycles - 1;   // -1: no cycle ran, the books are the reset state's zeros
+    const double *st_last = (last <= 0) ? d->state : ((last & 1) ? d->state_alt : d->state);
+    const int32_t *act_last = d->actions_by_game + (size_t)((last < 0 ? 0 : last) & 1) * act_stride;
+    if (d->pack)
+        return coevo_mpe_final_step_pack(st_last, d->n_games, act_last, last, d->game_limit, d->pos_first, d->rewards,
+                                         d->pack->out, d->pack->dist, d->pack->n_roles, d->pack->n_local, d->pack->hof,
+                                         d->pack->dist_pitch, d->pack->dist_first, main_s);
+    return coevo_mpe_final_step(st_last, d->n_games, act_last, last, d->game_limit, d->pos_first, d->rewards, main_s);
+}
+
 COEVO_DEFINE_TU_FLAGS(rollout_api)

@@ -115,6 +115,27 @@ def _play_mpe_device(env, player1, player2, adversary, args, eval):
     return float(r[0]), float(r[1]), float(r[2])
 
 
+def _play_mpe_device16(env, player1, player2, adversary, args, eval):
+    """_play_mpe_device for three float16 nets: an fp16 slab (coevo_fc16_pack) and a float16 DeviceRollout"""
+    dev = "cuda"
+    ordinal = env.n_resets - 1  # the reset play_game just performed
+    s10, s8 = L.fc16_slab_stride(10), L.fc16_slab_stride(8)
+    slab = torch.zeros(2 * s10 + s8, dtype=torch.int32, device=dev)
+    for model, off, D in ((player1, 0, 10), (player2, s10, 10), (adversary, 2 * s10, 8)):
+        flat = torch.from_numpy(np.ascontiguousarray(model.flat(), dtype=np.float32)).to(dev)
+        L.call("coevo_fc16_pack", L._p(flat), slab.data_ptr() + 4 * off, 1, D)
+    plan = RolloutPlan(np.array([[2, 0, 1]]), [0, s10, 2 * s10], [10, 10, 8], device=dev)
+    ro = DeviceRollout(plan, slab, env_seed=env.seed_value, precision="float16")
+    limit = args.max_evaluation_steps if eval else args.max_timesteps_per_episode
+    T = effective_steps(limit, env.max_cycles)
+    ro.set_limits([T])
+    ro.reset(0, 1, ordinal)
+    ro.run((T + 2) // 3)
+    ro.check_status()
+    r = ro.rewards.cpu().numpy()[0]
+    return float(r[0]), float(r[1]), float(r[2])
+
+
 def _play_atari_aec(env, player1, player2, args, eval):
     """play_atari (:84-119) with the signature the call site at :227 uses; forwards on the GPU one step at a time"""
     rewards = {"first_0": 0, "second_0": 0}
@@ -163,13 +184,13 @@ def _play_atari_device(env, player1, player2, args, eval):
 def play_MPE(env, player1, player2, adversary, args, eval):
     """utils/game_logic_functions.py:123-212 - one episode on an ALREADY RESET env (play_game resets): the whole episode
     on the device when env and policies are this package's, else the AEC loop with one device forward per agent-step.
-    float16 nets always take the AEC loop (their forward is coevo_fc16_forward_argmax; the device rollout's cycle kernels
-    read fp32 slabs only)."""
+    Three float16 nets take the float16 device rollout (coevo_mpe16_rollout on an fp16 slab)."""
     from .fcnetwork import FCNetwork, FCNetworkHalf
     models = (player1, player2, adversary)
-    ours = isinstance(env, SimpleAdversaryAEC) and env.seed_value is not None and \
-        all(isinstance(m, FCNetwork) and not isinstance(m, FCNetworkHalf) for m in models)
-    if ours:
+    our_env = isinstance(env, SimpleAdversaryAEC) and env.seed_value is not None
+    if our_env and all(isinstance(m, FCNetworkHalf) for m in models):
+        return _play_mpe_device16(env, player1, player2, adversary, args, eval)
+    if our_env and all(isinstance(m, FCNetwork) and not isinstance(m, FCNetworkHalf) for m in models):
         return _play_mpe_device(env, player1, player2, adversary, args, eval)
     return _play_mpe_aec(env, player1, player2, adversary, args, eval)
 

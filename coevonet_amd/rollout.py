@@ -203,10 +203,21 @@ class DeviceRollout:
     """Env copies resident on the GPU.  One C-ABI call (coevo_mpe_rollout) enqueues every cycle of every cohort: per
     cycle and cohort ONE merged launch (shared-opponent workgroups on the matrix cores + per-individual streaming
     workgroups, env step fused in); ``merged=False`` keeps the two-launch form (shared-opponent launch on a side stream
-    beside the streaming launch) for A/B runs."""
+    beside the streaming launch) for A/B runs.  ``precision="float16"`` plays float16 nets (FCNetworkHalf) out of an fp16 slab
+    through coevo_mpe16_rollout."""
 
     def __init__(self, plan: RolloutPlan, slab: torch.Tensor, env_seed=sa.ENV_SEED, timing_pairs=0, fused_step=True,
-                 merged=None):
+                 merged=None, precision="float32"):
+        if precision not in ("float32", "float16"):
+            raise ValueError(f"Unsupported precision: {precision}")
+        # float16: `slab` is an fp16 slab (coevo_fc16_pack; int32 words, the plan's offsets count words) and every enqueue
+        # goes to coevo_mpe16_rollout: the fused env step, one launch per env-cycle and cohort, never the persistent form
+        self.precision = precision
+        self._entry = "coevo_mpe16_rollout" if precision == "float16" else "coevo_mpe_rollout"
+        if precision == "float16":
+            if not fused_step:
+                raise ValueError("the float16 rollout has the fused env step only")
+            merged = True
         if merged is None:
             # one launch per env-cycle (shared-opponent + per-individual workgroups together): 385 vs 347 generations/s
             # on cfg2; COEVO_MERGED=0 keeps the two launches on two streams for A/B runs
@@ -263,7 +274,7 @@ class DeviceRollout:
         # chip at once plays its n_cycles in ONE launch; the C side decides per cohort): tagged action words, per cohort
         self.sync_words_per_cohort = int(L.load().coevo_mpe_persistent_sync_words(n))
         self.sync_words = None
-        if fused_step and merged:
+        if fused_step and merged and precision == "float32":
             self.sync_words = torch.zeros(self.n_cohorts * self.sync_words_per_cohort, dtype=torch.int32, device=dev)
             self.desc.sync_words = L._p(self.sync_words)
 
@@ -343,7 +354,7 @@ class DeviceRollout:
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    L.call("coevo_mpe_rollout", L.C.byref(self.desc), ctx, 0)
+                    L.call(self._entry, L.C.byref(self.desc), ctx, 0)
                 self._graphs[key] = g
             g.replay()
             if timed:
@@ -351,7 +362,7 @@ class DeviceRollout:
             return
         self.desc.light_stamps = None
         self.desc.n_cycles = n_cycles
-        L.call("coevo_mpe_rollout", L.C.byref(self.desc), ctx, 1 if timed else 0)
+        L.call(self._entry, L.C.byref(self.desc), ctx, 1 if timed else 0)
 
     def enqueue(self, n_cycles, final=True, armed=False, pack=None):
         """plain enqueue on the current stream (no graph of its own): for callers that capture a larger graph.
@@ -375,7 +386,7 @@ class DeviceRollout:
             fp = L.FinalPack(L._p(out), L._p(dist), int(n_roles), int(n_local), int(hof), int(pitch), int(first), 0)
             self.desc.pack = L.C.addressof(fp)
         try:
-            L.call("coevo_mpe_rollout", L.C.byref(self.desc), self.ctx if (self.overlap or self.n_cohorts > 1) else None, 0)
+            L.call(self._entry, L.C.byref(self.desc), self.ctx if (self.overlap or self.n_cohorts > 1) else None, 0)
         finally:
             self.desc.rewards = keep
             self.desc.pack = None
@@ -409,7 +420,7 @@ class DeviceRollout:
         if self.sync_words is not None:   # this cohort's own scratch (zeroed by the launch, or by the reset launch: armed)
             d.sync_words = self.sync_words.data_ptr() + 4 * k * self.sync_words_per_cohort
             d.sync_cleared = 1 if armed else 0
-        L._check(L.load().coevo_mpe_rollout(L.C.byref(d), self.ctx, 0, stream.cuda_stream), "coevo_mpe_rollout")
+        L._check(getattr(L.load(), self._entry)(L.C.byref(d), self.ctx, 0, stream.cuda_stream), self._entry)
         if self.time_light:
             self._pending_stamps = int(n_cycles)
 

@@ -44,7 +44,7 @@ extern "C" {
 #define COEVO_ST_NO_ACTION 16
 #define COEVO_ST_SYNC_TIMEOUT 32 /* coevo_mpe_rollout_persistent: a workgroup waited too long for the other rows of its games (no
                                   * reference counterpart: more such launches side by side than the device holds at once) */
-#define COEVO_ST_BAD_TASK 64     /* coevo_fc16_forward_argmax: a task with D not 8 / 10, n_rows outside 1 .. COEVO_FC_MAX_ROWS or a
+#define COEVO_ST_BAD_TASK 64     /* coevo_fc16_forward_argmax / coevo_mpe16_policy_cycle: a task with D not 8 / 10, n_rows outside 1 .. COEVO_FC_MAX_ROWS or a
                                   * net_off that is not a multiple of 4 words was skipped (its rows are not written) */
 
 /* FCNetwork geometry (MPE/fcnetwork.py:14-22) */
@@ -394,6 +394,31 @@ int coevo_mpe_final_step(const double *state, int n_games, const int32_t *action
 int coevo_mpe_final_step_pack(const double *state, int n_games, const int32_t *actions_by_game, int cycle,
                               const int32_t *game_limit, int pos_first, double *rewards, double *pack, const float *dist,
                               int n_roles, int n_local, int hof, int dist_pitch, int dist_first, void *stream);
+
+/* ---- float16 nets at population scale: the env-cycle launch and the rollout on an fp16 slab (coevo_fc16_pack) ---- */
+/* coevo_mpe_policy_cycle_fused for an fp16 slab (args.precision == "float16", MPE/fcnetwork.py:13): FCNetwork.forward +
+ * determine_action (MPE/fcnetwork.py:37-90) in the float16 contract of DESIGN.md "float16 nets" for every row of every task,
+ * with the world step of the previous cycle (env.step / env.last, utils/game_logic_functions.py:179-190) fused in: a row
+ * derives its game's state from state_prev + act_prev, observes it (x = f16(obs)), writes its action to
+ * act_cur[game][slot]; the adversary-seat row publishes the state to state_next.  ONE launch for the whole table: one
+ * workgroup per task, rows in passes of 8 (tasks of up to COEVO_FC_MAX_ROWS rows beside tasks of one).  A task with D not
+ * 8 / 10, n_rows outside 1 .. COEVO_FC_MAX_ROWS or a net_off that is not a multiple of 4 words is skipped with
+ * COEVO_ST_BAD_TASK.  COEVO_TASK_RESIDENT selects plain instead of non-temporal weight loads (cache policy only; a task of
+ * more than 8 rows re-reads its net through L2 and uses plain loads too).  stamps as in coevo_mpe_policy_cycle_stamped. */
+int coevo_mpe16_policy_cycle(const void *slab16, const coevo_fc_task *tasks, int n_tasks, int max_rows_per_task,
+                             const double *state_prev, double *state_next, int n_games, const int32_t *row_game,
+                             const int32_t *row_slot, const int32_t *act_prev, int32_t *act_cur,
+                             const int32_t *game_limit, int cycle, int pos_first, int32_t *status, uint64_t *stamps,
+                             void *stream);
+/* coevo_mpe_rollout for an fp16 slab (desc->slab): play_game / play_MPE at batch scale (utils/game_logic_functions.py:
+ * 123-228) with float16 nets.  Per env-cycle and cohort ONE coevo_mpe16_policy_cycle launch over the cohort's `heavy` tasks
+ * (first) and `light` tasks; cohort k on the context's stream k, forked from and joined to `stream`; then the closing
+ * coevo_mpe_final_step (or _pack) when `rewards` is given - rewards are fp64 and do not depend on the precision.  The fused
+ * env step is the only form: COEVO_ERR_ARG without state_alt / actions_by_game.  There is no persistent fp16 launch:
+ * COEVO_ERR_UNSUPPORTED when sync_words is set.  game_limit, pos_first, light_stamps, stamps_armed, n_cohorts, heavy_begin /
+ * light_begin and pack as in coevo_mpe_rollout; merged and concurrent_hint are not used.  Asynchronous, allocates nothing,
+ * graph-capturable (the cohort streams must have been reserved: coevo_rollout_ctx_reserve_cohorts). */
+int coevo_mpe16_rollout(const coevo_rollout_desc *desc, void *ctx, int time_light, void *stream);
 
 /* ---------------------------------------------------------------- K3/K4/K8: offspring on device ------------- */
 /* The noise contract: rounds of the Philox4x32 generator behind every device-built offspring (7).  A checkpoint / a binding

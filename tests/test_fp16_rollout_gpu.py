@@ -1,0 +1,522 @@
+"""The float16 device rollout against the C checker (tests/checker16/fc16_checker.c through tests/fp16_checker.py): the
+env-cycle launch coevo_mpe16_policy_cycle stepped cycle by cycle, DeviceRollout(precision="float16") through every entry
+point the trainers use, the full cfg 2 shape, the numerical edges inside launches of healthy games, and play_game's device
+route.  Every comparison is an equality: rewards fp64 bit for bit, actions exact, status words equal."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from coevonet_amd import lib as L
+from coevonet_amd.rollout import DeviceRollout, RolloutPlan, effective_steps
+from oracle import ref_port as rp
+from tests import fp16_checker as ck
+from tests.test_fp16_gpu import random_flat
+from tests.util import Bag, load_golden
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+MAXC = 25
+POISON_ACT = 0x7f7f7f7f
+
+
+def pack16(flats10, flats8):
+    """every 10-wide net, then every 8-wide net, in one fp16 slab -> (slab, word offset per net id, width per net id)"""
+    s10, s8 = L.fc16_slab_stride(10), L.fc16_slab_stride(8)
+    n10, n8 = len(flats10), len(flats8)
+    slab = torch.full((n10 * s10 + n8 * s8,), -1, dtype=torch.int32, device=DEV)
+    for flats, D, first in ((flats10, 10, 0), (flats8, 8, n10 * s10)):
+        if len(flats):
+            src = torch.from_numpy(np.ascontiguousarray(np.stack(flats), dtype=np.float32)).to(DEV)
+            L.call("coevo_fc16_pack", L._p(src), slab.data_ptr() + 4 * first, len(flats), D)
+    off = [i * s10 for i in range(n10)] + [n10 * s10 + k * s8 for k in range(n8)]
+    return slab, off, [10] * n10 + [8] * n8
+
+
+def want_games(flats, games, limits, max_cycles, first, pos_first=1):
+    """the checker's play_game of every game (adversary, agent_0, agent_1 net ids): reset ordinal first + g"""
+    stream = rp.Stream()
+    rp.lib().oracle_mpe_set_pos_first(pos_first)
+    try:
+        return [ck.play_game(stream, flats[a0], flats[a1], flats[adv], limits[g], max_cycles, ordinal=first + g)
+                for g, (adv, a0, a1) in enumerate(games)]
+    finally:
+        rp.lib().oracle_mpe_set_pos_first(1)
+
+
+def eq_bits(got, want):
+    return np.array_equal(np.asarray(got, dtype=np.float64).view(np.uint64), np.asarray(want, dtype=np.float64).view(np.uint64))
+
+
+class Stepper:
+    """games stepped cycle by cycle with coevo_mpe16_policy_cycle on hand-built task / row tables.  tasks: list of
+    (net id, [(game, slot), ...]); every task's rows are followed by padding rows that name the canary game (one game past
+    the real ones, NaN state, never reset): a launch that touched a padding row would write the canary's words."""
+
+    def __init__(self, slab, off, Ds, tasks, n_real, limits, first, pos_first=1, net_off_shift=None, status0=0):
+        self.n = n = n_real + 1
+        self.n_real, self.pos_first, self.slab = n_real, pos_first, slab
+        row_game, row_slot, tab = [], [], []
+        for i, (net, rows) in enumerate(tasks):
+            shift = (net_off_shift or {}).get(i, 0)
+            tab.append((off[net] + shift, len(row_game), len(rows), Ds[net], 0))
+            for g, s in rows:
+                row_game.append(g)
+                row_slot.append(s)
+            for _ in range(1 + i % 3):   # padding rows
+                row_game.append(n_real)
+                row_slot.append(i % 3)
+        self.tasks_np = np.array(tab, dtype=L.TASK_DTYPE)
+        self.tasks = L.tasks_to_device(self.tasks_np, DEV)
+        self.max_rows = int(self.tasks_np["n_rows"].max())
+        self.row_game = torch.tensor(row_game, dtype=torch.int32, device=DEV)
+        self.row_slot = torch.tensor(row_slot, dtype=torch.int32, device=DEV)
+        self.state2 = torch.full((2, L.MPE_STATE_DOUBLES, n), float("nan"), dtype=torch.float64, device=DEV)
+        self.act = torch.full((2, n, 3), POISON_ACT, dtype=torch.int32, device=DEV)
+        self.rewards = torch.full((n, 3), float("nan"), dtype=torch.float64, device=DEV)
+        self.status = torch.full((1,), status0, dtype=torch.int32, device=DEV)
+        T = [effective_steps(lim, MAXC) for lim in limits] + [0]
+        self.T = T
+        self.limits = torch.tensor(T, dtype=torch.int32, device=DEV)
+        st0 = torch.zeros(L.MPE_STATE_DOUBLES, n, dtype=torch.float64, device=DEV)
+        L.call("coevo_mpe_reset", L._p(st0), n, 0, n_real, L.PCG64State.from_seed(rp.ENV_SEED), int(first))
+        st0[:, n_real] = float("nan")
+        self.state2[0].copy_(st0)
+
+    def cycle(self, c):
+        prev = self.state2[0] if c == 0 else self.state2[(c - 1) & 1]
+        nxt = self.state2[1] if c == 0 else self.state2[c & 1]
+        L.call("coevo_mpe16_policy_cycle", L._p(self.slab), L._p(self.tasks), len(self.tasks_np), self.max_rows,
+               prev.data_ptr(), nxt.data_ptr(), self.n, L._p(self.row_game), L._p(self.row_slot),
+               self.act[(c + 1) & 1].data_ptr(), self.act[c & 1].data_ptr(), L._p(self.limits), c, self.pos_first,
+               L._p(self.status), None)
+        torch.cuda.synchronize()
+        return self.act[c & 1].cpu().numpy()
+
+    def close(self, n_cycles):
+        last = n_cycles - 1
+        st_last = self.state2[0] if last <= 0 or (last & 1) == 0 else self.state2[1]
+        L.call("coevo_mpe_final_step", st_last.data_ptr(), self.n, self.act[last & 1].data_ptr(), last, L._p(self.limits),
+               self.pos_first, L._p(self.rewards))
+        torch.cuda.synchronize()
+        return self.rewards.cpu().numpy()
+
+    def play_and_compare(self, want, n_cycles):
+        """every action of every game against the checker's list, timestep by timestep; then the rewards"""
+        for c in range(n_cycles):
+            act = self.cycle(c)
+            for g in range(self.n_real):
+                for slot in range(3):
+                    step = 3 * c + slot
+                    if step < self.T[g]:
+                        assert act[g, slot] == want[g]["actions"][step], (c, g, slot)
+            assert (act[self.n_real] == POISON_ACT).all(), "a padding row was played"
+        rew = self.close(n_cycles)
+        for g in range(self.n_real):
+            assert want[g]["steps"] == self.T[g]
+            assert eq_bits(rew[g], want[g]["rewards"]), (g, rew[g], want[g]["rewards"])
+        assert torch.isnan(self.state2[:, :18, self.n_real]).all(), "the canary game's state was written"
+
+
+def cut_tasks(rng, pairs, sizes, first_net):
+    pairs = [pairs[i] for i in rng.permutation(len(pairs))]
+    assert sum(sizes) == len(pairs)
+    out, at = [], 0
+    for i, sz in enumerate(sizes):
+        out.append((first_net + i, pairs[at:at + sz]))
+        at += sz
+    return out
+
+
+GOOD_SIZES = (32, 17, 16, 9, 8, 5, 2, 1, 8, 8, 5, 5, 2, 1, 1)   # 120 rows: 15 nets of width 10
+ADV_SIZES = (16, 17, 9, 8, 5, 2, 1, 1, 1)                        # 60 rows: 9 nets of width 8
+
+
+def build_mixed(seed, n_games=60):
+    """60 games over 24 nets; tasks of 1, 2, 5, 8, 9, 16, 17 and 32 rows side by side"""
+    rng = np.random.default_rng(seed)
+    flats10 = [random_flat(rng, 10, scale=0.05 * (1 + i % 3)) for i in range(len(GOOD_SIZES))]
+    flats8 = [random_flat(rng, 8, scale=0.05 * (1 + i % 3)) for i in range(len(ADV_SIZES))]
+    tasks = cut_tasks(rng, [(g, s) for g in range(n_games) for s in (1, 2)], GOOD_SIZES, 0)
+    tasks += cut_tasks(rng, [(g, 0) for g in range(n_games)], ADV_SIZES, len(flats10))
+    tasks = [tasks[i] for i in rng.permutation(len(tasks))]
+    seat = np.zeros((n_games, 3), dtype=np.int64)
+    for net, rows in tasks:
+        for g, s in rows:
+            seat[g, s] = net
+    games = [(int(seat[g, 0]), int(seat[g, 1]), int(seat[g, 2])) for g in range(n_games)]
+    return flats10 + flats8, flats10, flats8, tasks, games
+
+
+@pytest.mark.parametrize("pos_first", [1, 0])
+def test_every_action_of_every_game(pos_first):
+    """60 games, 24 nets, task sizes 1 .. 32, limits None, 1, 2, 3, 4, T-1 and T side by side, both integration orders"""
+    flats, flats10, flats8, tasks, games = build_mixed(11)
+    assert {len(r) for _, r in tasks} >= {1, 2, 5, 8, 9, 16, 17, 32}
+    T = 3 * MAXC
+    choices = (None, 1, 2, 3, 4, T - 1, T)
+    limits = [choices[(5 * g + g // 7) % len(choices)] for g in range(len(games))]
+    assert set(limits) == set(choices)
+    first = 17
+    want = want_games(flats, games, limits, MAXC, first, pos_first)
+    assert all(w["status"] == 0 for w in want)
+    slab, off, Ds = pack16(flats10, flats8)
+    s = Stepper(slab, off, Ds, tasks, len(games), limits, first, pos_first)
+    s.play_and_compare(want, MAXC)
+    assert int(s.status.item()) == 0
+
+
+# ---------------------------------------------------------------------------------------------- DeviceRollout
+class GaSetup:
+    """a GA-shaped batch: per role, individual i in its own seat against HoF trio k in the two other seats; individuals dealt
+    to K contiguous cohorts; one fp16 slab"""
+    ROLE_SLOT = (1, 2, 0)   # agent_0, agent_1, adversary_0
+
+    def __init__(self, npop, nh, K, seed, heavy_rows=16, resident="none"):
+        self.npop, self.nh, self.K = npop, nh, K
+        n10 = 2 * (npop + nh)
+        # net ids: role r (0, 1: width 10) individuals [r * (npop + nh), +npop), its HoF [.. + npop, + nh); role 2: width 8 after them
+        self.base = [0, npop + nh, n10]
+        games, cohort = [], []
+        for r, slot in enumerate(self.ROLE_SLOT):
+            for i in range(npop):
+                for k in range(nh):
+                    seats = [0, 0, 0]
+                    for r2, slot2 in enumerate(self.ROLE_SLOT):
+                        seats[slot2] = self.base[r2] + (i if r2 == r else npop + k)
+                    games.append(tuple(seats))
+                    cohort.append(i * K // npop)
+        self.games = games
+        rng = np.random.default_rng(seed)
+        self.flats10 = [random_flat(rng, 10, scale=0.05 * (1 + i % 3)) for i in range(n10)]
+        self.flats8 = [random_flat(rng, 8, scale=0.05 * (1 + i % 3)) for i in range(npop + nh)]
+        self.flats = self.flats10 + self.flats8
+        self.slab, off, Ds = pack16(self.flats10, self.flats8)
+        light_nets = [self.base[r] + i for r in range(3) for i in range(npop)]
+        res = {"none": (), "all": light_nets, "half": light_nets[::2]}[resident]
+        self.plan = RolloutPlan(np.array(games), off, Ds, device=DEV, heavy_rows=heavy_rows,
+                                game_cohort=np.array(cohort, dtype=np.int32), resident_nets=res)
+        assert self.plan.n_cohorts == K
+        c = np.array(cohort)
+        # a cohort's games: one contiguous range per role phase
+        per_role = npop * nh
+        self.cohort_segs = [[(r * per_role + int(np.argmax(c[:per_role] == k)), int((c[:per_role] == k).sum())) for r in range(3)]
+                            for k in range(K)]
+        self.ro = DeviceRollout(self.plan, self.slab, precision="float16")
+        assert self.ro.sync_words is None and not self.ro.desc.sync_words
+        self._want = {}
+
+    def want(self, first, limits, n_cycles, only=None):
+        key = (first, tuple(limits), n_cycles)
+        if key not in self._want:
+            self._want[key] = {}
+        have = self._want[key]
+        todo = [g for g in (range(len(self.games)) if only is None else only) if g not in have]
+        stream = rp.Stream()
+        for g in todo:
+            adv, a0, a1 = self.games[g]
+            have[g] = ck.play_game(stream, self.flats[a0], self.flats[a1], self.flats[adv], limits[g], n_cycles, ordinal=first + g)
+        return have
+
+
+def poison(ro):
+    ro.stamps.fill_(5)
+    ro.state2[1].fill_(float("nan"))
+    ro.actions_by_game.fill_(POISON_ACT)
+    ro.rewards.fill_(float("nan"))
+
+
+def play(s, mode, n_cycles, first):
+    ro, n_games, K = s.ro, s.plan.n_games, s.plan.n_cohorts
+    if mode in ("run_eager", "run_graph"):
+        ro.use_graph = mode == "run_graph"
+        ro.reset(0, n_games, first)
+        ro.run(n_cycles)
+    elif mode == "enqueue":
+        ro.reset_segments([(0, n_games // 2, first), (n_games // 2, n_games - n_games // 2, first + n_games // 2)],
+                          arm=(0 if K == 1 else None, n_cycles))
+        ro.enqueue(n_cycles, armed=True)
+    elif mode == "cohorts":
+        for k, segs in enumerate(s.cohort_segs):
+            ro.reset_segments([(g0, cnt, first + g0) for g0, cnt in segs], arm=(k, n_cycles))
+            ro.enqueue_cohort(k, n_cycles, torch.cuda.current_stream(), armed=True)
+        ro.enqueue_final_step(n_cycles)
+    elif mode == "open_books":
+        ro.reset(0, n_games, first)
+        ro.enqueue(n_cycles, final=False)
+        ro.enqueue_final_step(n_cycles)
+    else:
+        raise AssertionError(mode)
+    torch.cuda.synchronize()
+    return ro.rewards.cpu().numpy()
+
+
+def assert_checker_equal(s, got, want, what):
+    for g in range(len(s.games)):
+        assert want[g]["status"] == 0
+        assert eq_bits(got[g], want[g]["rewards"]), (what, g, got[g], want[g]["rewards"])
+    assert int(s.ro.status.item()) == 0, what
+
+
+ROLLOUT_FORMS = [("run_eager", 1), ("run_graph", 1), ("run_graph", 2), ("enqueue", 1), ("enqueue", 2), ("enqueue", 3),
+                 ("cohorts", 2), ("open_books", 2)]
+
+
+@pytest.mark.parametrize("mode,K", ROLLOUT_FORMS)
+def test_device_rollout_float16_forms(mode, K):
+    """3 roles x pop 12 x HoF 3 = 108 games: rollout A, then B (other ordinals) and C (other cycle count and limits) on the
+    same object with its scratch poisoned in between, every game of each against the checker"""
+    s = GaSetup(12, 3, K, seed=21)
+    n_games = len(s.games)
+    for i, n_cycles in enumerate((14, 14, 9)):
+        T = 3 * n_cycles - 2 + i
+        limits = [T] * n_games
+        if i == 2:
+            limits = [(1, 2, 3, 4, T - 1, T)[g % 6] for g in range(n_games)]
+        s.ro.set_limits(limits)
+        first = 3 + 1000 * i
+        s.ro.time_light = (i == 1 and mode != "run_eager")
+        if i > 0:
+            poison(s.ro)
+        got = play(s, mode, n_cycles, first)
+        assert_checker_equal(s, got, s.want(first, limits, n_cycles), f"{mode} K={K} rollout {'ABC'[i]}")
+        if s.ro.time_light:
+            st = s.ro.stamps[:K * n_cycles].cpu().numpy()
+            assert (st != 5).all(), "a clock stamp still holds the poison"
+            assert (st[..., 1] >= st[..., 0]).all()
+
+
+def test_full_size_cfg2():
+    """cfg 2: 3 roles x pop 200 x HoF 5 = 3000 games, 25 cycles.  Sample rule: the checker plays the 600 deciding games (the last
+    HoF slot of every individual: the only game whose reward the GA fitness reads) and every 8th of the 2400 others (300) on
+    the CPU; all 3000 games' rewards, last actions and final state are bit-identical between one and two cohorts and between
+    no task resident and every task resident, so every game is anchored directly or through those equalities."""
+    npop, nh, n_cycles, first = 200, 5, 25, 9
+    T = 3 * n_cycles
+    results = []
+    s0 = None
+    for K, resident in ((2, "none"), (1, "none"), (2, "all")):
+        s = GaSetup(npop, nh, K, seed=33, resident=resident)
+        n_games = len(s.games)
+        assert n_games == 3000
+        flagged = int((s.plan.light_np["reserved"] & L.TASK_RESIDENT).sum())
+        assert flagged == (3 * npop if resident == "all" else 0)
+        s.ro.set_limits([T] * n_games)
+        poison(s.ro)
+        got = play(s, "run_graph", n_cycles, first)
+        assert int(s.ro.status.item()) == 0
+        last = n_cycles - 1
+        results.append((got, s.ro.actions_by_game[last & 1].cpu().numpy(), s.ro.state2[last & 1].cpu().numpy()))
+        if s0 is None:
+            s0 = s
+        else:
+            del s
+            torch.cuda.empty_cache()
+    for other in results[1:]:
+        for a, b in zip(results[0], other):
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    deciding = [g for g in range(3000) if g % nh == nh - 1]
+    others = [g for g in range(3000) if g % nh != nh - 1][::8]
+    sample = deciding + others
+    assert len(deciding) == 600 and len(sample) == 900
+    want = s0.want(first, [T] * 3000, n_cycles, only=sample)
+    got, act_last, _ = results[0]
+    for g in sample:
+        assert want[g]["status"] == 0
+        assert eq_bits(got[g], want[g]["rewards"]), g
+        assert list(act_last[g]) == want[g]["actions"][T - 3:T], g
+
+
+# ---------------------------------------------------------------------------------------------- edges
+def tie_net(rng, D=10):
+    """actions 1, 3 and 4 share their output row and bias and carry the maximum: exact three-way logit ties"""
+    flat = random_flat(rng, D)
+    P = L.fc_param_count(D)
+    w3 = P - 5 - 5 * 256
+    for o in (3, 4):
+        flat[w3 + o * 256:w3 + (o + 1) * 256] = flat[w3 + 256:w3 + 512]
+    flat[P - 5 + 1] = np.float32(np.float16(flat[P - 5 + 1] + np.float32(64.0)))
+    flat[P - 5 + 3] = flat[P - 5 + 4] = flat[P - 5 + 1]
+    return flat
+
+
+def subnormal_values(rng, n):
+    k = rng.integers(1, 1024, n) * rng.choice([-1, 1], n)
+    return (k.astype(np.float64) * 2.0 ** -24).astype(np.float32)   # every one an fp16 subnormal, exactly
+
+
+def edge_nets(rng):
+    """-> {name: (flat, D)}"""
+    out = {"ties": (tie_net(rng), 10)}
+    f = random_flat(rng, 10)
+    o_w2 = 10 * 512 + 3 * 512
+    f[o_w2:o_w2 + 256 * 512] = subnormal_values(rng, 256 * 512)
+    out["fc2_subnormal"] = (f, 10)
+    f = random_flat(rng, 8)
+    f[:8 * 512] = subnormal_values(rng, 8 * 512)
+    out["fc1_subnormal"] = (f, 8)
+    f = random_flat(rng, 10)
+    f[o_w2:o_w2 + 256 * 512] = np.float32(60000.0)
+    out["fc2_overflow"] = (f, 10)
+    f = random_flat(rng, 10)
+    f[10 * 512:10 * 512 + 512] = np.float32(65504.0)
+    f[10 * 512] = np.float32(-65504.0)
+    f[:10 * 512] = np.float32(8000.0)
+    out["fc1_overflow"] = (f, 10)
+    return out
+
+
+def edge_batch(seed, names):
+    """12 healthy games plus, per named edge net, two games it plays in (full-length games: every forward the launch runs is
+    one the checker runs, so the status words can be compared)"""
+    rng = np.random.default_rng(seed)
+    nets = edge_nets(rng)
+    n_healthy = 12
+    flats10 = [random_flat(rng, 10) for _ in range(6)]
+    flats8 = [random_flat(rng, 8) for _ in range(3)]
+    edge_id = {}
+    for name in names:
+        flat, D = nets[name]
+        if D == 10:
+            edge_id[name] = ("10", len(flats10))
+            flats10.append(flat)
+        else:
+            edge_id[name] = ("8", len(flats8))
+            flats8.append(flat)
+    n10 = len(flats10)
+    games = [(n10 + g % 3, g % 6, (g + 1) % 6) for g in range(n_healthy)]
+    for j, name in enumerate(names):
+        kind, idx = edge_id[name]
+        for rep in range(2):
+            if kind == "10":
+                games.append((n10 + rep, idx, (j + rep) % 6) if rep == 0 else (n10 + rep, (j + 2) % 6, idx))
+            else:
+                games.append((n10 + idx, (j + rep) % 6, (j + rep + 3) % 6))
+    by_net = {}
+    for g, seats in enumerate(games):
+        for slot, net in enumerate(seats):
+            by_net.setdefault(net, []).append((g, slot))
+    tasks = [(net, rows) for net, rows in sorted(by_net.items())]
+    assert max(len(r) for _, r in tasks) <= L.FC_MAX_ROWS
+    return flats10 + flats8, flats10, flats8, tasks, games, n_healthy
+
+
+EDGE_CASES = [(("ties",), 0), (("fc2_subnormal", "fc1_subnormal"), 0), (("fc2_overflow",), 4 | 8 | 16), (("fc1_overflow",), 2)]
+
+
+@pytest.mark.parametrize("names,must_have", EDGE_CASES)
+def test_edges_inside_a_launch_of_healthy_games(names, must_have):
+    """numerical edges the kernel must absorb: every action and reward of every game, faulty or healthy, equals the checker's,
+    and the status word, started at a foreign bit, ends as that bit OR the OR of the checker's per-game words"""
+    flats, flats10, flats8, tasks, games, n_healthy = edge_batch(41, names)
+    limits = [None] * len(games)
+    want = want_games(flats, games, limits, MAXC, 5)
+    assert all(w["status"] == 0 for w in want[:n_healthy])
+    want_st = 0
+    for w in want:
+        want_st |= w["status"]
+    assert want_st & must_have == must_have and (must_have != 0 or want_st == 0)
+    if "ties" in names:
+        assert all(set(w["actions"][1::3]) == {1} for w in want[n_healthy:n_healthy + 1])   # agent_0 is the tie net: first maximum
+    if "fc2_overflow" in names:
+        assert all(set(w["actions"][1::3]) == {0} for w in want[n_healthy:n_healthy + 1])   # no action -> 0, the game goes on
+    foreign = 1 << 20
+    slab, off, Ds = pack16(flats10, flats8)
+    s = Stepper(slab, off, Ds, tasks, len(games), limits, 5, status0=foreign)
+    s.play_and_compare(want, MAXC)
+    assert int(s.status.item()) == foreign | want_st
+
+
+def test_unaligned_net_offset_is_reported_and_writes_nothing():
+    flats, flats10, flats8, tasks, games, _ = edge_batch(43, ())
+    limits = [None] * len(games)
+    want = want_games(flats, games, limits, MAXC, 5)
+    slab, off, Ds = pack16(flats10, flats8)
+    bad = 4   # this task's net offset is moved by 2 words: its rows keep the poison, the others are played
+    s = Stepper(slab, off, Ds, tasks, len(games), limits, 5, net_off_shift={bad: 2})
+    act = s.cycle(0)
+    assert int(s.status.item()) == 64
+    skipped = set(tasks[bad][1])
+    for g in range(len(games)):
+        for slot in range(3):
+            if (g, slot) in skipped:
+                assert act[g, slot] == POISON_ACT
+            else:
+                assert act[g, slot] == want[g]["actions"][slot]
+    assert len(skipped) > 0
+
+
+def test_rollout_refuses_sync_words_and_missing_fused_fields():
+    s = GaSetup(4, 2, 1, seed=5)
+    ro = s.ro
+    ro.set_limits([6] * len(s.games))
+    ro.reset(0, len(s.games), 3)
+    d = L.RolloutDesc()
+    C.memmove(C.byref(d), C.byref(ro.desc), C.sizeof(d))
+    d.n_cycles = 2
+    words = torch.zeros(int(L.load().coevo_mpe_persistent_sync_words(len(s.games))), dtype=torch.int32, device=DEV)
+    d.sync_words = L._p(words)
+    before = ro.actions_by_game.clone()
+    assert L.load().coevo_mpe16_rollout(C.byref(d), ro.ctx, 0, L._stream()) == -3   # COEVO_ERR_UNSUPPORTED
+    d.sync_words = None
+    d.state_alt = None
+    assert L.load().coevo_mpe16_rollout(C.byref(d), ro.ctx, 0, L._stream()) == -1   # COEVO_ERR_ARG
+    d.state_alt = ro.desc.state_alt
+    d.actions_by_game = None
+    assert L.load().coevo_mpe16_rollout(C.byref(d), ro.ctx, 0, L._stream()) == -1
+    torch.cuda.synchronize()
+    assert torch.equal(before, ro.actions_by_game)   # nothing was launched
+    with pytest.raises(ValueError):
+        DeviceRollout(s.plan, s.slab, precision="bfloat16")
+
+
+# ---------------------------------------------------------------------------------------------- play_game
+def fixture_play(monkeypatch, wrap):
+    from coevonet_amd import game_logic as gl
+    from coevonet_amd.mpe.simple_adversary import ENV_SEED, SimpleAdversaryAEC
+    got, want = [], []
+    for c in load_golden("play_game_f16.json")["cases"]:
+        torch.manual_seed(c["torch_seed"])
+        np.random.seed(c["torch_seed"])
+        env = SimpleAdversaryAEC(max_cycles=c["max_cycles"])
+        env.reset(seed=ENV_SEED)
+        args = Bag(precision="float16", max_timesteps_per_episode=c["limit"], max_evaluation_steps=c["limit"])
+        ags = [gl.create_agent(env, args, r) for r in ("agent_0", "agent_1", "adversary_0")]
+        if c["mutated"]:
+            for a in ags:
+                a.mutate(c["mutate_std"])
+        played = wrap(env)
+        for g in c["games"]:
+            got.append(list(gl.play_game(played, ags[0].model, ags[1].model, ags[2].model, args, eval=False)))
+            want.append(g["rewards"])
+    return got, want
+
+
+def test_play_game_takes_the_device_route(monkeypatch):
+    """half agents on the package's seeded env: no AEC loop, and the 18 fixture triples"""
+    from coevonet_amd import game_logic as gl
+
+    def no_aec(*a, **k):
+        raise AssertionError("the AEC loop was taken")
+    monkeypatch.setattr(gl, "_play_mpe_aec", no_aec)
+    got, want = fixture_play(monkeypatch, lambda env: env)
+    assert len(got) == 18 and got == want
+
+
+def test_play_game_foreign_env_keeps_the_aec_loop(monkeypatch):
+    from coevonet_amd import game_logic as gl
+
+    class Foreign:
+        """an AEC env that is not this package's class: only the AEC surface is forwarded"""
+        def __init__(self, env):
+            self._env = env
+
+        def __getattr__(self, name):
+            return getattr(self._env, name)
+
+    def no_device(*a, **k):
+        raise AssertionError("the device route was taken")
+    monkeypatch.setattr(gl, "_play_mpe_device16", no_device)
+    got, want = fixture_play(monkeypatch, Foreign)
+    assert len(got) == 18 and got == want
