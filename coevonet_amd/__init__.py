@@ -24,3 +24,13 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 # in one process) died with a segmentation fault inside hipDeviceSynchronize under it, twice out of two, and never without.
 # So: export it yourself for a process that runs the host-cores mode after a graph-replaying mode and is short-lived, or do
 # what bench.py does - run the host-cores mode in a process of its own.
+
+__all__ = ["HalfGAEngine"]
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package alone loads neither torch nor the trainers
+    if name == "HalfGAEngine":
+        from .ga_half import HalfGAEngine
+        return HalfGAEngine
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,353 @@
+// Float16 Co-GA breeding on the fp16 slab of fc16_layout.hip.h: offspring with their stale-agent distance fused in, the
+// distance of nets already in a slab, its finalize with the fp16 rounding, net copies and the promotion.
+//
+// Replaces, for args.precision == "float16" (reference file:line): MPEAgent.clone + Agent.mutate (agent.py:25-29:
+// half_param.data += torch.normal(0, sigma, size) - the sum in fp32, rounded once to half; LayerNorm affine stays fp32),
+// np.linalg.norm(a16 - b16) of diversity_penalty on get_weights_ES() (utils/game_logic_functions.py:12-37) and the elite /
+// Hall-of-Fame bookkeeping of genetic_algorithm.py:262-275.
+//
+// The float16 breeding contract (DESIGN.md "float16 nets"):
+//   Linear weight or bias  child = f16(f32(parent) + noise), noise = sigma * eps(seed, stream, p) rounded to fp32 first,
+//                          p the canonical flat parameters() index: the number the fp32 child of the same stream draws.
+//                          Round to nearest even, past 65504 -> inf, fp16 subnormals kept.  A bias is an fp32 word that
+//                          holds an fp16 value, before and after.
+//   LayerNorm gamma / beta parent + noise in fp32, unrounded (left alone under COEVO_PERTURB_SKIP_LAYERNORM)
+//   distance               per Linear entry d = f16(f32(a) - f32(b)); d * d accumulated in fp64: the eight (or four) entries
+//                          of a thread's 16-byte piece in slab order, then block_sum_f64; one partial per 256-piece block.
+//                          dist = f16(sqrt(sum of the partials)), stored as an fp32 word.
+// A thread owns ONE 16-byte piece of the net: in W2h that is k = 8kb .. 8kb+7 of output column j = eight consecutive canonical
+// indices = two Philox quads; W3h likewise; a W1h piece is eight outputs of one input k, eight canonical indices D apart (one
+// Philox block each, 3.6 % of a net); a piece of the fp32 tail is one quad.
+#include <hip/hip_runtime.h>
+
+#include "coevo_common.hip.h"
+#include "fc16_layout.hip.h"
+#include "philox.hip.h"
+
+namespace coevo {
+
+constexpr int F16_W2_PIECES = (int)(F16_W1 / 4);   // 16384 pieces of W2h
+__host__ __device__ constexpr int f16_half_pieces(int D) { return (int)(f16_off_b1(D) / 4); }   // W2h + W1h + W3h
+__host__ __device__ constexpr int f16_pieces(int D) { return (int)(f16_stride(D) / 4); }
+__host__ __device__ constexpr int f16_perturb_blocks(int D) { return (f16_pieces(D) + 255) / 256; }
+
+// word w (>= f16_off_b1) of the fp32 tail: 0 = a bias (an fp16 value), 1 = LayerNorm affine, 2 = the stride's padding
+__device__ __forceinline__ int f16_tail_kind(int w, int D)
+{
+    const int b1 = (int)f16_off_b1(D), b2 = (int)f16_off_b2(D), b3 = (int)f16_off_b3(D);
+    if (w < b2) return (w - b1) < H1 ? 0 : 1;
+    if (w < b3) return (w - b2) < H2 ? 0 : 1;
+    return w < b3 + NACT ? 0 : 2;
+}
+
+// ... and its canonical flat index (w < f16_used(D)); the three tail sections start at multiples of four in both orders
+__device__ __forceinline__ int f16_tail_flat(int w, int D)
+{
+    const int b1 = (int)f16_off_b1(D), b2 = (int)f16_off_b2(D), b3 = (int)f16_off_b3(D);
+    if (w < b2) return (int)fc_off_b1(D) + (w - b1);
+    if (w < b3) return (int)fc_off_b2(D) + (w - b2);
+    return (int)fc_off_b3(D) + (w - b3);
+}
+
+// eps(seed, stream, p) alone: the Box-Muller pair that holds element p % 4 of Philox block p / 4 (the bits of
+// philox_normal4's z[p % 4]; the other pair of the block is not evaluated)
+__device__ __forceinline__ float philox_normal1(uint64_t seed, uint32_t slo, uint32_t shi, int p)
+{
+    const u32x4 o = philox4x32<COEVO_NOISE_ROUNDS>((uint32_t)(p >> 2), slo, shi, 0x636f6576u, (uint32_t)seed,
+                                                   (uint32_t)(seed >> 32));
+    const bool hi = (p & 2) != 0;
+    float z0, z1;
+    box_muller(hi ? o.v[2] : o.v[0], hi ? o.v[3] : o.v[1], z0, z1);
+    return (p & 1) ? z1 : z0;
+}
+
+// squared distance of piece u of net a to the same piece of net b: the piece's Linear entries in slab order
+__device__ __forceinline__ double f16_piece_d2(const uint4 &a, const uint4 &b, int u, int D)
+{
+    double d2 = 0.0;
+    if (u < f16_half_pieces(D)) {
+        _Float16 ha[8], hb[8];
+        __builtin_memcpy(ha, &a, sizeof(ha));
+        __builtin_memcpy(hb, &b, sizeof(hb));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float d = f16r((float)ha[i] - (float)hb[i]);
+            d2 += (double)d * (double)d;
+        }
+    } else {
+        float fa[4], fb[4];
+        __builtin_memcpy(fa, &a, sizeof(fa));
+        __builtin_memcpy(fb, &b, sizeof(fb));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (f16_tail_kind(4 * u + i, D) == 0) {
+                const float d = f16r(fa[i] - fb[i]);
+                d2 += (double)d * (double)d;
+            }
+        }
+    }
+    return d2;
+}
+
+// grid (f16_perturb_blocks(D), n_children): workgroup (bx, c) writes pieces 256 bx .. 256 bx + 255 of child c
+__global__ __launch_bounds__(256) void fc16_perturb_dist_kernel(const uint32_t *parent_slab, const int32_t *parent_idx,
+                                                                 uint32_t *child_slab, int child_first, int D,
+                                                                 const float *sigma_dev, uint64_t seed,
+                                                                 uint32_t stream_lo_first, uint32_t stream_hi, int flags,
+                                                                 const int32_t *gen_dev, const uint32_t *dist_ref,
+                                                                 double *dist_partial)
+{
+    __shared__ double scratch[4];
+    if (gen_dev) stream_hi += 4u * (uint32_t)(*gen_dev);   // generation-indexed noise stream without a host argument
+    const bool skip_layernorm = (flags & COEVO_PERTURB_SKIP_LAYERNORM) != 0;
+    const int c = blockIdx.y, bx = blockIdx.x;
+    const uint32_t slo = stream_lo_first + (uint32_t)c;
+    const int64_t stride = f16_stride(D);
+    const int u = bx * 256 + (int)threadIdx.x;
+    double d2 = 0.0;
+    if (u < f16_pieces(D)) {
+        const float sigma = *sigma_dev;
+        const uint4 pv = reinterpret_cast<const uint4 *>(parent_slab + (int64_t)parent_idx[c] * stride)[u];
+        uint4 ov;
+        if (u < f16_half_pieces(D)) {
+            float z[8];
+            const int w1_pieces = D * (H1 / 8);
+            if (u < F16_W2_PIECES || u >= F16_W2_PIECES + w1_pieces) {
+                // W2h piece (kb, j) = fc2.w[j][8kb .. 8kb+7]; W3h piece t = output.w flat 8t .. 8t+7: eight consecutive
+                // canonical indices from a multiple of eight - two Philox blocks
+                const int p0 = (u < F16_W2_PIECES)
+                                   ? (int)fc_off_w2(D) + (u & (H2 - 1)) * H1 + 8 * (u >> 8)
+                                   : (int)fc_off_w3(D) + 8 * (u - F16_W2_PIECES - w1_pieces);
+                philox_normal4(seed, slo, stream_hi, (uint32_t)(p0 >> 2), z);
+                philox_normal4(seed, slo, stream_hi, (uint32_t)(p0 >> 2) + 1u, z + 4);
+            } else {
+                // W1h[k][j0 .. j0+7] = fc1.w[j0 + i][k]: canonical (j0 + i) D + k, a Philox block each
+                const int h0 = 8 * (u - F16_W2_PIECES), k = h0 >> 9, j0 = h0 & (H1 - 1);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) z[i] = philox_normal1(seed, slo, stream_hi, (j0 + i) * D + k);
+            }
+            _Float16 hin[8], hout[8];
+            __builtin_memcpy(hin, &pv, sizeof(hin));
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float noise = sigma * z[i];               // rounded first, then added (agent.py:28-29)
+                hout[i] = (_Float16)((float)hin[i] + noise);    // the sum in fp32, rounded once to half
+            }
+            __builtin_memcpy(&ov, hout, sizeof(hout));
+        } else {
+            const int w0 = 4 * u;
+            float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (w0 < (int)f16_used(D)) philox_normal4(seed, slo, stream_hi, (uint32_t)(f16_tail_flat(w0, D) >> 2), z);
+            float in[4], out[4];
+            __builtin_memcpy(in, &pv, sizeof(in));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int kind = f16_tail_kind(w0 + i, D);
+                const float v = in[i] + sigma * z[i];
+                out[i] = (kind == 0) ? f16r(v) : ((kind == 1 && !skip_layernorm) ? v : in[i]);
+            }
+            __builtin_memcpy(&ov, out, sizeof(out));
+        }
+        // a plain store: the rollout reads the child next
+        reinterpret_cast<uint4 *>(child_slab + (int64_t)(child_first + c) * stride)[u] = ov;
+        if (dist_partial) d2 = f16_piece_d2(ov, reinterpret_cast<const uint4 *>(dist_ref)[u], u, D);
+    }
+    if (dist_partial) {   // uniform over the launch
+        const double tot = block_sum_f64(d2, scratch);
+        if (threadIdx.x == 0) dist_partial[(size_t)c * gridDim.x + bx] = tot;
+    }
+}
+
+// the same partials for nets that are already in a slab (generation 0, uploaded populations): grid (blocks, n)
+__global__ __launch_bounds__(256) void fc16_distance_kernel(const uint32_t *ref_net, const uint32_t *pop_slab, int D,
+                                                             double *dist_partial)
+{
+    __shared__ double scratch[4];
+    const int n = blockIdx.y, bx = blockIdx.x;
+    const int u = bx * 256 + (int)threadIdx.x;
+    double d2 = 0.0;
+    if (u < f16_pieces(D))
+        d2 = f16_piece_d2(reinterpret_cast<const uint4 *>(pop_slab + (int64_t)n * f16_stride(D))[u],
+                          reinterpret_cast<const uint4 *>(ref_net)[u], u, D);
+    const double tot = block_sum_f64(d2, scratch);
+    if (threadIdx.x == 0) dist_partial[(size_t)n * gridDim.x + bx] = tot;
+}
+
+// fp64 -> fp16 in ONE rounding (to nearest even): to fp32 with round-to-odd first, which the fp32 -> fp16 conversion then
+// rounds as if it saw the fp64 value (fp32 carries more than two bits beyond fp16's eleven)
+__device__ inline float f16_of_f64(double s)
+{
+    float f = (float)s;
+    if ((double)f != s && !__builtin_isinf(f) && !__builtin_isnan(f)) {
+        uint32_t b = __float_as_uint(f);
+        if (__builtin_fabs((double)f) > __builtin_fabs(s)) b -= 1u;   // back to the truncated value
+        f = __uint_as_float(b | 1u);                                    // sticky bit
+    }
+    return f16r(f);
+}
+
+// dist[first + c] = f16(sqrt(sum_b partial[c][b])), dist_finalize_kernel's order (lane-strided sums, then the xor tree);
+// head: dist[first - 1] = *head
+__global__ __launch_bounds__(64) void fc16_dist_finalize_kernel(const double *partial, int n_blocks, float *dist, int first,
+                                                                 const float *head)
+{
+    const int c = blockIdx.x, l = threadIdx.x;
+    double v = 0.0;
+    for (int b = l; b < n_blocks; b += 64) v += partial[(size_t)c * n_blocks + b];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
+    if (l == 0) {
+        dist[first + c] = f16_of_f64(sqrt(v));
+        if (c == 0 && head) dist[first - 1] = *head;
+    }
+}
+
+// dst[dst_first + c] = src[src_idx[c]], whole 16-byte words of the stride
+__global__ __launch_bounds__(256) void fc16_gather_kernel(const uint32_t *src_slab, const int32_t *src_idx,
+                                                           uint32_t *dst_slab, int dst_first, int D)
+{
+    const int c = blockIdx.y;
+    const int u = blockIdx.x * 256 + (int)threadIdx.x;
+    if (u >= f16_pieces(D)) return;
+    const int64_t stride = f16_stride(D);
+    const uint4 v = reinterpret_cast<const uint4 *>(src_slab + (int64_t)src_idx[c] * stride)[u];
+    reinterpret_cast<uint4 *>(dst_slab + (int64_t)(dst_first + c) * stride)[u] = v;
+}
+
+// ---- elites -> elite buffer, HoF FIFO push, best -> pop[0] for up to three roles in one launch: ga_promote_kernel of
+// offspring.hip on fp16 nets.  A thread owns one 16-byte piece of every net it touches and reads its piece of every source
+// before the first store that could alias it; the pieces live in the frames of a compile-time recursion (loads on the way
+// down, stores on the way back), so the in-place shift needs no second buffer and no runtime-indexed array.
+struct Ga16PromoteArgs {
+    coevo_ga16_promote_role role[3];
+    int E, hof;
+};
+constexpr int PROMOTE16_MAX_E = 8, PROMOTE16_MAX_HOF = 16;
+
+template <int I>
+__device__ __forceinline__ void promote16_hof_shift(uint4 *hof, int64_t pitch, int n)
+{
+    if constexpr (I < PROMOTE16_MAX_HOF) {
+        const uint4 v = hof[(int64_t)(I < n ? I : n - 1) * pitch];
+        promote16_hof_shift<I + 1>(hof, pitch, n);
+        hof[(int64_t)(I < n ? I - 1 : n - 1) * pitch] = v;   // (a surplus level rewrites the last slot; the caller overwrites it)
+    }
+}
+
+// elite[k] = pop[order[k]] for k < E (k descending on the way back); returns pop[order[0]]
+template <int K>
+__device__ __forceinline__ uint4 promote16_elites(const uint4 *pop, const int32_t *order, uint4 *elite, int64_t pitch, int E)
+{
+    if constexpr (K < PROMOTE16_MAX_E) {
+        const int kc = K < E ? K : E - 1;
+        const uint4 v = pop[(int64_t)order[kc] * pitch];
+        promote16_elites<K + 1>(pop, order, elite, pitch, E);
+        elite[(int64_t)kc * pitch] = v;
+        return v;
+    } else {
+        return make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+__global__ __launch_bounds__(256) void ga16_promote_kernel(Ga16PromoteArgs a)
+{
+    // (field-wise selects: indexing the by-value argument array dynamically copies it to scratch)
+    const unsigned y = blockIdx.y;
+#define PROMOTE16_SEL(f) (y == 0 ? a.role[0].f : (y == 1 ? a.role[1].f : a.role[2].f))
+    void *pop_v = PROMOTE16_SEL(pop), *hof_v = PROMOTE16_SEL(hof), *elite_v = PROMOTE16_SEL(elite);
+    const int32_t *order = PROMOTE16_SEL(order);
+    const int D = PROMOTE16_SEL(D), from_pop = PROMOTE16_SEL(elites_from_pop), to_pop0 = PROMOTE16_SEL(best_to_pop0);
+#undef PROMOTE16_SEL
+    const int u = blockIdx.x * 256 + (int)threadIdx.x;
+    if (u >= f16_pieces(D)) return;
+    const int64_t pitch = f16_pieces(D);   // 16-byte pieces between consecutive nets
+    uint4 *pop = static_cast<uint4 *>(pop_v) + u, *hof = static_cast<uint4 *>(hof_v) + u, *elite = static_cast<uint4 *>(elite_v) + u;
+    const uint4 e0 = from_pop ? promote16_elites<0>(pop, order, elite, pitch, a.E) : elite[0];
+    promote16_hof_shift<1>(hof, pitch, a.hof);
+    hof[(int64_t)(a.hof - 1) * pitch] = e0;
+    if (to_pop0) pop[0] = e0;
+}
+
+}  // namespace coevo
+
+using namespace coevo;
+
+static bool fc16_dim_ok(int D) { return D == 8 || D == 10; }
+static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+extern "C" int64_t coevo_fc16_perturb_blocks(int D) { return fc16_dim_ok(D) ? f16_perturb_blocks(D) : COEVO_ERR_ARG; }
+
+extern "C" int coevo_fc16_perturb_dist(const void *parent_slab, const int32_t *parent_idx, void *child_slab, int child_first,
+                                       int n_children, int D, const float *sigma_dev, uint64_t seed,
+                                       uint32_t stream_lo_first, uint32_t stream_hi, int flags, const int32_t *gen_dev,
+                                       const void *dist_ref, double *dist_partial, void *stream)
+{
+    if ((dist_ref == nullptr) != (dist_partial == nullptr)) return COEVO_ERR_ARG;
+    if (!parent_slab || !parent_idx || !child_slab || !sigma_dev || !fc16_dim_ok(D)) return COEVO_ERR_ARG;
+    if (!aligned16(parent_slab) || !aligned16(child_slab) || !aligned16(dist_ref)) return COEVO_ERR_ARG;
+    if (n_children < 0 || child_first < 0 || n_children > 65535 || (flags & ~COEVO_PERTURB_SKIP_LAYERNORM)) return COEVO_ERR_ARG;
+    if (n_children == 0) return COEVO_OK;
+    const dim3 grid((unsigned)f16_perturb_blocks(D), (unsigned)n_children);
+    hipLaunchKernelGGL(fc16_perturb_dist_kernel, grid, dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const uint32_t *>(parent_slab), parent_idx, static_cast<uint32_t *>(child_slab),
+                       child_first, D, sigma_dev, seed, stream_lo_first, stream_hi, flags, gen_dev,
+                       static_cast<const uint32_t *>(dist_ref), dist_partial);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_fc16_distance(const void *ref_net, const void *pop_slab, int n, int D, double *dist_partial, void *stream)
+{
+    if (!ref_net || !pop_slab || !dist_partial || !fc16_dim_ok(D) || n < 0 || n > 65535) return COEVO_ERR_ARG;
+    if (!aligned16(ref_net) || !aligned16(pop_slab)) return COEVO_ERR_ARG;
+    if (n == 0) return COEVO_OK;
+    const dim3 grid((unsigned)f16_perturb_blocks(D), (unsigned)n);
+    hipLaunchKernelGGL(fc16_distance_kernel, grid, dim3(256), 0, (hipStream_t)stream, static_cast<const uint32_t *>(ref_net),
+                       static_cast<const uint32_t *>(pop_slab), D, dist_partial);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_fc16_distance_finalize(const double *dist_partial, int n_blocks, int n, float *dist, int first,
+                                            const float *head, void *stream)
+{
+    if (!dist_partial || !dist || n_blocks <= 0 || n <= 0 || first < 0 || (head && first < 1)) return COEVO_ERR_ARG;
+    hipLaunchKernelGGL(fc16_dist_finalize_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, dist_partial, n_blocks, dist,
+                       first, head);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_fc16_gather(const void *src_slab, const int32_t *src_idx, void *dst_slab, int dst_first, int n, int D,
+                                 void *stream)
+{
+    if (!src_slab || !src_idx || !dst_slab || !fc16_dim_ok(D) || n < 0 || dst_first < 0 || n > 65535) return COEVO_ERR_ARG;
+    if (!aligned16(src_slab) || !aligned16(dst_slab)) return COEVO_ERR_ARG;
+    if (n == 0) return COEVO_OK;
+    const dim3 grid((unsigned)f16_perturb_blocks(D), (unsigned)n);
+    hipLaunchKernelGGL(fc16_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, static_cast<const uint32_t *>(src_slab),
+                       src_idx, static_cast<uint32_t *>(dst_slab), dst_first, D);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+static_assert(sizeof(coevo_ga16_promote_role) == 48, "layout mirrored by coevonet_amd/lib.py GaPromoteRole");
+
+extern "C" int coevo_ga16_promote(const coevo_ga16_promote_role *roles, int n_roles, int E, int hof, void *stream)
+{
+    if (!roles || n_roles < 1 || n_roles > 3 || E < 1 || E > PROMOTE16_MAX_E || hof < 1 || hof > PROMOTE16_MAX_HOF)
+        return COEVO_ERR_ARG;
+    Ga16PromoteArgs a{};
+    int max_blocks = 0;
+    for (int r = 0; r < n_roles; ++r) {
+        const coevo_ga16_promote_role &R = roles[r];
+        if (!R.pop || !R.hof || !R.elite || !fc16_dim_ok(R.D) || (R.elites_from_pop && !R.order)) return COEVO_ERR_ARG;
+        if (!aligned16(R.pop) || !aligned16(R.hof) || !aligned16(R.elite)) return COEVO_ERR_ARG;
+        a.role[r] = R;
+        if (f16_perturb_blocks(R.D) > max_blocks) max_blocks = f16_perturb_blocks(R.D);
+    }
+    a.E = E; a.hof = hof;
+    hipLaunchKernelGGL(ga16_promote_kernel, dim3((unsigned)max_blocks, (unsigned)n_roles), dim3(256), 0, (hipStream_t)stream, a);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}

@@ -1,0 +1,230 @@
+"""Float16 Co-GA generations on one GPU: ``HalfGAEngine``, the engine of ``args.precision == "float16"`` nets
+(reference MPE/fcnetwork.py:13, genetic_algorithm.py:51-345).
+
+The population, the Hall of Fame, the elites and the stale agent of the three roles live in ONE fp16 slab
+(coevo_fc16_pack's layout).  A generation is: the float16 device rollout of all 3 * pop * hof games plus the evaluation games
+of the previous generation's best trio (``DeviceRollout(precision="float16")``), the selection (coevo_ga_select on
+fp16-valued distances), the promotion (coevo_ga16_promote) and the offspring with their stale-agent distances fused in
+(coevo_fc16_perturb_dist, coevo_fc16_distance_finalize) - the order and the noise streams of ``GAEngine.breed_device`` on
+one GPU.  The rounding points are the float16 contract of DESIGN.md "float16 nets".
+
+One cohort, device env, ``device_philox`` offspring, fixed mutation powers.  ``GATrainer`` / ``genetic_algorithm_train``
+still refuse float16: this object is the float16 route until the trainers are switched over."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import lib as L
+from .genetic_algorithm import N_EVAL, RET_SLOT, ROLE_D, ROLES
+from .mpe.simple_adversary import ENV_SEED
+from .rollout import DeviceRollout, RolloutPlan, effective_steps
+
+# The game table, the rollout / evaluation calls and load_initial below follow GAEngine's (genetic_algorithm.py) line by line:
+# GAEngine cannot take a precision while the trainers must keep refusing float16.  The trainer switch
+# folds the two into one table builder.
+REGIONS = ("pop", "hof", "elite", "stale", "hof_tmp")
+
+
+class HalfGAEngine:
+    """Device-resident float16 population / HoF / elites of the three roles and the per-generation steps.
+
+    ``rollout(gen)`` -> ``select()`` -> ``breed(gen, sigmas)`` is one generation; ``run(generations, sigmas)`` loops them.
+    Nets go in and out as flat float32 arrays of fp16 values in parameters() order (``FCNetworkHalf.flat()``)."""
+
+    def __init__(self, pop, hof, elites, limit_train=None, limit_eval=None, max_cycles=25, device="cuda",
+                 env_seed=ENV_SEED, philox_seed=0, first_ordinal=1, *, adaptive=False, shard=(0, 1), env="device",
+                 rng="device_philox"):
+        # what float16 does not cover is refused before the library is loaded
+        if adaptive:
+            raise ValueError("HalfGAEngine: adaptive mutation power is not built for precision float16")
+        if tuple(shard) != (0, 1):
+            raise ValueError(f"HalfGAEngine: precision float16 runs on one rank only, not shard {tuple(shard)}")
+        if env != "device":
+            raise ValueError(f'HalfGAEngine: precision float16 has the device env only, not env="{env}"')
+        if rng != "device_philox":
+            raise ValueError(f'HalfGAEngine: precision float16 breeds with rng="device_philox" only, not "{rng}"')
+        if not (2 <= pop <= 4096 and 1 <= elites <= min(pop, 8) and 1 <= hof <= 16):
+            raise ValueError(f"HalfGAEngine: population {pop} (2 .. 4096), elites {elites} (1 .. 8, <= population) or "
+                             f"hof {hof} (1 .. 16) out of range")
+        self.pop, self.hof, self.E = pop, hof, elites
+        self.device, self.philox_seed = device, int(philox_seed)
+        self.T_train = effective_steps(limit_train, max_cycles)
+        self.T_eval = effective_steps(limit_eval, max_cycles)
+        self.n_cycles = (max(self.T_train, self.T_eval) + 2) // 3
+        self.first_ordinal, self.env_seed = first_ordinal, env_seed
+        # ---- slab layout (32-bit words): per role [pop | hof | elite | stale | hof_tmp] -----------------------
+        self.stride = {r: L.fc16_slab_stride(ROLE_D[r]) for r in ROLES}
+        self.P = {r: L.fc_param_count(ROLE_D[r]) for r in ROLES}
+        self.base, off = {}, 0
+        for r in ROLES:
+            self.base[r] = {}
+            for region, count in zip(REGIONS, (pop, hof, elites, 1, hof)):
+                self.base[r][region] = off
+                off += count * self.stride[r]
+        self.slab = torch.zeros(off, dtype=torch.int32, device=device)
+        # ---- GAEngine's game table: Q2 / Q4 seats, then the N_EVAL games of the newest HoF trio ----------------
+        net_off, net_D, ids = [], [], {}
+
+        def net(region, role, i):
+            key = (region, role, i)
+            if key not in ids:
+                ids[key] = len(net_off)
+                net_off.append(self.base[role][region] + i * self.stride[role])
+                net_D.append(ROLE_D[role])
+            return ids[key]
+
+        games, h = [], hof
+        for role in ROLES:
+            for i in range(pop):
+                for k in range(h):
+                    if role == "agent_0":      # genetic_algorithm.py:136-142
+                        a0, a1, adv = net("pop", role, i), net("hof", "agent_1", h - 1 - k), net("hof", "adversary_0", h - 1 - k)
+                    elif role == "agent_1":    # :168-174
+                        a0, a1, adv = net("hof", "agent_0", h - 1 - k), net("pop", role, i), net("hof", "adversary_0", h - 1 - k)
+                    else:                      # :201-207, Q4: agent_1's seat is also filled from hof_agent_0
+                        a0, a1, adv = net("hof", "agent_0", h - 1 - k), net("hof", "agent_0", h - 1 - k), net("pop", role, i)
+                    games.append((adv, a0, a1))
+        self.n_main = len(games)
+        for _ in range(N_EVAL):   # evaluate_current_weights(best trio) = the newest HoF members (:12-29, :301)
+            games.append((net("hof", "adversary_0", h - 1), net("hof", "agent_0", h - 1), net("hof", "agent_1", h - 1)))
+        self.plan = RolloutPlan(np.array(games), net_off, net_D, device=device, heavy_rows=16, row_order="class")
+        self.ro = DeviceRollout(self.plan, self.slab, env_seed=env_seed, precision="float16")
+        # ---- small device buffers ------------------------------------------------------------------------------
+        f32 = dict(dtype=torch.float32, device=device)
+        self.dist = {r: torch.zeros(pop, **f32) for r in ROLES}          # fp16 values in fp32 words
+        self.div = {r: torch.zeros(1, **f32) for r in ROLES}
+        self.fitness = {r: torch.zeros(pop, **f32) for r in ROLES}
+        self.order = {r: torch.zeros(pop, dtype=torch.int32, device=device) for r in ROLES}
+        self.sigma = {r: torch.zeros(1, **f32) for r in ROLES}
+        self.best_dist = {r: torch.zeros(1, **f32) for r in ROLES}
+        self.pblocks = {r: L.fc16_perturb_blocks(ROLE_D[r]) for r in ROLES}
+        self.dist_partial = {r: torch.zeros(pop * self.pblocks[r], dtype=torch.float64, device=device) for r in ROLES}
+        self.parent_idx = torch.tensor([c % elites for c in range(pop - 1)], dtype=torch.int32, device=device)
+        self._dist_current = False
+        self.steps_per_generation = 3 * pop * hof * self.T_train + N_EVAL * self.T_eval
+
+    # ------------------------------------------------------------------ loading weights
+    def _ptr(self, role, region, i=0):
+        return self.slab.data_ptr() + 4 * (self.base[role][region] + i * self.stride[role])
+
+    def upload(self, role, region, first, flat_np):
+        """flat_np [n][P] (parameters() order, fp16 values in float32) -> nets first.. of a region"""
+        flat = torch.from_numpy(np.ascontiguousarray(flat_np, dtype=np.float32)).to(self.device)
+        L.call("coevo_fc16_pack", L._p(flat), self._ptr(role, region, first), flat.shape[0], ROLE_D[role])
+        if region in ("pop", "stale"):
+            self._dist_current = False   # (the distances breed() left behind no longer describe the slab)
+        return flat   # keep alive until the stream has consumed it
+
+    def download(self, role, region, first, n):
+        out = torch.zeros(n, self.P[role], dtype=torch.float32, device=self.device)
+        L.call("coevo_fc16_unpack", self._ptr(role, region, first), L._p(out), n, ROLE_D[role])
+        return out.cpu().numpy()
+
+    def load_initial(self, pop_flat, hof_flat):
+        """pop_flat[role] [pop][P], hof_flat[role] [hof][P]; the stale agent of Q3 is the initial pop[pop-1]"""
+        keep = []
+        for r in ROLES:
+            keep.append(self.upload(r, "pop", 0, pop_flat[r]))
+            keep.append(self.upload(r, "hof", 0, hof_flat[r]))
+            keep.append(self.upload(r, "stale", 0, pop_flat[r][self.pop - 1:self.pop]))
+        torch.cuda.current_stream().synchronize()
+
+    # ------------------------------------------------------------------ one generation
+    def _ordinal_base(self, gen):
+        return self.first_ordinal + gen * (3 * self.pop * self.hof + N_EVAL)
+
+    def rollout(self, gen):
+        """plays generation `gen`'s 3 * pop * hof games and, riding along from generation 1 on, the evaluation games of
+        generation gen - 1 (they depend only on that generation's selection: GAEngine.rollout)"""
+        limits = np.zeros(self.plan.n_games, dtype=np.int32)
+        limits[:self.n_main] = self.T_train
+        if gen > 0:
+            limits[self.n_main:] = self.T_eval
+        self.ro.set_limits(limits)
+        self.ro.reset(0, self.n_main, self._ordinal_base(gen))
+        if gen > 0:
+            self.ro.reset(self.n_main, N_EVAL, self._ordinal_base(gen - 1) + self.n_main)
+        self.ro.run(self.n_cycles)
+
+    def eval_only(self, gen):
+        """the evaluation games of generation `gen` alone (the flush after the last generation) -> their mean triple"""
+        limits = np.zeros(self.plan.n_games, dtype=np.int32)
+        limits[self.n_main:] = self.T_eval
+        self.ro.set_limits(limits)
+        self.ro.reset(0, self.n_main, 0)
+        self.ro.reset(self.n_main, N_EVAL, self._ordinal_base(gen) + self.n_main)
+        self.ro.run((self.T_eval + 2) // 3)
+        return self.eval_rewards()
+
+    def rewards_host(self):
+        return self.ro.rewards.cpu().numpy()
+
+    def eval_rewards(self):
+        """mean reward triple (agent_0, agent_1, adversary_0) of the evaluation games in the last rollout"""
+        self.ro.check_status()
+        r = self.rewards_host()[self.n_main:]
+        tot = [0.0, 0.0, 0.0]
+        for g in range(N_EVAL):   # python-float accumulation order of evaluate_current_weights
+            for s in range(3):
+                tot[s] += float(r[g, s])
+        return [t / 10 for t in tot]
+
+    def select(self):
+        """fitness sharing + fitness + ranking of the three roles in one launch; the elite ids stay on the device"""
+        self.ro.check_status()
+        if not self._dist_current:   # generation 0, or a population loaded from the host
+            for r in ROLES:
+                L.call("coevo_fc16_distance", self._ptr(r, "stale"), self._ptr(r, "pop"), self.pop, ROLE_D[r],
+                       L._p(self.dist_partial[r]))
+                L.call("coevo_fc16_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop,
+                       L._p(self.dist[r]), 0, None)
+            self._dist_current = True
+        roles = (L.GaSelectRole * 3)()
+        per_phase = self.pop * self.hof
+        for ri, r in enumerate(ROLES):
+            roles[ri] = L.GaSelectRole(L._p(self.dist[r]), L._p(self.ro.rewards), L._p(self.div[r]), L._p(self.fitness[r]),
+                                       L._p(self.order[r]), L._p(self.best_dist[r]), ri * per_phase, RET_SLOT[r])
+        L.call("coevo_ga_select", roles, 3, self.pop, self.hof, self.hof)
+
+    def breed(self, gen, sigmas):
+        """elites -> elite buffer, HoF FIFO, population := [best] + (pop - 1) mutated clones (child c at pop[1 + c] from
+        elite[c % E], noise stream (c, 4 gen + role index)), the children's stale-agent distances accumulated while they
+        are written; the unchanged best keeps the distance it had"""
+        for r in ROLES:
+            self.sigma[r].fill_(float(sigmas[r]))
+        roles = (L.GaPromoteRole * 3)()
+        for ri, r in enumerate(ROLES):
+            roles[ri] = L.GaPromoteRole(self._ptr(r, "pop"), self._ptr(r, "hof"), self._ptr(r, "elite"), L._p(self.order[r]),
+                                        ROLE_D[r], 1, 1, 0)
+        L.call("coevo_ga16_promote", roles, 3, self.E, self.hof)
+        for ri, r in enumerate(ROLES):
+            L.call("coevo_fc16_perturb_dist", self._ptr(r, "elite"), L._p(self.parent_idx), self._ptr(r, "pop"), 1,
+                   self.pop - 1, ROLE_D[r], L._p(self.sigma[r]), self.philox_seed, 0, gen * 4 + ri, 0, None,
+                   self._ptr(r, "stale"), L._p(self.dist_partial[r]))
+            L.call("coevo_fc16_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop - 1,
+                   L._p(self.dist[r]), 1, L._p(self.best_dist[r]))
+        self._dist_current = True
+
+    def elite_ids(self):
+        return {r: self.order[r][:self.E].cpu().numpy().astype(int).tolist() for r in ROLES}
+
+    def diversity(self):
+        """the sharing score of each role in the last select() (float32)"""
+        return {r: np.float32(self.div[r].item()) for r in ROLES}
+
+    def run(self, generations, sigmas):
+        """`generations` whole generations with fixed mutation powers `sigmas` {role: sigma} -> {"elite_ids": [per generation
+        {role: ids}], "eval_rewards": [per generation mean triple], "diversity": [per generation {role: float32}]}"""
+        out = {"elite_ids": [], "eval_rewards": [], "diversity": []}
+        for gen in range(generations):
+            self.rollout(gen)
+            if gen > 0:
+                out["eval_rewards"].append(self.eval_rewards())
+            self.select()
+            out["elite_ids"].append(self.elite_ids())
+            out["diversity"].append(self.diversity())
+            self.breed(gen, sigmas)
+        if generations > 0:
+            out["eval_rewards"].append(self.eval_only(generations - 1))
+        return out

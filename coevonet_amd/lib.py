@@ -122,7 +122,7 @@ class GaAdaptArgs(C.Structure):     # coevo_ga_adapt_args
                 ("reserved", C.c_int32)]
 
 
-class GaPromoteRole(C.Structure):
+class GaPromoteRole(C.Structure):   # coevo_ga_promote_role, and coevo_ga16_promote_role (the same fields, untyped regions)
     _fields_ = [("pop", C.c_void_p), ("hof", C.c_void_p), ("elite", C.c_void_p), ("order", C.c_void_p),
                 ("D", C.c_int32), ("elites_from_pop", C.c_int32), ("best_to_pop0", C.c_int32), ("reserved", C.c_int32)]
 
@@ -150,6 +150,15 @@ _SIGS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "coevo_mpe16_rollout": (C.c_int, [C.POINTER(RolloutDesc), C.c_void_p, C.c_int, C.c_void_p]),
+    "coevo_fc16_perturb_blocks": (C.c_int64, [C.c_int]),
+    "coevo_fc16_perturb_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "coevo_fc16_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "coevo_fc16_distance_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p]),
+    "coevo_fc16_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "coevo_ga16_promote": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "coevo_fc_forward_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "coevo_mpe_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, PCG64State, C.c_uint64, C.c_void_p]),
@@ -356,6 +365,10 @@ def fc_slab_stride(D):
 
 def fc16_slab_stride(D):
     return int(load().coevo_fc16_slab_stride(D))
+
+
+def fc16_perturb_blocks(D):
+    return int(load().coevo_fc16_perturb_blocks(D))
 
 
 def host_tensor(ctx, shape, dtype):

@@ -543,6 +543,42 @@ int coevo_ga_promote_rebuild(const coevo_ga_promote_role *roles, int n_roles, in
 int coevo_fc_gather(const float *src_slab, const int32_t *src_idx, float *dst_slab, int dst_first, int n, int D,
                     void *stream);
 
+/* ---- float16 Co-GA breeding on an fp16 slab (coevo_fc16_pack; args.precision == "float16", MPE/fcnetwork.py:13) ----
+ * The rounding points (DESIGN.md "float16 nets"): a Linear weight or bias of a child is f16(f32(parent) + noise) with noise =
+ * sigma * eps(seed, stream, p) rounded to fp32 first - torch's half_param.data += torch.normal(0, sigma, size) (agent.py:
+ * 25-29) with the number the fp32 child of the same (seed, stream_lo, stream_hi) draws at canonical index p; round to nearest
+ * even, past 65504 inf, fp16 subnormals kept; LayerNorm gamma / beta take the fp32 rule parent + noise, unrounded.  The
+ * distance to a reference net is np.linalg.norm(a16 - b16) over get_weights_ES() (utils/game_logic_functions.py:12-37) as:
+ * d = f16(f32(a) - f32(b)) per Linear entry, d * d accumulated in fp64 in a fixed order per block of 256 16-byte pieces,
+ * dist = f16(sqrt(sum)), stored as an fp32 word that holds an fp16 value.  Every slab pointer must be 16-byte aligned. */
+int64_t coevo_fc16_perturb_blocks(int D);   /* partial sums per net: ceil(coevo_fc16_slab_stride(D) / 4 / 256) */
+/* coevo_fc_perturb_dist for fp16 slabs: child c (net child_first + c of child_slab) from net parent_idx[c] of parent_slab
+ * with noise stream (stream_lo_first + c, stream_hi [+ 4 * *gen_dev]); flags: COEVO_PERTURB_SKIP_LAYERNORM or 0; dist_ref
+ * (one net) and dist_partial [n_children][coevo_fc16_perturb_blocks(D)] are both NULL or both set.  n_children == 0 is
+ * COEVO_OK. */
+int coevo_fc16_perturb_dist(const void *parent_slab, const int32_t *parent_idx, void *child_slab, int child_first,
+                            int n_children, int D, const float *sigma_dev, uint64_t seed, uint32_t stream_lo_first,
+                            uint32_t stream_hi, int flags, const int32_t *gen_dev, const void *dist_ref,
+                            double *dist_partial, void *stream);
+/* the same partial sums for n nets that are already in a slab (generation 0, an uploaded population): bit-equal to what
+ * coevo_fc16_perturb_dist writes for a child with these words */
+int coevo_fc16_distance(const void *ref_net, const void *pop_slab, int n, int D, double *dist_partial, void *stream);
+/* dist[first + c] = f16(sqrt(sum of net c's partials)); head != NULL: also dist[first - 1] = *head, as
+ * coevo_fc_distance_finalize has it */
+int coevo_fc16_distance_finalize(const double *dist_partial, int n_blocks, int n, float *dist, int first, const float *head,
+                                 void *stream);
+/* coevo_fc_gather for fp16 slabs: dst[dst_first + i] = src[src_idx[i]], whole 16-byte words of the stride */
+int coevo_fc16_gather(const void *src_slab, const int32_t *src_idx, void *dst_slab, int dst_first, int n, int D, void *stream);
+/* coevo_ga_promote for fp16 slabs (genetic_algorithm.py:262-275): elite[k] = pop[order[k]] (k < E <= 8; skipped when
+ * elites_from_pop == 0), hof.pop(0); hof.append(elite[0]) (hof <= 16, shifted in place), pop[0] = elite[0] when
+ * best_to_pop0 != 0; up to three roles in one launch.  The fields of coevo_ga_promote_role with untyped regions. */
+typedef struct coevo_ga16_promote_role {
+    void *pop, *hof, *elite;    /* first net of each region (fp16 slab layout of width D) */
+    const int32_t *order;       /* device, [>= E]; may be NULL when elites_from_pop == 0 */
+    int32_t D, elites_from_pop, best_to_pop0, reserved;
+} coevo_ga16_promote_role;
+int coevo_ga16_promote(const coevo_ga16_promote_role *roles, int n_roles, int E, int hof, void *stream);
+
 /* K5: theta += lr/(n*sigma) * sum_i fitness[i] * (pert_i - theta) over the Linear weights/biases, i ascending
  * (compute_weight_update, evolutionary_strategy.py:120-148; the reference multiplies the stored n x P noise matrix).
  * theta is ONE net in slab layout, pert_slab the n perturbed nets coevo_fc_perturb materialised from it. */
