@@ -15,51 +15,16 @@
 //   distance               per Linear entry d = f16(f32(a) - f32(b)); d * d accumulated in fp64: the eight (or four) entries
 //                          of a thread's 16-byte piece in slab order, then block_sum_f64; one partial per 256-piece block.
 //                          dist = f16(sqrt(sum of the partials)), stored as an fp32 word.
-// A thread owns ONE 16-byte piece of the net: in W2h that is k = 8kb .. 8kb+7 of output column j = eight consecutive canonical
-// indices = two Philox quads; W3h likewise; a W1h piece is eight outputs of one input k, eight canonical indices D apart (one
-// Philox block each, 3.6 % of a net); a piece of the fp32 tail is one quad.
+// A thread owns ONE 16-byte piece of the net (fc16_pieces.hip.h, which also holds the noise of a piece: the float16 Co-ES
+// update of fc16_es.hip regenerates it from there).
 #include <hip/hip_runtime.h>
 
 #include "coevo_common.hip.h"
 #include "fc16_layout.hip.h"
+#include "fc16_pieces.hip.h"
 #include "philox.hip.h"
 
 namespace coevo {
-
-constexpr int F16_W2_PIECES = (int)(F16_W1 / 4);   // 16384 pieces of W2h
-__host__ __device__ constexpr int f16_half_pieces(int D) { return (int)(f16_off_b1(D) / 4); }   // W2h + W1h + W3h
-__host__ __device__ constexpr int f16_pieces(int D) { return (int)(f16_stride(D) / 4); }
-__host__ __device__ constexpr int f16_perturb_blocks(int D) { return (f16_pieces(D) + 255) / 256; }
-
-// word w (>= f16_off_b1) of the fp32 tail: 0 = a bias (an fp16 value), 1 = LayerNorm affine, 2 = the stride's padding
-__device__ __forceinline__ int f16_tail_kind(int w, int D)
-{
-    const int b1 = (int)f16_off_b1(D), b2 = (int)f16_off_b2(D), b3 = (int)f16_off_b3(D);
-    if (w < b2) return (w - b1) < H1 ? 0 : 1;
-    if (w < b3) return (w - b2) < H2 ? 0 : 1;
-    return w < b3 + NACT ? 0 : 2;
-}
-
-// ... and its canonical flat index (w < f16_used(D)); the three tail sections start at multiples of four in both orders
-__device__ __forceinline__ int f16_tail_flat(int w, int D)
-{
-    const int b1 = (int)f16_off_b1(D), b2 = (int)f16_off_b2(D), b3 = (int)f16_off_b3(D);
-    if (w < b2) return (int)fc_off_b1(D) + (w - b1);
-    if (w < b3) return (int)fc_off_b2(D) + (w - b2);
-    return (int)fc_off_b3(D) + (w - b3);
-}
-
-// eps(seed, stream, p) alone: the Box-Muller pair that holds element p % 4 of Philox block p / 4 (the bits of
-// philox_normal4's z[p % 4]; the other pair of the block is not evaluated)
-__device__ __forceinline__ float philox_normal1(uint64_t seed, uint32_t slo, uint32_t shi, int p)
-{
-    const u32x4 o = philox4x32<COEVO_NOISE_ROUNDS>((uint32_t)(p >> 2), slo, shi, 0x636f6576u, (uint32_t)seed,
-                                                   (uint32_t)(seed >> 32));
-    const bool hi = (p & 2) != 0;
-    float z0, z1;
-    box_muller(hi ? o.v[2] : o.v[0], hi ? o.v[3] : o.v[1], z0, z1);
-    return (p & 1) ? z1 : z0;
-}
 
 // squared distance of piece u of net a to the same piece of net b: the piece's Linear entries in slab order
 __device__ __forceinline__ double f16_piece_d2(const uint4 &a, const uint4 &b, int u, int D)
@@ -110,40 +75,23 @@ __global__ __launch_bounds__(256) void fc16_perturb_dist_kernel(const uint32_t *
         const uint4 pv = reinterpret_cast<const uint4 *>(parent_slab + (int64_t)parent_idx[c] * stride)[u];
         uint4 ov;
         if (u < f16_half_pieces(D)) {
-            float z[8];
-            const int w1_pieces = D * (H1 / 8);
-            if (u < F16_W2_PIECES || u >= F16_W2_PIECES + w1_pieces) {
-                // W2h piece (kb, j) = fc2.w[j][8kb .. 8kb+7]; W3h piece t = output.w flat 8t .. 8t+7: eight consecutive
-                // canonical indices from a multiple of eight - two Philox blocks
-                const int p0 = (u < F16_W2_PIECES)
-                                   ? (int)fc_off_w2(D) + (u & (H2 - 1)) * H1 + 8 * (u >> 8)
-                                   : (int)fc_off_w3(D) + 8 * (u - F16_W2_PIECES - w1_pieces);
-                philox_normal4(seed, slo, stream_hi, (uint32_t)(p0 >> 2), z);
-                philox_normal4(seed, slo, stream_hi, (uint32_t)(p0 >> 2) + 1u, z + 4);
-            } else {
-                // W1h[k][j0 .. j0+7] = fc1.w[j0 + i][k]: canonical (j0 + i) D + k, a Philox block each
-                const int h0 = 8 * (u - F16_W2_PIECES), k = h0 >> 9, j0 = h0 & (H1 - 1);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) z[i] = philox_normal1(seed, slo, stream_hi, (j0 + i) * D + k);
-            }
+            float noise[8];
+            f16_half_piece_noise(u, D, sigma, seed, slo, stream_hi, noise);
             _Float16 hin[8], hout[8];
             __builtin_memcpy(hin, &pv, sizeof(hin));
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float noise = sigma * z[i];               // rounded first, then added (agent.py:28-29)
-                hout[i] = (_Float16)((float)hin[i] + noise);    // the sum in fp32, rounded once to half
-            }
+            for (int i = 0; i < 8; ++i) hout[i] = (_Float16)((float)hin[i] + noise[i]);   // the sum in fp32, rounded once to half
             __builtin_memcpy(&ov, hout, sizeof(hout));
         } else {
             const int w0 = 4 * u;
-            float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (w0 < (int)f16_used(D)) philox_normal4(seed, slo, stream_hi, (uint32_t)(f16_tail_flat(w0, D) >> 2), z);
+            float noise[4];
+            f16_tail_piece_noise(u, D, sigma, seed, slo, stream_hi, noise);
             float in[4], out[4];
             __builtin_memcpy(in, &pv, sizeof(in));
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int kind = f16_tail_kind(w0 + i, D);
-                const float v = in[i] + sigma * z[i];
+                const float v = in[i] + noise[i];
                 out[i] = (kind == 0) ? f16r(v) : ((kind == 1 && !skip_layernorm) ? v : in[i]);
             }
             __builtin_memcpy(&ov, out, sizeof(out));
@@ -171,19 +119,6 @@ __global__ __launch_bounds__(256) void fc16_distance_kernel(const uint32_t *ref_
                           reinterpret_cast<const uint4 *>(ref_net)[u], u, D);
     const double tot = block_sum_f64(d2, scratch);
     if (threadIdx.x == 0) dist_partial[(size_t)n * gridDim.x + bx] = tot;
-}
-
-// fp64 -> fp16 in ONE rounding (to nearest even): to fp32 with round-to-odd first, which the fp32 -> fp16 conversion then
-// rounds as if it saw the fp64 value (fp32 carries more than two bits beyond fp16's eleven)
-__device__ inline float f16_of_f64(double s)
-{
-    float f = (float)s;
-    if ((double)f != s && !__builtin_isinf(f) && !__builtin_isnan(f)) {
-        uint32_t b = __float_as_uint(f);
-        if (__builtin_fabs((double)f) > __builtin_fabs(s)) b -= 1u;   // back to the truncated value
-        f = __uint_as_float(b | 1u);                                    // sticky bit
-    }
-    return f16r(f);
 }
 
 // dist[first + c] = f16(sqrt(sum_b partial[c][b])), dist_finalize_kernel's order (lane-strided sums, then the xor tree);

@@ -159,6 +159,11 @@ _SIGS = {
                                                C.c_void_p]),
     "coevo_fc16_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "coevo_ga16_promote": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "coevo_es16_partial_floats": (C.c_int64, [C.c_int]),
+    "coevo_es16_fitness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "coevo_es16_partial": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                     C.c_void_p, C.c_void_p]),
+    "coevo_es16_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p]),
     "coevo_fc_forward_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "coevo_mpe_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, PCG64State, C.c_uint64, C.c_void_p]),
@@ -369,6 +374,10 @@ def fc16_slab_stride(D):
 
 def fc16_perturb_blocks(D):
     return int(load().coevo_fc16_perturb_blocks(D))
+
+
+def es16_partial_floats(D):
+    return int(load().coevo_es16_partial_floats(D))
 
 
 def host_tensor(ctx, shape, dtype):

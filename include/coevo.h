@@ -579,6 +579,38 @@ typedef struct coevo_ga16_promote_role {
 } coevo_ga16_promote_role;
 int coevo_ga16_promote(const coevo_ga16_promote_role *roles, int n_roles, int E, int hof, void *stream);
 
+/* ---- float16 Co-ES update on an fp16 slab (args.precision == "float16"; evolutionary_strategy.py:63-148, 259-265) ----
+ * The reference multiplies the stored noise, rounded to half (mutate_ES(...).astype(np.float16), np.dot(noises.T, fitness) on
+ * half arrays); a float16 perturbed net is f16(f32(theta) + noise), so pert - theta is not that noise and coevo_es_partial's
+ * route does not carry over.  coevo_es16_partial draws every individual's noise again - the numbers coevo_fc16_perturb_dist
+ * (flags COEVO_PERTURB_SKIP_LAYERNORM) added for the same (seed, stream_lo_first + j, stream_hi) - and rounds it to fp16.  The
+ * rounding points (DESIGN.md 6a "Float16 Co-ES"):
+ *   noise16[j][p] = f16(sigma * eps(seed, stream_lo_first + j, stream_hi, p)), the product rounded to fp32 first; Linear
+ *                   weights and biases only; round to nearest even, fp16 subnormals kept
+ *   fit16[j]      = f16(reward_j), ONE rounding from fp64; with a sharing score f16(f32(f16(reward_j)) / (1.0f + score));
+ *                   stored as fp32 words that hold fp16 values
+ *   sum           = the canonical ES summation above: chunk c = individuals [c*n/C, (c+1)*n/C), j ascending from 0 with
+ *                   acc = fmaf(f32(fit16[j]), f32(noise16[j][p]), acc) in fp32 (the product of two halves is exact in fp32),
+ *                   chunk sums added left to right in fp32; dot16 = f16(sum), past 65504 inf.  chunks_total = 1 is numpy's
+ *                   half np.dot bit for bit.
+ *   apply         scale16 = f16(lr / (n * sigma)) (fp64 quotient of the double lr and the device fp32 sigma, one rounding),
+ *                   upd16 = f16(f32(scale16) * f32(dot16)), theta' = f16(f32(theta) + f32(upd16)).  Biases stay fp16 values in
+ *                   fp32 words; LayerNorm gamma / beta and the stride's padding keep their words.
+ * A chunk partial holds coevo_es16_partial_floats(D) floats: the net's entries in fp16-slab order with every half entry widened
+ * to one float - 8 floats per 16-byte piece of W2h, W1h, W3h (one per Linear weight),
+ * then one float per 32-bit word of the fp32 tail up to coevo_fc16_slab_stride(D), 0 at LayerNorm and padding words.
+ * partial [chunks_total][coevo_es16_partial_floats(D)] and the base net must be 16-byte aligned.  chunks_total is 1 .. 64; a
+ * chunk without an individual (n_total < chunks_total) gives a zero partial. */
+int64_t coevo_es16_partial_floats(int D);
+/* fitness[j] = f16(rewards[game_idx[j]][slot]) for j < n, rewards = play_game triples [games][3] fp64; score != NULL (device,
+ * the fp32 word of coevo_sharing_score): divided by 1.0f + *score in fp32 and rounded to fp16 again */
+int coevo_es16_fitness(const double *rewards, const int32_t *game_idx, int slot, int n, const float *score, float *fitness,
+                       void *stream);
+int coevo_es16_partial(int D, const float *fitness, int n_total, int chunks_total, const float *sigma_dev, uint64_t seed,
+                       uint32_t stream_lo_first, uint32_t stream_hi, float *partial, void *stream);
+int coevo_es16_apply(void *theta16_net, const float *partial, int chunks_total, int D, int n_total, const float *sigma_dev,
+                     double lr, void *stream);
+
 /* K5: theta += lr/(n*sigma) * sum_i fitness[i] * (pert_i - theta) over the Linear weights/biases, i ascending
  * (compute_weight_update, evolutionary_strategy.py:120-148; the reference multiplies the stored n x P noise matrix).
  * theta is ONE net in slab layout, pert_slab the n perturbed nets coevo_fc_perturb materialised from it. */
