@@ -79,7 +79,8 @@ __global__ void gather_f32_kernel(float *dst, const float *src, const int32_t *i
     if (i < n) dst[i] = src[idx[i]];
 }
 
-// score = sum_i max(0, 1 - d_i / mean(d)), mean rounded to fp32 as np.mean of an fp32 array is
+// score = sum_i max(0, 1 - d_i / mean(d)), mean rounded to fp32 as np.mean of an fp32 array is.  np.maximum propagates NaN:
+// a NaN share (mean 0, a NaN distance, inf / inf) makes the score NaN - hence !(sh <= 0), which a NaN passes, not sh > 0.
 __global__ __launch_bounds__(256) void sharing_score_kernel(const float *dist, int n, float *score)
 {
     __shared__ double scratch[4];
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(256) void sharing_score_kernel(const float *dist, i
     double sc = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) {
         const float sh = 1.0f - dist[i] / sigma;
-        if (sh > 0.0f) sc += (double)sh;
+        if (!(sh <= 0.0f)) sc += (double)sh;
     }
     const double tot = block_sum_f64(sc, scratch);
     if (threadIdx.x == 0) *score = (float)tot;
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(256) void ga_select_kernel(GaSelectArgs a)
     double sc = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) {
         const float sh = 1.0f - dist_of(i) / sigma;
-        if (sh > 0.0f) sc += (double)sh;
+        if (!(sh <= 0.0f)) sc += (double)sh;
     }
     const double tot = block_sum_f64(sc, scratch);
     if (threadIdx.x == 0) {
@@ -269,17 +270,15 @@ __global__ void ga_adapt_kernel(coevo_ga_adapt_args a)
 
 // cfg 3 extension mode (NOT in the reference, which has its normalisation commented out at
 // evolutionary_strategy.py:133-135): centered ranks u_i = rank_i / (n-1) - 0.5, rank_i = number of individuals that sort
-// before i in a stable ascending sort (ties: lower index first).  One thread per individual, any n.
+// before i in a stable ascending sort (ties: lower index first; NaN last, -0 == +0: rank_less).  One thread per individual,
+// any n.
 __global__ __launch_bounds__(256) void centered_rank_kernel(const float *f, int n, float *out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float fi = f[i];
     int rank = 0;
-    for (int j = 0; j < n; ++j) {
-        const float fj = f[j];
-        rank += (fj < fi || (fj == fi && j < i)) ? 1 : 0;
-    }
+    for (int j = 0; j < n; ++j) rank += rank_less(f[j], j, fi, i) ? 1 : 0;
     out[i] = (n > 1) ? (float)rank / (float)(n - 1) - 0.5f : 0.0f;
 }
 

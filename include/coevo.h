@@ -633,13 +633,15 @@ int coevo_es_partial(const float *theta_net, const float *pert_slab_local, int i
 int coevo_es_apply(float *theta_net, const float *partials, int chunks_total, int chunks_per_block,
                    int64_t block_stride_floats, int D, int n_total, const float *sigma_dev, float lr, void *stream);
 /* cfg 3 extension mode (BASELINE.json configs[2]; the reference's own normalisation is commented out at
- * evolutionary_strategy.py:133-135): out[i] = rank_i / (n-1) - 0.5, stable ascending rank (ties: lower index first) */
+ * evolutionary_strategy.py:133-135): out[i] = rank_i / (n-1) - 0.5, stable ascending rank (ties: lower index first; NaN
+ * last as in np.argsort, -0 == +0) */
 int coevo_centered_ranks(const float *fitness, int n, float *out, void *stream);
 
 /* ---------------------------------------------------------------- K6/K7: fitness, sharing, selection -------- */
 /* distances d[i] = || w_i - w_ref ||_2 over the Linear weights/biases (get_weights_ES default layers) and the
  * sharing score sum_i max(0, 1 - d_i/mean(d)) (utils/game_logic_functions.py:12-37). ref_net is one net in slab
- * layout, pop_slab holds n nets.  dist [n] fp32, score one fp32. */
+ * layout, pop_slab holds n nets.  dist [n] fp32, score one fp32.  As np.maximum does, the max propagates NaN: a NaN share
+ * (mean 0, a NaN distance, inf/inf) makes the score NaN. */
 int coevo_fc_diversity(const float *ref_net, const float *pop_slab, int n, int D, float *dist, float *score,
                        void *stream);
 /* the distances alone (the part each GPU computes for its population shard) */

@@ -335,7 +335,7 @@ double oracle_diversity(const float *individual, const float *w, int n, size_t s
     double score = 0.0;
     for (int i = 0; i < n; ++i) {
         float sh = 1.0f - d[i] / sigma;
-        if (sh > 0.0f) score += sh;
+        if (!(sh <= 0.0f)) score += sh;   /* np.maximum(0, sh): a NaN share makes the score NaN */
     }
     free(d);
     return score;

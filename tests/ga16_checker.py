@@ -77,7 +77,8 @@ def f16_bits(x):
 # test_diversity_fitness_rank pins the device kernels to the same expressions).
 def sharing_score(dist):
     """the oracle's sharing arithmetic (oracle_diversity) on given distances: each distance is handed over as a one-entry
-    'net' against a zero individual, whose fp64 sqrt(d * d) is d again"""
+    'net' against a zero individual, whose fp64 sqrt(d * d) is d again.  A NaN share (all distances 0, a NaN or two infinite
+    distances) makes the score NaN, as np.maximum does in the reference's expression"""
     dist = np.ascontiguousarray(dist, dtype=np.float32)
     zero = np.zeros(1, dtype=np.float32)
     so, sl = np.array([0], dtype=np.int32), np.array([1], dtype=np.int32)
