@@ -25,7 +25,7 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 # So: export it yourself for a process that runs the host-cores mode after a graph-replaying mode and is short-lived, or do
 # what bench.py does - run the host-cores mode in a process of its own.
 
-__all__ = ["HalfGAEngine", "HalfESEngine"]
+__all__ = ["HalfGAEngine", "HalfESEngine", "DeepQNHalf"]
 
 
 def __getattr__(name):
@@ -36,4 +36,7 @@ def __getattr__(name):
     if name == "HalfESEngine":
         from .es_half import HalfESEngine
         return HalfESEngine
+    if name == "DeepQNHalf":
+        from .deepqn import DeepQNHalf
+        return DeepQNHalf
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -16,7 +16,8 @@ class Agent:
     def mutate(self, noise_std):
         """GA mutation: every parameter (LayerNorm affine included) += N(0, noise_std), drawn with the global torch
         generator in parameters() order, exactly as agent.py:25-29 does (host_reference RNG mode).  On a float16 net the
-        Linear tensors are half: torch adds the fp32 noise in fp32 and rounds the sum once to half, as in the reference."""
+        half tensors - the Linear layers of FCNetworkHalf, every parameter of DeepQNHalf, the BatchNorm affine included - take
+        torch's own update: the fp32 noise is added in fp32 and the sum rounded once to half, as in the reference."""
         for param in self.model.parameters():
             noise = torch.normal(0, noise_std, size=param.size())
             param.data += noise

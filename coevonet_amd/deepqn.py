@@ -188,16 +188,113 @@ class DeepQN:
         return int(actions[0])
 
 
-def batched_actions(nets_flat, frames_per_net, C, n_actions, device="cuda", fc1_tiled=False):
+class DeepQNHalf:
+    """``DeepQN(input_channels, n_actions, "float16")`` of the reference (Atari/deepqn.py:12-37): every module is converted
+    with ``.to(torch.float16)``, so all sixteen parameters - the BatchNorm affine included, unlike FCNetwork's LayerNorms -
+    and the BatchNorm running statistics are half.  ``DeepQN`` itself is float32-only, so the half net is this sibling with
+    the same surface (it is to ``DeepQN`` what ``FCNetworkHalf`` is to ``FCNetwork``); ``AtariAgent`` builds it when
+    ``args.precision == "float16"``.
+
+    Each parameter is its own torch-CPU half tensor, so ``param.data += noise`` (Agent.mutate) is the reference's own update
+    (the sum in fp32, rounded once to half).  ``flat()`` is the fp32 image in the canonical order (fp16 values are exact in
+    fp32); the forward runs in libcoevo's float16 kernels (coevo_dqn16_forward_argmax), never on the CPU."""
+
+    def __init__(self, input_channels, n_actions, precision="float16"):
+        if precision != "float16":
+            raise ValueError(f"DeepQNHalf is the float16 net, not {precision}")
+        # the fp32 init consumes the global generator exactly like the reference's constructions (Atari/deepqn.py:16-37);
+        # the reference then converts each module with .to(float16) (round to nearest even)
+        full = DeepQN(input_channels, n_actions, "float32")
+        self.dtype = torch.float16
+        self.input_channels, self.n_actions, self.precision = full.input_channels, full.n_actions, precision
+        self._params = OrderedDict((k, v.detach().to(torch.float16).clone()) for k, v in full._params.items())
+        self.layers = []
+        for name in LAYER_ORDER:
+            layer = _Layer(name, self._params[name + ".weight"], self._params[name + ".bias"])
+            setattr(self, name, layer)
+            self.layers.append(layer)
+        # the BatchNorm buffers in the module's dtypes: running statistics half, the batch counter long
+        self._buffers = OrderedDict(
+            (k, v.clone() if v.dtype == torch.long else v.to(torch.float16)) for k, v in full._buffers.items())
+
+    # the accessors of Atari/deepqn.py:63-231 that do not depend on the dtype are DeepQN's own functions
+    parameters = DeepQN.parameters
+    named_modules = DeepQN.named_modules
+    state_dict = DeepQN.state_dict
+    get_weights = DeepQN.get_weights
+    set_weights = DeepQN.set_weights
+    get_perturbable_layers = DeepQN.get_perturbable_layers
+    get_weights_ES = DeepQN.get_weights_ES                   # float16: the reference concatenates the half tensors' numpy views
+    get_perturbable_weights = DeepQN.get_perturbable_weights
+    set_perturbable_weights = DeepQN.set_perturbable_weights
+    _to_frames = staticmethod(DeepQN._to_frames)
+
+    def load_state_dict(self, sd, strict=True):
+        for k, v in self._params.items():
+            if k in sd:
+                v.copy_(torch.as_tensor(sd[k]).to(v.dtype))
+            elif strict:
+                raise KeyError(f"Missing key in state_dict: {k}")
+        for k, v in self._buffers.items():
+            if k in sd:
+                v.copy_(torch.as_tensor(sd[k]).to(v.dtype))
+
+    def set_weights_ES(self, flat_weights, args, layers=None):
+        """(:174-215) the slices become half tensors by the reference's own torch.tensor(slice, dtype=float16); default: the
+        perturbable layers"""
+        layers = self.get_perturbable_layers() if layers is None else layers
+        flat_weights = np.asarray(flat_weights)
+        i = 0
+        for layer in layers:
+            for t in (layer.weight, layer.bias):
+                n = t.numel()
+                t.copy_(torch.tensor(flat_weights[i:i + n].reshape(tuple(t.shape)), dtype=t.dtype))   # as :196 / :204
+                i += n
+
+    def flat(self):
+        """the whole net in the canonical order as float32 holding fp16 values (a copy)"""
+        return np.concatenate([self._params[k].detach().to(torch.float32).numpy().ravel() for k in PARAM_ORDER])
+
+    def set_flat(self, flat):
+        flat = torch.as_tensor(np.asarray(flat, dtype=np.float32))
+        off = 0
+        for k in PARAM_ORDER:
+            v = self._params[k]
+            n = v.numel()
+            v.copy_(flat[off:off + n].view(v.shape).to(v.dtype))
+            off += n
+
+    def forward(self, x):
+        logits, _ = batched_actions([self.flat()], [self._to_frames(x).numpy()], self.input_channels, self.n_actions,
+                                    precision="float16")
+        return torch.from_numpy(logits[0][None]).to(torch.float16)
+
+    def determine_action(self, inputs, args):
+        _, actions = batched_actions([self.flat()], [self._to_frames(inputs).numpy()], self.input_channels,
+                                     self.n_actions, precision="float16")
+        return int(actions[0])
+
+
+def batched_actions(nets_flat, frames_per_net, C, n_actions, device="cuda", fc1_tiled=False, precision="float32"):
     """nets_flat: list of flat parameter vectors; frames_per_net: list of uint8 arrays [r_i, 84, 84, C] (r_i <= 16).
     -> (logits [sum r_i, n_actions] float32, actions [sum r_i] int32).  One task per net.  fc1_tiled: the slab keeps fc1 in
-    the layout of v_mfma_f32_16x16x4 (include/coevo.h COEVO_DQN_FC1_TILED; same results)"""
+    the layout of v_mfma_f32_16x16x4 (include/coevo.h COEVO_DQN_FC1_TILED; same results).  precision "float16": the nets
+    are packed into an fp16 slab (coevo_dqn16_pack rounds every entry to half) and run through
+    coevo_dqn16_forward_argmax; the logits are float32 holding fp16 values"""
+    if precision not in ("float32", "float16"):
+        raise ValueError(f"Unsupported precision: {precision}")
+    half = precision == "float16"
+    if half and fc1_tiled:
+        raise ValueError("the fp16 slab has one fc1 layout: fc1_tiled does not apply to precision float16")
+    sym = "coevo_dqn16" if half else "coevo_dqn"
     n_nets = len(nets_flat)
     Cw = C | (L.DQN_FC1_TILED if fc1_tiled else 0)
-    stride = int(L.load().coevo_dqn_slab_stride(C, n_actions))
+    stride = int(getattr(L.load(), sym + "_slab_stride")(C, n_actions))
+    if stride < 0:
+        raise ValueError("unsupported DeepQN shape for the HIP kernels (1..6 channels, <= 32 actions)")
     flat = torch.from_numpy(np.ascontiguousarray(np.stack(nets_flat), dtype=np.float32)).to(device)
-    slab = torch.zeros(n_nets, stride, dtype=torch.float32, device=device)
-    L.call("coevo_dqn_pack", L._p(flat), L._p(slab), n_nets, Cw, n_actions)
+    slab = torch.zeros(n_nets, stride, dtype=torch.int32 if half else torch.float32, device=device)
+    L.call(sym + "_pack", L._p(flat), L._p(slab), n_nets, Cw, n_actions)
     tasks = np.zeros(n_nets, dtype=L.DQN_TASK_DTYPE)
     row = 0
     for i, fr in enumerate(frames_per_net):
@@ -209,8 +306,8 @@ def batched_actions(nets_flat, frames_per_net, C, n_actions, device="cuda", fc1_
     actions = torch.zeros(row, dtype=torch.int32, device=device)
     logits = torch.zeros(row, L.DQN_LOGIT_STRIDE, dtype=torch.float32, device=device)
     status = torch.zeros(1, dtype=torch.int32, device=device)
-    ws = torch.zeros(int(L.load().coevo_dqn_workspace_bytes(row)) // 4, dtype=torch.float32, device=device)
-    L.call("coevo_dqn_forward_argmax", L._p(slab), L._p(d_tasks), n_nets, int(max(f.shape[0] for f in frames_per_net)),
+    ws = torch.zeros(int(getattr(L.load(), sym + "_workspace_bytes")(row)) // 4, dtype=torch.float32, device=device)
+    L.call(sym + "_forward_argmax", L._p(slab), L._p(d_tasks), n_nets, int(max(f.shape[0] for f in frames_per_net)),
            row, Cw, n_actions, L._p(frames), L._p(actions), L._p(logits), L._p(status), L._p(ws))
     L.raise_on_status(status)
     return logits[:, :n_actions].cpu().numpy(), actions.cpu().numpy()
@@ -222,7 +319,9 @@ class AtariAgent(Agent):
     def __init__(self, env, args):
         self.input_channels = env.observation_space(env.agents[0]).shape[-1]
         self.n_actions = env.action_space(env.agents[0]).n
-        self.model = DeepQN(self.input_channels, self.n_actions, args.precision)
+        # Atari/deepqn.py:12: precision "float16" makes every module half (DeepQN here is float32-only)
+        net = DeepQNHalf if args.precision == "float16" else DeepQN
+        self.model = net(self.input_channels, self.n_actions, args.precision)
         self.optimizer = None
         super().__init__(self.model, self.optimizer, args)
 

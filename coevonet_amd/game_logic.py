@@ -197,7 +197,8 @@ def play_MPE(env, player1, player2, adversary, args, eval):
 
 def play_atari(env, player1, player2, args, eval=False):
     """utils/game_logic_functions.py:84-119 (its own signature has no eval flag - quirk Q10; the call site at :227 passes
-    one, so it is accepted here and selects the step limit as for MPE)"""
+    one, so it is accepted here and selects the step limit as for MPE).  Two float16 players (DeepQNHalf, not a DeepQN)
+    walk the AEC loop, one coevo_dqn16_forward_argmax per agent-step: the device episode route is float32-only"""
     from .deepqn import DeepQN
     if isinstance(env, SyntheticAtariAEC) and isinstance(player1, DeepQN) and isinstance(player2, DeepQN) \
             and not getattr(args, "coevo_host_aec", False):

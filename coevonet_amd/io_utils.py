@@ -8,6 +8,9 @@
 * ``save_state_dicts`` writes, beside every pickle, ``<name>.state_dict.pth``: plain ``OrderedDict``s of tensors (one
   ``state_dict()`` per agent, keys = the reference's parameter names) that ``torch.load(..., weights_only=True)`` accepts
   - no code object is unpickled; ``agents_from_state_dicts`` rebuilds the ``Agent`` objects from them.
+  A float16 agent's state_dict holds ``torch.float16`` tensors (``FCNetworkHalf``: the Linear layers; ``DeepQNHalf``: every
+  parameter and the BatchNorm running statistics), and ``create_agent`` under ``args.precision == "float16"`` rebuilds the
+  half net they load into, so both writers carry half agents unchanged.
 * ``MetricsWriter`` replaces the three matplotlib savefigs per generation (utils/utils_pth_and_plots.py:153-262, 2.6 s per
   generation in the reference, and a crash without --adaptive at :235) with one JSON line per generation.
 """

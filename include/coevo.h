@@ -722,6 +722,33 @@ int coevo_dqn_unpack(const float *slab, float *flat, int n, int C, int n_actions
 /* n nets from a slab of one fc1 layout into a slab of the other (channel arguments of the two slabs; slab strides are equal) */
 int coevo_dqn_relayout(const float *src_slab, float *dst_slab, int n, int C_src, int C_dst, int n_actions, void *stream);
 
+/* ---------------------------------------------------------------- DeepQN in float16 ------------------------------- */
+/* DeepQN with args.precision == "float16" (Atari/deepqn.py:12-37: every conv, Linear and BatchNorm module is half).  The
+ * fp16 slab keeps fc1.weight (95 % of a net) as 2-byte values, tiled [out block of 64][k / 8][out % 64][k % 8] - a lane's
+ * 16-byte load holds eight consecutive k of its own output - and every other entry (conv weights in the fp32 slab's lane
+ * order, biases, BatchNorm affine, the output matrix) as an fp32 word that holds an fp16 value: 884 710 words for C = 4,
+ * n = 6 against 1 687 526.  Strides and coevo_dqn_task.net_off count 32-bit words; a net starts at a multiple of 4 words.
+ * Arithmetic: DESIGN.md 6a "Float16 DeepQN" - the canonical fp32 chains on fp16 values, rounded once to fp16 after /255,
+ * after every conv, BatchNorm and Linear. */
+int64_t coevo_dqn16_slab_stride(int C, int n_actions);   /* 32-bit words between consecutive nets; COEVO_ERR_ARG for a bad shape */
+/* flat[n][P] fp32 in coevo_dqn_param_count's canonical order <-> slab; pack rounds every entry to fp16 to nearest even
+ * (exact for fp16 values) and zeroes the stride's padding */
+int coevo_dqn16_pack(const float *flat, void *slab, int n, int C, int n_actions, void *stream);
+int coevo_dqn16_unpack(const void *slab, float *flat, int n, int C, int n_actions, void *stream);
+int64_t coevo_dqn16_workspace_bytes(int n_rows_total);   /* conv3 activations + fc1 outputs of every row */
+/* coevo_dqn_forward_argmax for fp16 slabs: the same arguments; logits (or NULL) are fp16 values stored as fp32, n_actions
+ * per row (the other floats of a row are not written), actions the first maximum.  C is the plain channel count 1 .. 6
+ * (COEVO_DQN_FC1_TILED or any other bit is COEVO_ERR_ARG), the slab pointer must be 16-byte aligned, max_rows_per_task is
+ * 1 .. COEVO_DQN_MAX_ROWS and otherwise advisory here: the one kernel form serves every task by its own n_rows, so a task
+ * with more rows than max_rows_per_task (and at most COEVO_DQN_MAX_ROWS) is served, not refused.  The tasks must tile the
+ * rows 0 .. n_rows_total-1 contiguously in ascending row_begin order: a row in a gap between two tasks is attributed to the
+ * task in front of it, whose fc1 launch never computes it.  A task whose n_rows is outside 1 .. COEVO_DQN_MAX_ROWS or whose net_off is not a multiple of 4
+ * words is skipped with COEVO_ST_BAD_TASK: nothing is written for its rows.  status bits are or-ed into *status.  Three
+ * launches on `stream`; synchronises with nothing and creates nothing. */
+int coevo_dqn16_forward_argmax(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
+                               int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *actions,
+                               float *logits, int32_t *status, void *workspace, void *stream);
+
 /* ---------------------------------------------------------------- DeepQN population engine (cfg 4 / cfg 5) ---------- */
 /* Offspring of the DeepQN layout on the device: child = parent +- sigma * eps(seed, stream, p), p = canonical flat index
  * (the order above), same Philox / Box-Muller as coevo_fc_perturb.  Replaces AtariAgent.clone + Agent.mutate
