@@ -30,6 +30,7 @@ from . import lib as L
 from .atari_synthetic import SYNTH_SEED
 from .deepqn import DeepQN
 from .genetic_algorithm import N_EVAL, adapt_mutation_power
+from .population import NetTable, SlabIO, slab_layout
 
 ROLES2 = ("first_0", "second_0")
 SIGMA2 = ("mutation_power_agent_0", "mutation_power_agent_1")
@@ -326,22 +327,19 @@ def dqn_init_flat(C, n_actions):
     return DeepQN(C, n_actions, "float32").flat().copy()
 
 
-class _SlabMixin:
-    def _ptr(self, role, region, i=0):
-        return self.slab.data_ptr() + 4 * (self.base[role][region] + i * self.stride)
+class _DQNSlabIO(SlabIO):
+    """one scalar stride / P for both roles; the layout-dependent entry points take (Cw, n_actions)"""
+    _pack_unpack = ("coevo_dqn_pack", "coevo_dqn_unpack")
+
+    def _net_args(self, role):
+        return (self.Cw, self.n_actions)
 
     def upload(self, role, region, first, flat_np):
-        flat = torch.from_numpy(np.ascontiguousarray(flat_np, dtype=np.float32)).to(self.device)
-        L.call("coevo_dqn_pack", L._p(flat), self._ptr(role, region, first), flat.shape[0], self.Cw, self.n_actions)
+        super().upload(role, region, first, flat_np)
         torch.cuda.current_stream().synchronize()
 
-    def download(self, role, region, first, n):
-        out = torch.zeros(n, self.P, dtype=torch.float32, device=self.device)
-        L.call("coevo_dqn_unpack", self._ptr(role, region, first), L._p(out), n, self.Cw, self.n_actions)
-        return out.cpu().numpy()
 
-
-class DQNGAEngine(_SlabMixin):
+class DQNGAEngine(_DQNSlabIO):
     def __init__(self, pop, hof, elites, C, n_actions, T_train, T_eval, device="cuda", env_seed=SYNTH_SEED,
                  philox_seed=0, shard=(0, 1), gather=None, first_ordinal=1, capacity=1024, sigmas=(0.05, 0.05),
                  sig_min=0.001, sig_max=0.2, adaptive=True, frames="device"):
@@ -365,23 +363,13 @@ class DQNGAEngine(_SlabMixin):
         lib = L.load()
         self.stride = int(lib.coevo_dqn_slab_stride(C, n_actions))
         self.P = int(lib.coevo_dqn_param_count(C, n_actions))
-        self.base, off = {}, 0
-        for r in ROLES2:
-            self.base[r] = {}
-            for region, count in (("pop", pop), ("hof", hof), ("elite", elites), ("stale", 1), ("hof_tmp", hof),
-                                  ("elite_prev", elites)):
-                self.base[r][region] = off
-                off += count * self.stride
-        self.slab = torch.zeros(off, dtype=torch.float32, device=device)
+        strides = dict.fromkeys(ROLES2, self.stride)
+        self.base, total = slab_layout(ROLES2, (("pop", pop), ("hof", hof), ("elite", elites), ("stale", 1), ("hof_tmp", hof),
+                                                ("elite_prev", elites)), strides)
+        self.slab = torch.zeros(total, dtype=torch.float32, device=device)
         # ---- games of one generation launch (this rank's individuals) + the evaluation games of the previous one
-        net_off, ids = [], {}
-
-        def net(region, role, i):
-            key = (region, role, i)
-            if key not in ids:
-                ids[key] = len(net_off)
-                net_off.append(self.base[role][region] + i * self.stride)
-            return ids[key]
+        net = NetTable(self.base, strides)
+        net_off = net.net_off
 
         h, M = hof, 2 * pop * hof
         self.per_gen = M + N_EVAL
@@ -653,7 +641,7 @@ def es_cohort_bounds(n_local, K):
     return [2 * (k * n_local // K) for k in range(K)] + [2 * n_local] if K > 1 else None
 
 
-class DQNESEngine(_SlabMixin):
+class DQNESEngine(_DQNSlabIO):
     def __init__(self, pop, C, n_actions, T_train, T_eval, device="cuda", env_seed=SYNTH_SEED, philox_seed=0,
                  shard=(0, 1), gather=None, first_ordinal=1, antithetic=False, centered_rank=False, chunks=8,
                  frames="device"):
@@ -676,11 +664,8 @@ class DQNESEngine(_SlabMixin):
         lib = L.load()
         self.stride = int(lib.coevo_dqn_slab_stride(C, n_actions))
         self.P = int(lib.coevo_dqn_param_count(C, n_actions))
-        self.base, off = {}, 0
-        for r in ROLES2:
-            self.base[r] = {"base": off, "pert": off + self.stride}
-            off += (1 + self.n_local) * self.stride
-        self.slab = torch.zeros(off, dtype=torch.float32, device=device)
+        self.base, total = slab_layout(ROLES2, (("base", 1), ("pert", self.n_local)), dict.fromkeys(ROLES2, self.stride))
+        self.slab = torch.zeros(total, dtype=torch.float32, device=device)
         self.per_gen = 2 * pop + N_EVAL
         net_off = [self.base["first_0"]["base"], self.base["second_0"]["base"]]
         games, ordinal0 = [], []

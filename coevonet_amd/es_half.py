@@ -21,21 +21,19 @@ import torch
 
 from . import lib as L
 from .evolutionary_strategy import ES_CHUNKS
-from .genetic_algorithm import N_EVAL, RET_SLOT, ROLE_D, ROLES
+from .genetic_algorithm import RET_SLOT
 from .mpe.simple_adversary import ENV_SEED
+from .population import N_EVAL, ROLE_D, ROLES, CoESSchedule, NetTable, SlabIO, co_es_games, slab_layout
 from .rollout import DeviceRollout, RolloutPlan, effective_steps
 
-# The game table and the rollout / evaluation calls below follow ESEngine's (evolutionary_strategy.py) line by line: ESEngine
-# cannot take a precision while the trainers must keep refusing float16.  The trainer switch folds the two
-# into one table builder.
 
-
-class HalfESEngine:
+class HalfESEngine(SlabIO, CoESSchedule):
     """Device-resident float16 base and perturbed nets of the three roles and the per-generation steps.
 
     ``perturb(gen, sigmas)`` -> ``rollout(gen)`` -> ``update(gen, lr, fitness_sharing)`` -> ``evaluate(gen)`` is one
     generation (``generation`` does the four); ``run`` loops them.  Nets go in and out as flat float32 arrays of fp16 values in
     parameters() order (``FCNetworkHalf.flat()``)."""
+    _pack_unpack = ("coevo_fc16_pack", "coevo_fc16_unpack")   # flat arrays carry fp16 values in float32
 
     def __init__(self, pop, limit_train=None, limit_eval=None, max_cycles=25, device="cuda", env_seed=ENV_SEED,
                  philox_seed=0, first_ordinal=1, chunks=ES_CHUNKS, *, rng="device_philox", env="device", shard=(0, 1),
@@ -61,37 +59,19 @@ class HalfESEngine:
         # ---- slab layout (32-bit words): per role [base | pert x pop] ----------------------------------------------
         self.stride = {r: L.fc16_slab_stride(ROLE_D[r]) for r in ROLES}
         self.P = {r: L.fc_param_count(ROLE_D[r]) for r in ROLES}
-        self.base, off = {}, 0
-        for r in ROLES:
-            self.base[r] = {"base": off, "pert": off + self.stride[r]}
-            off += (1 + self.pop) * self.stride[r]
-        self.slab = torch.zeros(off, dtype=torch.int32, device=device)
-        # ---- ESEngine's game table: game 3j + role = perturbed net j of the role against the two other base nets ----
-        net_off, net_D, ids = [], [], {}
-
-        def net(region, role, i=0):
-            key = (region, role, i)
-            if key not in ids:
-                ids[key] = len(net_off)
-                net_off.append(self.base[role][region] + i * self.stride[role])
-                net_D.append(ROLE_D[role])
-            return ids[key]
-
-        games = []
-        for j in range(self.pop):   # evolutionary_strategy.py:236-251: mutate_weights for agent_0, agent_1, adversary_0
-            for r in ROLES:
-                seat = {q: net("base", q) for q in ROLES}
-                seat[r] = net("pert", r, j)
-                games.append((seat["adversary_0"], seat["agent_0"], seat["agent_1"]))
+        self.base, total = slab_layout(ROLES, (("base", 1), ("pert", self.pop)), self.stride)
+        self.slab = torch.zeros(total, dtype=torch.int32, device=device)
+        # ---- the Co-ES game table of the whole population on this GPU (population.co_es_games) ----------------------
+        self.lo, self.hi, self.n_local, self.env_mode = 0, self.pop, self.pop, "device"
+        table = NetTable(self.base, self.stride, ROLE_D)
+        games, eval_games = co_es_games(table, self.pop)   # (the evaluation games: a rollout of their own, after the update)
         self.n_main = len(games)
-        # the evaluation games play the UPDATED base nets (and sigma_{g+1} may depend on them): their own plan, after the update
-        eval_games = [(net("base", "adversary_0"), net("base", "agent_0"), net("base", "agent_1"))] * N_EVAL
         heavy_rows = int(os.environ.get("COEVO_HEAVY_ROWS", "32"))
         es_cohorts = int(os.environ.get("COEVO_ES_COHORTS", "2"))
-        self.plan = RolloutPlan(np.array(games), net_off, net_D, device=device, heavy_rows=heavy_rows, n_cohorts=es_cohorts,
-                                row_order="class")
+        self.plan = RolloutPlan(np.array(games), table.net_off, table.net_D, device=device, heavy_rows=heavy_rows,
+                                n_cohorts=es_cohorts, row_order="class")
         self.ro = DeviceRollout(self.plan, self.slab, env_seed=env_seed, precision="float16")
-        self.eval_plan = RolloutPlan(np.array(eval_games), net_off, net_D, device=device, split_rows=5)
+        self.eval_plan = RolloutPlan(np.array(eval_games), table.net_off, table.net_D, device=device, split_rows=5)
         self.eval_ro = DeviceRollout(self.eval_plan, self.slab, env_seed=env_seed, precision="float16")
         # ---- small device buffers ----------------------------------------------------------------------------------
         f32 = dict(dtype=torch.float32, device=device)
@@ -108,26 +88,11 @@ class HalfESEngine:
         self._dist_gen = None   # the generation whose perturb() left the distance partials behind
         self.steps_per_generation = 3 * self.pop * self.T_train + N_EVAL * self.T_eval
 
-    # ------------------------------------------------------------------ loading weights
-    def _ptr(self, role, region, i=0):
-        return self.slab.data_ptr() + 4 * (self.base[role][region] + i * self.stride[role])
-
-    def upload(self, role, region, first, flat_np):
-        """flat_np [n][P] (parameters() order, fp16 values in float32) -> nets first.. of a region ("base" or "pert")"""
-        flat = torch.from_numpy(np.ascontiguousarray(flat_np, dtype=np.float32)).to(self.device)
-        L.call("coevo_fc16_pack", L._p(flat), self._ptr(role, region, first), flat.shape[0], ROLE_D[role])
+    # ------------------------------------------------------------------ loading weights (population.SlabIO)
+    def _uploaded(self, region):
         self._dist_gen = None   # (the distance partials perturb() left behind no longer describe the slab)
-        return flat   # keep alive until the stream has consumed it
 
-    def download(self, role, region, first, n):
-        out = torch.zeros(n, self.P[role], dtype=torch.float32, device=self.device)
-        L.call("coevo_fc16_unpack", self._ptr(role, region, first), L._p(out), n, ROLE_D[role])
-        return out.cpu().numpy()
-
-    # ------------------------------------------------------------------ one generation
-    def _ordinal_base(self, gen):
-        return self.first_ordinal + gen * (3 * self.pop + N_EVAL)
-
+    # ------------------------------------------------------------------ one generation (rollout, evaluate: population.CoESSchedule)
     def perturb(self, gen, sigmas, fitness_sharing=False):
         """perturbed net j of role ri = f16(f32(base) + sigma eps) on the Linear entries, noise stream (j, 4 gen + ri):
         ESEngine.perturb_device's numbering.  fitness_sharing: the distances to the base net are accumulated while the nets
@@ -139,19 +104,6 @@ class HalfESEngine:
                    self._ptr(r, "base") if fitness_sharing else None,
                    L._p(self.dist_partial[r]) if fitness_sharing else None)
         self._dist_gen = gen if fitness_sharing else None
-
-    def rollout(self, gen):
-        """the 3 * pop training games of generation `gen` (game ordinal 3j + role in the seeded stream)"""
-        ro = self.ro
-        ro.set_limits(np.full(self.plan.n_games, self.T_train, dtype=np.int32))
-        ro.reset(0, self.n_main, self._ordinal_base(gen))
-        if ro.n_cohorts > 1:
-            ro.enqueue((self.T_train + 2) // 3)   # cohort chains overlap only when enqueued eagerly
-        else:
-            ro.run((self.T_train + 2) // 3)
-
-    def rewards_host(self):
-        return self.ro.rewards.cpu().numpy()
 
     def update(self, gen, lr, fitness_sharing):
         """compute_weight_update (evolutionary_strategy.py:120-148) on half arrays + base += update, on the device; sigma is
@@ -175,20 +127,6 @@ class HalfESEngine:
             L.call("coevo_es16_apply", self._ptr(r, "base"), L._p(self.partial[r]), self.chunks, D, self.pop,
                    L._p(self.sigma[r]), float(lr))
         self._dist_gen = None   # the base nets moved
-
-    def evaluate(self, gen):
-        """evaluate_current_weights: 10 games of the current base trio -> mean reward triple (:22-59, :272)"""
-        ro = self.eval_ro
-        ro.set_limits(np.full(N_EVAL, self.T_eval, dtype=np.int32))
-        ro.reset(0, N_EVAL, self._ordinal_base(gen) + 3 * self.pop)
-        ro.run((self.T_eval + 2) // 3)
-        ro.check_status()
-        r = ro.rewards.cpu().numpy()
-        tot = [0.0, 0.0, 0.0]
-        for g in range(N_EVAL):   # python-float accumulation order of evaluate_current_weights
-            for s in range(3):
-                tot[s] += float(r[g, s])
-        return [t / 10 for t in tot]
 
     def diversity(self):
         """the sharing score of each role in the last update() with fitness sharing (float32)"""

@@ -35,6 +35,7 @@ from . import lib as L
 from .game_logic import create_agent
 from .genetic_algorithm import N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, adapt_mutation_power
 from .mpe.simple_adversary import ENV_SEED
+from .population import CoESSchedule, NetTable, SlabIO, co_es_games, slab_layout
 from .rollout import DeviceRollout, HostEnvRollout, RolloutPlan, effective_steps
 
 
@@ -90,7 +91,7 @@ def compute_weight_update(noises, rewards, args, role, individual_weights=None, 
 ES_CHUNKS = 8   # the canonical ES summation: this many chunk sums, added left to right (include/coevo.h, K5)
 
 
-class ESEngine:
+class ESEngine(SlabIO, CoESSchedule):
     def __init__(self, pop, limit_train=None, limit_eval=None, max_cycles=25, device="cuda", env_seed=ENV_SEED,
                  rng="device_philox", philox_seed=0, env="device", first_ordinal=1, shard=(0, 1), gather=None,
                  antithetic=False, centered_rank=False, chunks=ES_CHUNKS):
@@ -113,32 +114,11 @@ class ESEngine:
         self.first_ordinal = first_ordinal
         self.stride = {r: L.fc_slab_stride(ROLE_D[r]) for r in ROLES}
         self.P = {r: L.fc_param_count(ROLE_D[r]) for r in ROLES}
-        self.base, off = {}, 0
-        for r in ROLES:
-            self.base[r] = {"base": off, "pert": off + self.stride[r]}
-            off += (1 + self.n_local) * self.stride[r]
-        self.slab = torch.zeros(off, dtype=torch.float32, device=device)
-        net_off, net_D, ids = [], [], {}
-
-        def net(region, role, i=0):
-            key = (region, role, i)
-            if key not in ids:
-                ids[key] = len(net_off)
-                net_off.append(self.base[role][region] + i * self.stride[role])
-                net_D.append(ROLE_D[role])
-            return ids[key]
-
-        games = []
-        for j in range(self.n_local):  # evolutionary_strategy.py:236-251: mutate_weights for agent_0, agent_1, adversary_0
-            for r in ROLES:
-                seat = {q: net("base", q) for q in ROLES}
-                seat[r] = net("pert", r, j)
-                games.append((seat["adversary_0"], seat["agent_0"], seat["agent_1"]))
+        self.base, total = slab_layout(ROLES, (("base", 1), ("pert", self.n_local)), self.stride)
+        self.slab = torch.zeros(total, dtype=torch.float32, device=device)
+        table = NetTable(self.base, self.stride, ROLE_D)
+        games, eval_games = co_es_games(table, self.n_local)   # (the evaluation games: a rollout of their own, after the update)
         self.n_main = len(games)
-        # Unlike Co-GA, the evaluation games cannot ride in the next generation's launch: generation g+1 perturbs with
-        # sigma_{g+1}, which the adaptive rule derives from generation g's evaluation (evolutionary_strategy.py:272-316).
-        # They get their own 10-game rollout after each update.
-        eval_games = [(net("base", "adversary_0"), net("base", "agent_0"), net("base", "agent_1"))] * N_EVAL
         cls = DeviceRollout if env == "device" else HostEnvRollout
         heavy_rows = int(os.environ.get("COEVO_HEAVY_ROWS", "32"))
         # device env: 2 cohorts (114 vs 109 generations/s at cfg3); env on the host cores: COEVO_HOST_COHORTS alternating
@@ -149,12 +129,12 @@ class ESEngine:
         if env != "device" and es_cohorts > 1 and len(games) >= es_cohorts:
             # contiguous game ranges (a core then owns whole cache lines of the struct-of-arrays game state)
             game_cohort = (np.arange(len(games)) * es_cohorts // len(games)).astype(np.int32)
-        self.plan = RolloutPlan(np.array(games), net_off, net_D, device=device, heavy_rows=heavy_rows,
+        self.plan = RolloutPlan(np.array(games), table.net_off, table.net_D, device=device, heavy_rows=heavy_rows,
                                 n_cohorts=es_cohorts, game_cohort=game_cohort,
                                 row_order="class" if env == "device" else "cohort")
         self.ro = cls(self.plan, self.slab, env_seed=env_seed)
         # the 10 evaluation games: three nets x 10 rows, as two 5-row streaming tasks per net (1.0 -> 0.5 ms)
-        self.eval_plan = RolloutPlan(np.array(eval_games), net_off, net_D, device=device, split_rows=5)
+        self.eval_plan = RolloutPlan(np.array(eval_games), table.net_off, table.net_D, device=device, split_rows=5)
         self.eval_ro = cls(self.eval_plan, self.slab, env_seed=env_seed)
         f32 = dict(dtype=torch.float32, device=device)
         self.fitness = {r: torch.zeros(pop, **f32) for r in ROLES}
@@ -177,22 +157,6 @@ class ESEngine:
         self.partials = torch.zeros(self.world * self.part_block, **f32)
         self.steps_per_generation = 3 * pop * self.T_train + N_EVAL * self.T_eval
 
-    def _ptr(self, role, region, i=0):
-        return self.slab.data_ptr() + 4 * (self.base[role][region] + i * self.stride[role])
-
-    def upload(self, role, region, first, flat_np):
-        flat = torch.from_numpy(np.ascontiguousarray(flat_np, dtype=np.float32)).to(self.device)
-        L.call("coevo_fc_pack", L._p(flat), self._ptr(role, region, first), flat.shape[0], ROLE_D[role])
-        return flat
-
-    def download(self, role, region, first, n):
-        out = torch.zeros(n, self.P[role], dtype=torch.float32, device=self.device)
-        L.call("coevo_fc_unpack", self._ptr(role, region, first), L._p(out), n, ROLE_D[role])
-        return out.cpu().numpy()
-
-    def _ordinal_base(self, gen):
-        return self.first_ordinal + gen * (3 * self.pop + N_EVAL)
-
     def perturb_device(self, gen, sigmas):
         """this rank's perturbed nets: individual j (global index) of role ri takes noise stream (j, 4*gen + ri)"""
         flags = 1 | (2 if self.antithetic else 0)   # LayerNorm untouched; antithetic pairs in the extension mode
@@ -200,42 +164,6 @@ class ESEngine:
             self.sigma[r].fill_(float(sigmas[r]))
             L.call("coevo_fc_perturb_flags", self._ptr(r, "base"), L._p(self.zero_idx), self._ptr(r, "pert"), 0,
                    self.n_local, ROLE_D[r], L._p(self.sigma[r]), self.philox_seed, self.lo, gen * 4 + ri, flags)
-
-    def rollout(self, gen):
-        """this rank's 3*n_local training games of generation `gen` (game ordinal 3j + role in the seeded stream)"""
-        ro = self.ro
-        ro.set_limits(np.full(self.plan.n_games, self.T_train, dtype=np.int32))
-        first = self._ordinal_base(gen) + 3 * self.lo
-        if self.env_mode == "device":
-            ro.reset(0, self.n_main, first)
-        else:
-            ro.reset_from_ordinals(first + np.arange(self.n_main))
-        if getattr(ro, "n_cohorts", 1) > 1:
-            ro.enqueue((self.T_train + 2) // 3)  # cohort chains overlap only when enqueued eagerly
-        else:
-            ro.run((self.T_train + 2) // 3)
-
-    def evaluate(self, gen):
-        """evaluate_current_weights: 10 games of the current base trio -> mean reward triple (:22-59, :272)"""
-        ro = self.eval_ro
-        ro.set_limits(np.full(N_EVAL, self.T_eval, dtype=np.int32))
-        first = self._ordinal_base(gen) + 3 * self.pop
-        if self.env_mode == "device":
-            ro.reset(0, N_EVAL, first)
-        else:
-            ro.reset_from_ordinals(first + np.arange(N_EVAL))
-        ro.run((self.T_eval + 2) // 3)
-        ro.check_status()
-        r = ro.rewards.cpu().numpy() if torch.is_tensor(ro.rewards) else ro.rewards
-        tot = [0.0, 0.0, 0.0]
-        for g in range(N_EVAL):
-            for s in range(3):
-                tot[s] += float(r[g, s])
-        return [t / 10 for t in tot]
-
-    def rewards_host(self):
-        r = self.ro.rewards
-        return r.cpu().numpy() if torch.is_tensor(r) else r
 
     def update_device(self, gen, lr, fitness_sharing):
         """compute_weight_update (evolutionary_strategy.py:120-148) + base += update, on the device.  Sharded: the

@@ -16,21 +16,19 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .genetic_algorithm import N_EVAL, RET_SLOT, ROLE_D, ROLES
+from .genetic_algorithm import RET_SLOT
 from .mpe.simple_adversary import ENV_SEED
+from .population import N_EVAL, ROLE_D, ROLES, CoGASchedule, NetTable, SlabIO, co_ga_games, slab_layout
 from .rollout import DeviceRollout, RolloutPlan, effective_steps
 
-# The game table, the rollout / evaluation calls and load_initial below follow GAEngine's (genetic_algorithm.py) line by line:
-# GAEngine cannot take a precision while the trainers must keep refusing float16.  The trainer switch
-# folds the two into one table builder.
-REGIONS = ("pop", "hof", "elite", "stale", "hof_tmp")
 
-
-class HalfGAEngine:
+class HalfGAEngine(SlabIO, CoGASchedule):
     """Device-resident float16 population / HoF / elites of the three roles and the per-generation steps.
 
     ``rollout(gen)`` -> ``select()`` -> ``breed(gen, sigmas)`` is one generation; ``run(generations, sigmas)`` loops them.
     Nets go in and out as flat float32 arrays of fp16 values in parameters() order (``FCNetworkHalf.flat()``)."""
+    _pack_unpack = ("coevo_fc16_pack", "coevo_fc16_unpack")   # flat arrays carry fp16 values in float32
+    one_reset = True   # the whole population is on this GPU: one reset launch for the three phases
 
     def __init__(self, pop, hof, elites, limit_train=None, limit_eval=None, max_cycles=25, device="cuda",
                  env_seed=ENV_SEED, philox_seed=0, first_ordinal=1, *, adaptive=False, shard=(0, 1), env="device",
@@ -56,39 +54,14 @@ class HalfGAEngine:
         # ---- slab layout (32-bit words): per role [pop | hof | elite | stale | hof_tmp] -----------------------
         self.stride = {r: L.fc16_slab_stride(ROLE_D[r]) for r in ROLES}
         self.P = {r: L.fc_param_count(ROLE_D[r]) for r in ROLES}
-        self.base, off = {}, 0
-        for r in ROLES:
-            self.base[r] = {}
-            for region, count in zip(REGIONS, (pop, hof, elites, 1, hof)):
-                self.base[r][region] = off
-                off += count * self.stride[r]
-        self.slab = torch.zeros(off, dtype=torch.int32, device=device)
-        # ---- GAEngine's game table: Q2 / Q4 seats, then the N_EVAL games of the newest HoF trio ----------------
-        net_off, net_D, ids = [], [], {}
-
-        def net(region, role, i):
-            key = (region, role, i)
-            if key not in ids:
-                ids[key] = len(net_off)
-                net_off.append(self.base[role][region] + i * self.stride[role])
-                net_D.append(ROLE_D[role])
-            return ids[key]
-
-        games, h = [], hof
-        for role in ROLES:
-            for i in range(pop):
-                for k in range(h):
-                    if role == "agent_0":      # genetic_algorithm.py:136-142
-                        a0, a1, adv = net("pop", role, i), net("hof", "agent_1", h - 1 - k), net("hof", "adversary_0", h - 1 - k)
-                    elif role == "agent_1":    # :168-174
-                        a0, a1, adv = net("hof", "agent_0", h - 1 - k), net("pop", role, i), net("hof", "adversary_0", h - 1 - k)
-                    else:                      # :201-207, Q4: agent_1's seat is also filled from hof_agent_0
-                        a0, a1, adv = net("hof", "agent_0", h - 1 - k), net("hof", "agent_0", h - 1 - k), net("pop", role, i)
-                    games.append((adv, a0, a1))
-        self.n_main = len(games)
-        for _ in range(N_EVAL):   # evaluate_current_weights(best trio) = the newest HoF members (:12-29, :301)
-            games.append((net("hof", "adversary_0", h - 1), net("hof", "agent_0", h - 1), net("hof", "agent_1", h - 1)))
-        self.plan = RolloutPlan(np.array(games), net_off, net_D, device=device, heavy_rows=16, row_order="class")
+        self.base, total = slab_layout(ROLES, (("pop", pop), ("hof", hof), ("elite", elites), ("stale", 1), ("hof_tmp", hof)),
+                                       self.stride)
+        self.slab = torch.zeros(total, dtype=torch.int32, device=device)
+        # ---- the Co-GA game table of the whole population on this GPU (population.co_ga_games) ------------------
+        self.lo, self.hi, self.n_local, self.env_mode = 0, pop, pop, "device"
+        table = NetTable(self.base, self.stride, ROLE_D)
+        games, self.n_main = co_ga_games(table, 0, pop, hof)
+        self.plan = RolloutPlan(np.array(games), table.net_off, table.net_D, device=device, heavy_rows=16, row_order="class")
         self.ro = DeviceRollout(self.plan, self.slab, env_seed=env_seed, precision="float16")
         # ---- small device buffers ------------------------------------------------------------------------------
         f32 = dict(dtype=torch.float32, device=device)
@@ -104,71 +77,15 @@ class HalfGAEngine:
         self._dist_current = False
         self.steps_per_generation = 3 * pop * hof * self.T_train + N_EVAL * self.T_eval
 
-    # ------------------------------------------------------------------ loading weights
-    def _ptr(self, role, region, i=0):
-        return self.slab.data_ptr() + 4 * (self.base[role][region] + i * self.stride[role])
-
-    def upload(self, role, region, first, flat_np):
-        """flat_np [n][P] (parameters() order, fp16 values in float32) -> nets first.. of a region"""
-        flat = torch.from_numpy(np.ascontiguousarray(flat_np, dtype=np.float32)).to(self.device)
-        L.call("coevo_fc16_pack", L._p(flat), self._ptr(role, region, first), flat.shape[0], ROLE_D[role])
+    # ------------------------------------------------------------------ loading weights (population.SlabIO)
+    def _uploaded(self, region):
         if region in ("pop", "stale"):
             self._dist_current = False   # (the distances breed() left behind no longer describe the slab)
-        return flat   # keep alive until the stream has consumed it
 
-    def download(self, role, region, first, n):
-        out = torch.zeros(n, self.P[role], dtype=torch.float32, device=self.device)
-        L.call("coevo_fc16_unpack", self._ptr(role, region, first), L._p(out), n, ROLE_D[role])
-        return out.cpu().numpy()
-
-    def load_initial(self, pop_flat, hof_flat):
-        """pop_flat[role] [pop][P], hof_flat[role] [hof][P]; the stale agent of Q3 is the initial pop[pop-1]"""
-        keep = []
-        for r in ROLES:
-            keep.append(self.upload(r, "pop", 0, pop_flat[r]))
-            keep.append(self.upload(r, "hof", 0, hof_flat[r]))
-            keep.append(self.upload(r, "stale", 0, pop_flat[r][self.pop - 1:self.pop]))
-        torch.cuda.current_stream().synchronize()
-
-    # ------------------------------------------------------------------ one generation
-    def _ordinal_base(self, gen):
-        return self.first_ordinal + gen * (3 * self.pop * self.hof + N_EVAL)
-
+    # ------------------------------------------------------------------ one generation (schedule: population.CoGASchedule)
     def rollout(self, gen):
-        """plays generation `gen`'s 3 * pop * hof games and, riding along from generation 1 on, the evaluation games of
-        generation gen - 1 (they depend only on that generation's selection: GAEngine.rollout)"""
-        limits = np.zeros(self.plan.n_games, dtype=np.int32)
-        limits[:self.n_main] = self.T_train
-        if gen > 0:
-            limits[self.n_main:] = self.T_eval
-        self.ro.set_limits(limits)
-        self.ro.reset(0, self.n_main, self._ordinal_base(gen))
-        if gen > 0:
-            self.ro.reset(self.n_main, N_EVAL, self._ordinal_base(gen - 1) + self.n_main)
-        self.ro.run(self.n_cycles)
-
-    def eval_only(self, gen):
-        """the evaluation games of generation `gen` alone (the flush after the last generation) -> their mean triple"""
-        limits = np.zeros(self.plan.n_games, dtype=np.int32)
-        limits[self.n_main:] = self.T_eval
-        self.ro.set_limits(limits)
-        self.ro.reset(0, self.n_main, 0)
-        self.ro.reset(self.n_main, N_EVAL, self._ordinal_base(gen) + self.n_main)
-        self.ro.run((self.T_eval + 2) // 3)
-        return self.eval_rewards()
-
-    def rewards_host(self):
-        return self.ro.rewards.cpu().numpy()
-
-    def eval_rewards(self):
-        """mean reward triple (agent_0, agent_1, adversary_0) of the evaluation games in the last rollout"""
-        self.ro.check_status()
-        r = self.rewards_host()[self.n_main:]
-        tot = [0.0, 0.0, 0.0]
-        for g in range(N_EVAL):   # python-float accumulation order of evaluate_current_weights
-            for s in range(3):
-                tot[s] += float(r[g, s])
-        return [t / 10 for t in tot]
+        """generation `gen`'s games and, riding along from generation 1 on, the evaluation games of generation gen - 1"""
+        super().rollout(gen, gen > 0)
 
     def select(self):
         """fitness sharing + fitness + ranking of the three roles in one launch; the elite ids stay on the device"""

@@ -34,15 +34,14 @@ from . import lib as L
 from .fcnetwork import FCNetwork
 from .game_logic import create_agent
 from .mpe.simple_adversary import ENV_SEED
+from .population import (N_EVAL, ROLE_D, ROLES, CoGASchedule, NetTable, SlabIO, co_ga_games, mean_eval_triple,
+                         slab_layout)
 from .rollout import DeviceRollout, HostEnvRollout, RolloutPlan, effective_steps
 
-ROLES = ("agent_0", "agent_1", "adversary_0")
-ROLE_D = {"agent_0": 10, "agent_1": 10, "adversary_0": 8}
 ROLE_SLOT = {"agent_0": 1, "agent_1": 2, "adversary_0": 0}   # env slot the role acts in
 RET_SLOT = {"agent_0": 0, "agent_1": 1, "adversary_0": 2}    # position in play_game's return triple
 SIGMA_ATTR = {"agent_0": "mutation_power_agent_0", "agent_1": "mutation_power_agent_1",
               "adversary_0": "mutation_power_adversary"}
-N_EVAL = 10
 
 
 # ---- the reference's per-call helpers under their own names (genetic_algorithm.py:12-48): the sequential forms a caller of
@@ -151,7 +150,7 @@ DEVICE_LOOP_COHORTS = 2   # ... in the host-free loop, where their launches are 
 SMALL_SHARD = 80          # ... unless a rank holds fewer individuals per role than this: then one chain
 
 
-class GAEngine:
+class GAEngine(SlabIO, CoGASchedule):
     """Device-resident population / HoF / elites of the three roles and the per-generation pipeline.
 
     shard = (rank, world): this process evaluates individuals [lo, hi) of every role (contiguous ranges, all HoF games
@@ -178,43 +177,15 @@ class GAEngine:
         self.n_cycles = (max(self.T_train, self.T_eval) + 2) // 3
         self.first_ordinal = first_ordinal
         self.env_seed = env_seed
-        # ---- slab layout: per role [pop | hof | elite | stale | hof_tmp] -----------------------------------
+        # ---- slab layout: per role [pop | hof | elite | stale | hof_tmp | elite_prev] ----------------------
         self.stride = {r: L.fc_slab_stride(ROLE_D[r]) for r in ROLES}
         self.P = {r: L.fc_param_count(ROLE_D[r]) for r in ROLES}
-        self.base, off = {}, 0
-        for r in ROLES:
-            self.base[r] = {}
-            for region, count in (("pop", pop), ("hof", hof), ("elite", elites), ("stale", 1), ("hof_tmp", hof),
-                                  ("elite_prev", elites)):
-                self.base[r][region] = off
-                off += count * self.stride[r]
-        self.slab = torch.zeros(off, dtype=torch.float32, device=device)
-        # ---- game table of one generation launch -----------------------------------------------------------
-        net_off, net_D, ids = [], [], {}
-
-        def net(region, role, i):
-            key = (region, role, i)
-            if key not in ids:
-                ids[key] = len(net_off)
-                net_off.append(self.base[role][region] + i * self.stride[role])
-                net_D.append(ROLE_D[role])
-            return ids[key]
-
-        games = []
-        h = hof
-        for role in ROLES:
-            for i in range(self.lo, self.hi):
-                for k in range(h):
-                    if role == "agent_0":      # genetic_algorithm.py:136-142
-                        a0, a1, adv = net("pop", role, i), net("hof", "agent_1", h - 1 - k), net("hof", "adversary_0", h - 1 - k)
-                    elif role == "agent_1":    # :168-174
-                        a0, a1, adv = net("hof", "agent_0", h - 1 - k), net("pop", role, i), net("hof", "adversary_0", h - 1 - k)
-                    else:                      # :201-207, Q4: agent_1's seat is also filled from hof_agent_0
-                        a0, a1, adv = net("hof", "agent_0", h - 1 - k), net("hof", "agent_0", h - 1 - k), net("pop", role, i)
-                    games.append((adv, a0, a1))
-        self.n_main = len(games)
-        for _ in range(N_EVAL):  # evaluate_current_weights(best trio) = newest HoF members (:12-29, :301)
-            games.append((net("hof", "adversary_0", h - 1), net("hof", "agent_0", h - 1), net("hof", "agent_1", h - 1)))
+        self.base, total = slab_layout(ROLES, (("pop", pop), ("hof", hof), ("elite", elites), ("stale", 1), ("hof_tmp", hof),
+                                               ("elite_prev", elites)), self.stride)
+        self.slab = torch.zeros(total, dtype=torch.float32, device=device)
+        # ---- game table of one generation launch (population.co_ga_games) ----------------------------------
+        table = NetTable(self.base, self.stride, ROLE_D)
+        games, self.n_main = co_ga_games(table, self.lo, self.hi, hof)
         # 16-row shared-opponent tasks select the lean merged cycle kernel (four workgroups per CU); COEVO_HEAVY_ROWS=32
         # keeps the 32-row tiles for A/B runs
         # (host-stepped env: the same 16-row tasks, for the observation-fed merged launch coevo_fc_forward_merged)
@@ -245,17 +216,17 @@ class GAEngine:
                 return ()
             ind_bytes = sum(4 * self.stride[r] for r in ROLES)
             n = resident_prefix(resident_budget_bytes(), (hof + elites + 1) * ind_bytes, ind_bytes, self.cohort_bounds)
-            return [ids[("pop", r, self.lo + i)] for r in ROLES for k in range(self.K)
+            return [table.ids[("pop", r, self.lo + i)] for r in ROLES for k in range(self.K)
                     for i in range(int(self.cohort_bounds[k]), int(self.cohort_bounds[k]) + int(n[k]))]
 
         try:
-            self.plan = RolloutPlan(np.array(games), net_off, net_D, device=device, heavy_rows=heavy_rows,
+            self.plan = RolloutPlan(np.array(games), table.net_off, table.net_D, device=device, heavy_rows=heavy_rows,
                                     n_cohorts=self.K, game_cohort=game_cohort, row_order=row_order,
                                     resident_nets=resident_nets())
         except ValueError:  # tiny populations: the shared opponents have so few rows that they tie all games together
             self.K = 1
             self._set_cohort_bounds()
-            self.plan = RolloutPlan(np.array(games), net_off, net_D, device=device, heavy_rows=heavy_rows,
+            self.plan = RolloutPlan(np.array(games), table.net_off, table.net_D, device=device, heavy_rows=heavy_rows,
                                     row_order=row_order, resident_nets=resident_nets())
         if env == "device":
             self.ro = DeviceRollout(self.plan, self.slab, env_seed=env_seed, timing_pairs=timing_pairs)
@@ -282,92 +253,22 @@ class GAEngine:
         self.steps_per_generation = 3 * pop * hof * self.T_train + N_EVAL * self.T_eval
 
     # ------------------------------------------------------------------ loading weights
-    def _ptr(self, role, region, i=0):
-        return self.slab.data_ptr() + 4 * (self.base[role][region] + i * self.stride[role])
-
-    def upload(self, role, region, first, flat_np):
-        """flat_np [n][P] (parameters() order) -> nets first.. of a region"""
-        flat = torch.from_numpy(np.ascontiguousarray(flat_np, dtype=np.float32)).to(self.device)
-        L.call("coevo_fc_pack", L._p(flat), self._ptr(role, region, first), flat.shape[0], ROLE_D[role])
+    def _uploaded(self, region):
         if region in ("pop", "stale"):
             self._dist_current = False   # (the stale-agent distances breed_device() left behind no longer describe the slab)
-        return flat  # keep alive until the stream has consumed it
 
     def download(self, role, region, first, n):
         if region == "pop":
             self.flush_breeding()
-        out = torch.zeros(n, self.P[role], dtype=torch.float32, device=self.device)
-        L.call("coevo_fc_unpack", self._ptr(role, region, first), L._p(out), n, ROLE_D[role])
-        return out.cpu().numpy()
+        return super().download(role, region, first, n)
 
-    def load_initial(self, pop_flat, hof_flat):
-        """pop_flat[role] [pop][P], hof_flat[role] [hof][P]; the stale agent of Q3 is the initial pop[pop-1]"""
-        keep = []
-        for r in ROLES:
-            keep.append(self.upload(r, "pop", 0, pop_flat[r]))
-            keep.append(self.upload(r, "hof", 0, hof_flat[r]))
-            keep.append(self.upload(r, "stale", 0, pop_flat[r][self.pop - 1:self.pop]))
-        torch.cuda.current_stream().synchronize()
-
-    # ------------------------------------------------------------------ one generation
-    def _ordinal_base(self, gen):
-        return self.first_ordinal + gen * (3 * self.pop * self.hof + N_EVAL)
-
-    def rollout(self, gen, with_prev_eval):
-        """plays generation `gen`'s 3*n_local*hof games and, riding along, the 10 evaluation games of gen-1"""
-        ro, M = self.ro, 3 * self.pop * self.hof
-        limits = np.zeros(self.plan.n_games, dtype=np.int32)
-        limits[:self.n_main] = self.T_train
-        if with_prev_eval:
-            limits[self.n_main:] = self.T_eval
-        ro.set_limits(limits)
-        base = self._ordinal_base(gen)
-        per_phase = self.n_local * self.hof
-        if self.env_mode == "device":
-            for ph in range(3):
-                ro.reset(ph * per_phase, per_phase, base + ph * self.pop * self.hof + self.lo * self.hof)
-            if with_prev_eval:
-                ro.reset(self.n_main, N_EVAL, self._ordinal_base(gen - 1) + M)
-        else:
-            ords = np.zeros(self.plan.n_games, dtype=np.int64)
-            for ph in range(3):
-                ords[ph * per_phase:(ph + 1) * per_phase] = (base + ph * self.pop * self.hof + self.lo * self.hof
-                                                             + np.arange(per_phase))
-            ords[self.n_main:] = (self._ordinal_base(gen - 1) + M + np.arange(N_EVAL)) if with_prev_eval else 0
-            ro.reset_from_ordinals(ords)
-        ro.run(self.n_cycles)
-
-    def eval_only(self, gen):
-        """flush: the evaluation games of generation `gen` alone (main games disabled)"""
-        ro, M = self.ro, 3 * self.pop * self.hof
-        limits = np.zeros(self.plan.n_games, dtype=np.int32)
-        limits[self.n_main:] = self.T_eval
-        ro.set_limits(limits)
-        if self.env_mode == "device":
-            ro.reset(0, self.n_main, 0)
-            ro.reset(self.n_main, N_EVAL, self._ordinal_base(gen) + M)
-        else:
-            ords = np.zeros(self.plan.n_games, dtype=np.int64)
-            ords[self.n_main:] = self._ordinal_base(gen) + M + np.arange(N_EVAL)
-            ro.reset_from_ordinals(ords)
-        ro.run((self.T_eval + 2) // 3)
-        return self.eval_rewards()
-
-    def rewards_host(self):
-        r = self.ro.rewards
-        return r.cpu().numpy() if torch.is_tensor(r) else r
-
+    # ------------------------------------------------------------------ one generation (schedule: population.CoGASchedule)
     def eval_rewards(self):
         """mean reward triple (agent_0, agent_1, adversary_0) of the 10 evaluation games in the last rollout"""
         self.ro.check_status()
         if hasattr(self.ro, "collect_stamps"):
             self.ro.collect_stamps()  # check_status synchronised: this replay's kernel clock stamps are final
-        r = self.rewards_host()[self.n_main:]
-        tot = [0.0, 0.0, 0.0]
-        for g in range(N_EVAL):  # python-float accumulation order of evaluate_current_weights
-            for s in range(3):
-                tot[s] += float(r[g, s])
-        return [t / 10 for t in tot]
+        return mean_eval_triple(self.rewards_host()[self.n_main:])
 
     def select(self):
         """fitness sharing + fitness + ranking of all three roles on the device -> elite ids stay on the device"""

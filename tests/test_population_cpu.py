@@ -1,0 +1,247 @@
+"""coevonet_amd/population.py: the one slab layout, net numbering and game-table builder of the six engines.
+
+tests/golden/engine_tables.json holds what GAEngine, HalfGAEngine, ESEngine and HalfESEngine handed to RolloutPlan when each
+still built its own table (tests/golden/make_golden_tables.py): the shared functions must give the same lists, element for
+element.  The seat rules are then stated once more, independently, as a closed formula of the game index."""
+import json
+import os
+
+import pytest
+
+from coevonet_amd import population as P
+
+ROLES, ROLE_D, N_EVAL = P.ROLES, P.ROLE_D, P.N_EVAL
+GA_REGIONS = ("pop", "hof", "elite", "stale", "hof_tmp", "elite_prev")
+
+
+@pytest.fixture(scope="module")
+def tables(golden_dir):
+    with open(os.path.join(golden_dir, "engine_tables.json")) as f:
+        return json.load(f)
+
+
+def ga_regions(pop, hof, elites, elite_prev):
+    return list(zip(GA_REGIONS, (pop, hof, elites, 1, hof, elites)))[:6 if elite_prev else 5]
+
+
+def build(rec):
+    """the fixture's case through the shared functions, from its constructor arguments and strides alone"""
+    a, stride = rec["args"], rec["stride"]
+    rank, world = a.get("shard", (0, 1))
+    lo, hi = rank * a["pop"] // world, (rank + 1) * a["pop"] // world
+    if "hof" in a:
+        regions = ga_regions(a["pop"], a["hof"], a["elites"], elite_prev=rec["engine"] == "GAEngine")
+    else:
+        regions = [("base", 1), ("pert", hi - lo)]
+    base, total = P.slab_layout(ROLES, regions, stride)
+    table = P.NetTable(base, stride, ROLE_D)
+    if "hof" in a:
+        games, n_main = P.co_ga_games(table, lo, hi, a["hof"])
+        eval_games = None
+    else:
+        games, eval_games = P.co_es_games(table, hi - lo)
+        n_main = len(games)
+    return dict(lo=lo, hi=hi, base=base, total=total, n_main=n_main, games=[list(g) for g in games],
+                net_off=table.net_off, net_D=table.net_D, eval_games=eval_games and [list(g) for g in eval_games])
+
+
+CASES = ["ga_f32", "ga_f16", "ga_f32_shard", "es_f32", "es_f16", "es_f32_shard"]
+
+
+def test_the_fixture_holds_the_shapes_that_take_every_branch(tables):
+    assert sorted(tables) == sorted(CASES)
+    assert tables["ga_f32"]["args"] == tables["ga_f16"]["args"] == dict(pop=5, hof=3, elites=2)
+    assert tables["ga_f32_shard"]["args"] == dict(pop=6, hof=2, elites=2, shard=[1, 2]) and tables["ga_f32_shard"]["lo"] == 3
+    assert tables["es_f32"]["args"] == tables["es_f16"]["args"] == dict(pop=3)
+    assert tables["es_f32_shard"]["args"] == dict(pop=4, shard=[1, 2]) and tables["es_f32_shard"]["lo"] == 2
+    assert [tables[c]["engine"] for c in CASES] == ["GAEngine", "HalfGAEngine", "GAEngine", "ESEngine", "HalfESEngine",
+                                                    "ESEngine"]
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_layout_nets_and_games_equal_what_each_engine_built_on_its_own(tables, case):
+    rec, got = tables[case], build(tables[case])
+    for key in ("lo", "hi", "base", "total", "n_main", "net_off", "net_D", "games"):
+        assert got[key] == rec[key], key
+    if case.startswith("es"):
+        assert got["eval_games"] == rec["eval_games"] and len(got["eval_games"]) == N_EVAL
+    else:
+        assert "eval_games" not in rec and len(got["games"]) == got["n_main"] + N_EVAL
+
+
+def test_slab_layout_is_role_major_region_by_region():
+    stride = {"a": 3, "b": 5}
+    base, total = P.slab_layout(("a", "b"), [("x", 2), ("y", 0), ("z", 1)], stride)
+    assert base == {"a": {"x": 0, "y": 6, "z": 6}, "b": {"x": 9, "y": 19, "z": 19}} and total == 24
+
+
+def test_net_table_numbers_by_first_use_and_leaves_net_D_empty_without_widths():
+    base, _ = P.slab_layout(("a", "b"), [("x", 2), ("z", 1)], {"a": 3, "b": 5})
+    t = P.NetTable(base, {"a": 3, "b": 5}, {"a": 10, "b": 8})
+    assert [t("z", "b"), t("x", "a", 1), t("z", "b", 0), t("x", "a"), t("x", "a", 1)] == [0, 1, 0, 2, 1]
+    assert t.net_off == [9 + 10, 3, 0] and t.net_D == [8, 10, 10]
+    assert t.ids == {("z", "b", 0): 0, ("x", "a", 1): 1, ("x", "a", 0): 2}
+    u = P.NetTable(base, {"a": 3, "b": 5})
+    assert u("x", "b", 1) == 0 and u.net_off == [14] and u.net_D == []
+
+
+class Seats:
+    """a table that answers with the key itself: games come back as (region, role, i) triples"""
+
+    def __call__(self, region, role, i=0):
+        return (region, role, i)
+
+
+@pytest.mark.parametrize("lo,hi,hof", [(0, 5, 3), (3, 6, 2), (0, 1, 1), (2, 4, 4)])
+def test_co_ga_seat_of_every_game_by_closed_formula(lo, hi, hof):
+    """genetic_algorithm.py:119-301 of the reference: phase `role`, individual i, k-th game against Hall of Fame member
+    hof - 1 - k (newest first, so that the game that counts, the last one, meets the oldest: Q2); in the adversary's phase BOTH
+    good seats hold agent_0's member (Q4)"""
+    games, n_main = P.co_ga_games(Seats(), lo, hi, hof)
+    n = hi - lo
+    assert n_main == 3 * n * hof and len(games) == n_main + N_EVAL
+    for g, (adv, a0, a1) in enumerate(games[:n_main]):
+        ph, i, k = g // (n * hof), lo + g % (n * hof) // hof, g % hof
+        m = hof - 1 - k
+        want = {"adversary_0": ("hof", "adversary_0", m), "agent_0": ("hof", "agent_0", m), "agent_1": ("hof", "agent_1", m)}
+        if ROLES[ph] == "adversary_0":
+            want["agent_1"] = ("hof", "agent_0", m)
+        want[ROLES[ph]] = ("pop", ROLES[ph], i)
+        assert (adv, a0, a1) == (want["adversary_0"], want["agent_0"], want["agent_1"]), g
+    newest = hof - 1
+    assert games[n_main:] == [(("hof", "adversary_0", newest), ("hof", "agent_0", newest), ("hof", "agent_1", newest))] * N_EVAL
+
+
+@pytest.mark.parametrize("n", [1, 3, 4])
+def test_co_es_seat_of_every_game_by_closed_formula(n):
+    """evolutionary_strategy.py:236-251 of the reference: game 3j + role seats perturbed net j of that role (rank-local index)
+    against the two other roles' base nets; the evaluation games seat the base trio"""
+    games, eval_games = P.co_es_games(Seats(), n)
+    assert len(games) == 3 * n
+    for g, (adv, a0, a1) in enumerate(games):
+        j, r = g // 3, ROLES[g % 3]
+        want = {q: ("base", q, 0) for q in ROLES}
+        want[r] = ("pert", r, j)
+        assert (adv, a0, a1) == (want["adversary_0"], want["agent_0"], want["agent_1"]), g
+    assert eval_games == [(("base", "adversary_0", 0), ("base", "agent_0", 0), ("base", "agent_1", 0))] * N_EVAL
+
+
+def test_net_ids_follow_first_use_in_the_co_es_table():
+    """the three base nets first (agent_0, agent_1, adversary_0: the order the seats are filled in), then each perturbed net
+    as its game comes up"""
+    ones = dict.fromkeys(ROLES, 1)
+    t = P.NetTable(P.slab_layout(ROLES, [("base", 1), ("pert", 2)], ones)[0], ones, ROLE_D)
+    games, eval_games = P.co_es_games(t, 2)
+    assert games == [(2, 3, 1), (2, 0, 4), (5, 0, 1), (2, 6, 1), (2, 0, 7), (8, 0, 1)]
+    assert eval_games == [(2, 0, 1)] * N_EVAL
+
+
+def test_float32_and_float16_co_ga_tables_differ_only_by_stride(tables):
+    f32, f16 = tables["ga_f32"], tables["ga_f16"]
+    a = f32["args"]
+    assert f32["stride"] != f16["stride"]
+    assert f32["games"] == f16["games"] and f32["net_D"] == f16["net_D"] and f32["n_main"] == f16["n_main"]
+
+    def keys_of(rec, elite_prev):
+        """each net of the table as (role, region, index), recovered from its offset"""
+        base, _ = P.slab_layout(ROLES, ga_regions(a["pop"], a["hof"], a["elites"], elite_prev), rec["stride"])
+        t = P.NetTable(base, rec["stride"], ROLE_D)
+        P.co_ga_games(t, 0, a["pop"], a["hof"])
+        assert t.net_off == rec["net_off"]
+        return sorted(t.ids, key=t.ids.get)
+
+    assert keys_of(f32, True) == keys_of(f16, False)
+    # the same functions on the other precision's strides give the other precision's table, up to the float32 slab's elite_prev
+    for rec, other, elite_prev in ((f32, f16, False), (f16, f32, True)):
+        base, _ = P.slab_layout(ROLES, ga_regions(a["pop"], a["hof"], a["elites"], elite_prev), other["stride"])
+        t = P.NetTable(base, other["stride"], ROLE_D)
+        games, _ = P.co_ga_games(t, 0, a["pop"], a["hof"])
+        assert [list(g) for g in games] == rec["games"] and t.net_off == other["net_off"] and base == other["base"]
+
+
+def test_mean_eval_triple_keeps_the_python_float_accumulation_order():
+    """ten rows whose sum depends on the order: 1e16 + 1 - 1e16 is 0 left to right and 1 in any order that cancels first"""
+    import numpy as np
+    rows = np.array([[1e16, 3.0, 0.1], [1.0, 1e16, 0.2], [-1e16, 1.0, 0.3], [1.0, -1e16, 0.1], [1e16, 1.0, 0.7],
+                     [1.0, 1e-3, 0.1], [-1e16, 7.0, 0.9], [0.5, 2.0 ** -30, 0.1], [3.0, 1e16, 0.3], [1.0, -1e16, 0.1]])
+    want = [0.0, 0.0, 0.0]
+    for g in range(N_EVAL):
+        for s in range(3):
+            want[s] += float(rows[g, s])
+    want = [t / 10 for t in want]
+    got = P.mean_eval_triple(rows)
+    assert got == want and all(type(x) is float for x in got)
+    back = [0.0, 0.0, 0.0]
+    for g in reversed(range(N_EVAL)):
+        for s in range(3):
+            back[s] += float(rows[g, s])
+    assert all(w != b / 10 for w, b in zip(want, back)), "the rows do not tell one summation order from another"
+    # only the N_EVAL rows count
+    assert P.mean_eval_triple(np.vstack([rows, [[9.0, 9.0, 9.0]]])) == want
+
+
+def test_the_engines_share_the_functions_instead_of_copies():
+    from coevonet_amd import dqn_population, es_half, evolutionary_strategy, ga_half, genetic_algorithm
+    for cls in (genetic_algorithm.GAEngine, ga_half.HalfGAEngine):
+        assert issubclass(cls, P.SlabIO) and issubclass(cls, P.CoGASchedule)
+        assert cls._ordinal_base is P.CoGASchedule._ordinal_base and cls.eval_only is P.CoGASchedule.eval_only
+        assert cls.load_initial is P.CoGASchedule.load_initial and cls.rewards_host is P.CoGASchedule.rewards_host
+        assert cls.upload is P.SlabIO.upload and cls._ptr is P.SlabIO._ptr
+    assert genetic_algorithm.GAEngine.rollout is P.CoGASchedule.rollout and not genetic_algorithm.GAEngine.one_reset
+    assert ga_half.HalfGAEngine.eval_rewards is P.CoGASchedule.eval_rewards and ga_half.HalfGAEngine.one_reset
+    assert ga_half.HalfGAEngine.download is P.SlabIO.download
+    for cls in (evolutionary_strategy.ESEngine, es_half.HalfESEngine):
+        assert issubclass(cls, P.SlabIO) and issubclass(cls, P.CoESSchedule)
+        assert cls.rollout is P.CoESSchedule.rollout and cls.evaluate is P.CoESSchedule.evaluate
+        assert cls._ordinal_base is P.CoESSchedule._ordinal_base and cls.rewards_host is P.CoESSchedule.rewards_host
+        assert cls.upload is P.SlabIO.upload and cls.download is P.SlabIO.download and cls._ptr is P.SlabIO._ptr
+    for cls in (dqn_population.DQNGAEngine, dqn_population.DQNESEngine):
+        assert issubclass(cls, P.SlabIO) and cls._ptr is P.SlabIO._ptr and cls.download is P.SlabIO.download
+    assert not hasattr(dqn_population, "_SlabMixin")
+    for mod in (genetic_algorithm, ga_half, evolutionary_strategy, es_half):
+        assert (mod.ROLES, mod.ROLE_D, mod.N_EVAL) == (P.ROLES, P.ROLE_D, P.N_EVAL)
+
+
+class ResetLog:
+    def __init__(self):
+        self.resets = []
+
+    def reset(self, *a):
+        self.resets.append(a)
+
+    def set_limits(self, limits):
+        self.limits = list(limits)
+
+    def run(self, n_cycles):
+        self.cycles = n_cycles
+
+
+class Plan:
+    n_games = 3 * 4 * 2 + N_EVAL
+
+
+@pytest.mark.parametrize("one_reset,lo,n_local", [(False, 0, 4), (True, 0, 4), (False, 2, 2)])
+def test_co_ga_rollout_resets_every_game_to_its_ordinal_in_the_seeded_stream(one_reset, lo, n_local):
+    """game (phase, i, k) of generation g takes ordinal first + g (3 pop hof + N_EVAL) + (phase pop + i) hof + k, whether the
+    phases are reset one by one or, the whole population being here, in one launch; the evaluation games of g - 1 ride along
+    under the ordinals behind that generation's main games"""
+    pop, hof = 4, 2
+    s = P.CoGASchedule()
+    s.one_reset = one_reset
+    s.pop, s.hof, s.lo, s.n_local, s.n_main, s.first_ordinal = pop, hof, lo, n_local, 3 * n_local * hof, 7
+    s.T_train, s.T_eval, s.n_cycles, s.env_mode, s.plan, s.ro = 30, 20, 10, "device", Plan(), ResetLog()
+    s.plan.n_games = s.n_main + N_EVAL
+    s.rollout(2, True)
+    assert len(s.ro.resets) == (2 if one_reset else 4)
+    ordinal = {}
+    for first, n, o in s.ro.resets:
+        for j in range(n):
+            assert first + j not in ordinal
+            ordinal[first + j] = o + j
+    per_gen = 3 * pop * hof + N_EVAL
+    for ph in range(3):
+        for i in range(n_local):
+            for k in range(hof):
+                assert ordinal[(ph * n_local + i) * hof + k] == 7 + 2 * per_gen + (ph * pop + lo + i) * hof + k
+    assert [ordinal[s.n_main + j] for j in range(N_EVAL)] == [7 + per_gen + 3 * pop * hof + j for j in range(N_EVAL)]
+    assert len(ordinal) == s.n_main + N_EVAL and s.ro.limits == [30] * s.n_main + [20] * N_EVAL and s.ro.cycles == 10
