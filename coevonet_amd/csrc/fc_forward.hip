@@ -16,7 +16,13 @@
 // does the same sequential-k fma chains (tools/mfma4_chain_probe.hip: bit-identical) in far fewer issue slots and LDS
 // reads.  (v_mfma_f32_16x16x4_f32, tools/mfma16_chain_probe.hip, is exact as well but spends 16 tile rows on <= 8.)
 // All fp32 math follows the canonical order in coevo_common.hip.h, so logits equal the oracle's bit for bit.
+//
+// Five forward bodies live here (fc_policy_body, fc_policy_body_c, fc_policy_mfma_body, fc_policy_mfma16_body, the persistent
+// fc_rollout_small_kernel).  What they run the same way AND the compiler turns into the same code either way is written once
+// (out_chain, first_max_action, store_action, fc2_mfma4_consume, the packed LayerNorm passes of the two lean forms, the
+// persistent kernel's game copy and tagged-word wait); the other phases are still spelled out per body - profiles/r12_fc_forward_helpers.md has the measurements behind that line.
 #include <cstdlib>
+#include <type_traits>
 
 #include "coevo_common.hip.h"
 
@@ -35,6 +41,7 @@ namespace coevo {
 // (350 vs 349 generations/s); with the current one: 539.5 vs 517 (three alternating runs each).  -DCOEVO_NO_NT builds
 // the plain-load variant for A/B runs.
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x4_acc __attribute__((ext_vector_type(4)));   // accumulator of v_mfma_f32_4x4x1 / v_mfma_f32_16x16x4
 __device__ inline float4 load_stream16(const float4 *p)
 {
 #ifdef COEVO_NO_NT
@@ -133,6 +140,164 @@ __device__ unsigned long long g_wave_stamps[4096 * 4 * 16];
 #define COEVO_WSTAMP(i) do { } while (0)
 #define COEVO_CSTAMP(i) do { } while (0)
 #endif
+
+// Output layer of one (row, action) lane: the 256-long sequential fmaf chain from the bias, W3 row and h2 row out of LDS.
+// UNROLL k-quads of both operands are requested at a time (the chain waits for LDS 64 / UNROLL times).
+template <int UNROLL>
+__device__ __forceinline__ float out_chain(float y, const float *w3row, const float *h2row)
+{
+    const float4 *wr = reinterpret_cast<const float4 *>(w3row);
+    const float4 *xr = reinterpret_cast<const float4 *>(h2row);
+#pragma unroll UNROLL
+    for (int k = 0; k < H2 / 4; ++k) {
+        const float4 wv = wr[k], xv = xr[k];
+        y = __builtin_fmaf(wv.x, xv.x, y);
+        y = __builtin_fmaf(wv.y, xv.y, y);
+        y = __builtin_fmaf(wv.z, xv.z, y);
+        y = __builtin_fmaf(wv.w, xv.w, y);
+    }
+    return y;
+}
+
+// U k-quads of the 4x4x1 fc2: lane's streamed piece buf[u] = W2[64 w + l][4 q .. 4 q + 3] is the B operand of four MFMAs per
+// row group, the A operands of a row group are one ds_read_b128 of the k-quad image
+template <int NG, int U>
+__device__ __forceinline__ void fc2_mfma4_consume(f32x4_acc (&acc)[NG], const float4 (&buf)[U],
+                                                  const float (*h1q)[4 * NG + 1][4], int kq, int l)
+{
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        float4 x[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) x[g] = *reinterpret_cast<const float4 *>(&h1q[kq + u][4 * g + (l & 3)][0]);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].x, buf[u].x, acc[g], 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].y, buf[u].y, acc[g], 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].z, buf[u].z, acc[g], 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].w, buf[u].w, acc[g], 0, 0, 0);
+    }
+}
+
+// determine_action: the FIRST maximum of a row's NACT logits (strict '>' scan from -inf).  A non-finite logit raises
+// COEVO_ST_BAD_OUT in `st`; no logit above -inf (all NaN / -inf) raises COEVO_ST_NO_ACTION and gives action 0.
+struct FirstMax { int best, st; };
+__device__ __forceinline__ FirstMax first_max_action(const float *lg, int st)
+{
+    int best = -1;
+    float cur = -__builtin_inff();
+#pragma unroll
+    for (int o = 0; o < NACT; ++o) {
+        const float v = lg[o];
+        if (!__builtin_isfinite(v)) st |= COEVO_ST_BAD_OUT;
+        if (v > cur) { cur = v; best = o; }
+    }
+    if (best < 0) { st |= COEVO_ST_NO_ACTION; best = 0; }
+    return {best, st};
+}
+
+// The action of row `row`: by (game, slot) in a fused cycle, by row otherwise; + the optional copy of its logits
+template <int MODE>
+__device__ __forceinline__ void store_action(const FcArgs &a, int row, int best, const float *lg)
+{
+    if constexpr (MODE >= MODE_FUSED) {
+        a.act_cur[3 * a.row_game[row] + a.row_slot[row]] = best;  // by (game, slot)
+    } else {
+        a.actions[row] = best;
+    }
+    if (a.logits) {
+#pragma unroll
+        for (int o = 0; o < NACT; ++o) a.logits[(size_t)row * COEVO_LOGIT_STRIDE + o] = lg[o];
+    }
+}
+
+// ---- the packed LayerNorm of the lean bodies: a wave's N = HB * R block sums (R rows x its HB canonical blocks, value
+// HB * r + h) come from ONE packed butterfly into red[wave][]; lane r < R then combines row r's 4 HB partials left to right
+// (blocks 0..3 = first halves, 4..7 = second halves) and the result is broadcast with v_readlane.  HB = 2: LayerNorm(512),
+// HB = 1: LayerNorm(256).  The barriers between the passes are the caller's.
+template <int N>
+__device__ __forceinline__ void ln_block_sums(const float (&v)[N], float (*red)[16], int w, int l)
+{
+    const float s = packed_totals<N>(v, l);
+    if (l < N) red[w][l] = s;
+}
+
+template <int HB>
+__device__ __forceinline__ float ln_row_total(const float (*red)[16], int lr)
+{
+    float tot = red[0][HB * lr];
+#pragma unroll
+    for (int b = 1; b < 4 * HB; ++b) tot = tot + red[b & 3][HB * lr + (b >> 2)];
+    return tot;
+}
+
+// second pass: subtract the row means (from the sums in red), post the block sums of the squared deviations to red2
+template <int R, int HB>
+__device__ __forceinline__ void ln_center(float (&v)[HB * R], const float (*red)[16], float (*red2)[16], int w, int l, int lr)
+{
+    const float meanv = ln_row_total<HB>(red, lr) * (1.0f / (HB * 256));
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const float m = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(meanv), r));
+#pragma unroll
+        for (int h = 0; h < HB; ++h) v[HB * r + h] = v[HB * r + h] - m;
+    }
+    float sq[HB * R];
+#pragma unroll
+    for (int j = 0; j < HB * R; ++j) sq[j] = v[j] * v[j];
+    ln_block_sums<HB * R>(sq, red2, w, l);
+}
+
+// third pass of LayerNorm(512): affine + ReLU of this thread's two features of every row, into the row-major image (DPP:
+// the vector-ALU fc2 reads h1r) or the k-quad image (the 4x4x1 fc2 reads h1q); returns st, COEVO_ST_BAD_FC1 added
+template <int R, bool DPP, class SM>
+__device__ __forceinline__ int ln512_relu_store(SM &sm, const float (&v)[2 * R], int lr, int nrows, float p_g1a, float p_g1b,
+                                                float p_be1a, float p_be1b, int st)
+{
+    const int t = threadIdx.x;
+    const float rstdv = 1.0f / __builtin_sqrtf(ln_row_total<2>(sm.red2, lr) * (1.0f / H1) + LN_EPS);
+    bool bad = false;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const float rstd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rstdv), r));
+        const float y0 = __builtin_fmaf(v[2 * r] * rstd, p_g1a, p_be1a);
+        const float y1 = __builtin_fmaf(v[2 * r + 1] * rstd, p_g1b, p_be1b);
+        if (r < nrows) bad = bad || bad_post_relu(y0) || bad_post_relu(y1);
+        if constexpr (DPP) {
+            sm.h1r[r][t] = relu_keep_nan(y0);
+            sm.h1r[r][t + 256] = relu_keep_nan(y1);
+        } else {
+            sm.h1q[t >> 2][r][t & 3] = relu_keep_nan(y0);
+            sm.h1q[(t + 256) >> 2][r][t & 3] = relu_keep_nan(y1);
+        }
+    }
+    if (bad) st |= COEVO_ST_BAD_FC1;
+    return st;
+}
+
+// third pass of LayerNorm(256): affine + ReLU of column t of every row into h2; returns st, COEVO_ST_BAD_FC2 added
+__device__ __forceinline__ float ln256_rstd(const float (*red2)[16], int lr)
+{
+    return 1.0f / __builtin_sqrtf(ln_row_total<1>(red2, lr) * (1.0f / H2) + LN_EPS);
+}
+template <int R>
+__device__ __forceinline__ int ln256_relu_store(const float (&u)[R], float rstdv, int nrows, float p_g2, float p_be2,
+                                                float (*h2)[260], int st)
+{
+    const int t = threadIdx.x;
+    bool bad = false;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const float rstd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rstdv), r));
+        const float y = __builtin_fmaf(u[r] * rstd, p_g2, p_be2);
+        if (r < nrows) bad = bad || bad_post_relu(y);
+        h2[r][t] = relu_keep_nan(y);
+    }
+    if (bad) st |= COEVO_ST_BAD_FC2;
+    return st;
+}
 
 // One workgroup carries P nets (tasks first .. first+P-1).  P = 1 is the plain kernel.  P = 2 is used by the merged
 // cycle launch when one net per workgroup would not fit the CUs in a single round: the entry chains (env step,
@@ -303,7 +468,6 @@ __device__ __forceinline__ void fc_policy_body(const FcArgs &a, FcSmem<R, P> &sm
     //      used as is as the B operand of four v_mfma_f32_4x4x1_16B_f32 per row group ------------------------------
     // (Measured: a single left-over row - R = 5 - as VALU FMAs instead of a second 4-row MFMA group halves these
     // workgroups' matrix-pipe use but its serial fma chain and extra broadcast read cost more: 449 vs 516.)
-    typedef float f32x4_acc __attribute__((ext_vector_type(4)));
     constexpr int NG = FcSmem<R, P>::NG;
     f32x4_acc acc[P][NG];  // acc[p][g][i]: row 4g + i of net p, column 64w + l
 #pragma unroll
@@ -334,22 +498,7 @@ __device__ __forceinline__ void fc_policy_body(const FcArgs &a, FcSmem<R, P> &sm
 #pragma unroll
             for (int u = 0; u < U; ++u) buf[u] = load_stream16(wp + (size_t)(kq + u) * 64);
         };
-        auto consume = [&](const float4 (&buf)[U], int kq) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                float4 x[NG];
-#pragma unroll
-                for (int g = 0; g < NG; ++g) x[g] = *reinterpret_cast<const float4 *>(&sm.h1q[kq + u][4 * g + (l & 3)][0]);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[p][g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].x, buf[u].x, acc[p][g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[p][g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].y, buf[u].y, acc[p][g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[p][g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].z, buf[u].z, acc[p][g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[p][g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].w, buf[u].w, acc[p][g], 0, 0, 0);
-            }
-        };
+        auto consume = [&](const float4 (&buf)[U], int kq) { fc2_mfma4_consume<NG, U>(acc[p], buf, sm.h1q, kq, l); };
         issue(bufA, 0);
         int kq = 0;
         for (; kq < 128 - 2 * U; kq += 2 * U) {
@@ -411,17 +560,7 @@ __device__ __forceinline__ void fc_policy_body(const FcArgs &a, FcSmem<R, P> &sm
     // ---- output layer: one lane per (row, action), 256-long sequential chain out of LDS --------------------
     if (row_wave && l < R * NACT) {
         const int r = l / NACT, o = l % NACT;
-        float y = p_b3;
-        const float4 *wr = reinterpret_cast<const float4 *>(&sm.w3s[pw][o][0]);
-        const float4 *xr = reinterpret_cast<const float4 *>(&sm.h2[pw][r][0]);
-#pragma unroll 8
-        for (int k = 0; k < H2 / 4; ++k) {
-            const float4 wv = wr[k], xv = xr[k];
-            y = __builtin_fmaf(wv.x, xv.x, y);
-            y = __builtin_fmaf(wv.y, xv.y, y);
-            y = __builtin_fmaf(wv.z, xv.z, y);
-            y = __builtin_fmaf(wv.w, xv.w, y);
-        }
+        const float y = out_chain<8>(p_b3, &sm.w3s[pw][o][0], &sm.h2[pw][r][0]);
         sm.logit[pw][r][o] = y;
     }
     __syncthreads();
@@ -429,25 +568,10 @@ __device__ __forceinline__ void fc_policy_body(const FcArgs &a, FcSmem<R, P> &sm
 
     // ---- first-max action (strict '>' scan from -inf), status --------------------------------------------
     if (row_wave && l < nrows[pw]) {
-        int best = -1;
-        float cur = -__builtin_inff();
-#pragma unroll
-        for (int o = 0; o < NACT; ++o) {
-            const float v = sm.logit[pw][l][o];
-            if (!__builtin_isfinite(v)) st |= COEVO_ST_BAD_OUT;
-            if (v > cur) { cur = v; best = o; }
-        }
-        if (best < 0) { st |= COEVO_ST_NO_ACTION; best = 0; }
-        const int row = row0[pw] + l;
-        if constexpr (MODE >= MODE_FUSED) {
-            a.act_cur[3 * a.row_game[row] + a.row_slot[row]] = best;  // by (game, slot)
-        } else {
-            a.actions[row] = best;
-        }
-        if (a.logits) {
-#pragma unroll
-            for (int o = 0; o < NACT; ++o) a.logits[(size_t)row * COEVO_LOGIT_STRIDE + o] = sm.logit[pw][l][o];
-        }
+        const FirstMax fm = first_max_action(sm.logit[pw][l], st);
+        const int best = fm.best;
+        st = fm.st;
+        store_action<MODE>(a, row0[pw] + l, best, sm.logit[pw][l]);
     }
     if (st) atomicOr(a.status, st);
     COEVO_STAMP(6);
@@ -533,7 +657,6 @@ __device__ __forceinline__ void fc_policy_body_c(const FcArgs &a, FcSmemC<R> &sm
 {
     static_assert(!RES || FC2 == FC2_MFMA, "the vector-ALU form streams with plain loads already");
     static_assert((MODE == MODE_FUSED || MODE == MODE_OBS) && R * NACT <= 64 && R <= 8, "the lean merged cycle kernel");
-    typedef float f32x4_acc __attribute__((ext_vector_type(4)));
     constexpr int NG = FcSmemC<R>::NG;
     COEVO_STAMP(0);
     const int t = threadIdx.x, w = t >> 6, l = t & 63;
@@ -640,60 +763,18 @@ __device__ __forceinline__ void fc_policy_body_c(const FcArgs &a, FcSmemC<R> &sm
     float v[2 * R];
 #pragma unroll
     for (int r = 0; r < R; ++r) { v[2 * r] = c0[r >> 2][r & 3]; v[2 * r + 1] = c1[r >> 2][r & 3]; }
-    {
-        const float s = packed_totals<2 * R>(v, l);
-        if (l < 2 * R) sm.red[w][l] = s;          // red[wave][2 r + half]: block (4 half + wave) of row r
-    }
+    ln_block_sums<2 * R>(v, sm.red, w, l);          // red[wave][2 r + half]: block (4 half + wave) of row r
     COEVO_STAMP(9);
     COEVO_WSTAMP(2);
     __syncthreads();
     COEVO_WSTAMP(3);
     COEVO_STAMP(10);
     const int lr = l < R ? l : R - 1;             // lane r < R works on row r (the other lanes repeat the last row)
-    {
-        float tot = sm.red[0][2 * lr];            // blocks left to right: 0..3 = first halves, 4..7 = second halves
-#pragma unroll
-        for (int b = 1; b < 8; ++b) tot = tot + sm.red[b & 3][2 * lr + (b >> 2)];
-        const float meanv = tot * (1.0f / H1);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float m = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(meanv), r));
-            v[2 * r] = v[2 * r] - m;
-            v[2 * r + 1] = v[2 * r + 1] - m;
-        }
-    }
-    {
-        float sq[2 * R];
-#pragma unroll
-        for (int j = 0; j < 2 * R; ++j) sq[j] = v[j] * v[j];
-        const float s = packed_totals<2 * R>(sq, l);
-        if (l < 2 * R) sm.red2[w][l] = s;
-    }
+    ln_center<R, 2>(v, sm.red, sm.red2, w, l, lr);
     COEVO_WSTAMP(4);
     __syncthreads();   // every wave is also done with `par` (its fc1 weights and LayerNorm parameters are in registers)
     COEVO_WSTAMP(5);
-    {
-        float tot = sm.red2[0][2 * lr];
-#pragma unroll
-        for (int b = 1; b < 8; ++b) tot = tot + sm.red2[b & 3][2 * lr + (b >> 2)];
-        const float rstdv = 1.0f / __builtin_sqrtf(tot * (1.0f / H1) + LN_EPS);
-        bool bad = false;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float rstd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rstdv), r));
-            const float y0 = __builtin_fmaf(v[2 * r] * rstd, p_g1a, p_be1a);
-            const float y1 = __builtin_fmaf(v[2 * r + 1] * rstd, p_g1b, p_be1b);
-            if (r < nrows) bad = bad || bad_post_relu(y0) || bad_post_relu(y1);
-            if constexpr (FC2 == FC2_DPP) {
-                sm.h1r[r][t] = relu_keep_nan(y0);
-                sm.h1r[r][t + 256] = relu_keep_nan(y1);
-            } else {
-                sm.h1q[t >> 2][r][t & 3] = relu_keep_nan(y0);
-                sm.h1q[(t + 256) >> 2][r][t & 3] = relu_keep_nan(y1);
-            }
-        }
-        if (bad) st |= COEVO_ST_BAD_FC1;
-    }
+    st = ln512_relu_store<R, FC2 == FC2_DPP>(sm, v, lr, nrows, p_g1a, p_g1b, p_be1a, p_be1b, st);
     COEVO_WSTAMP(6);
     __syncthreads();
     COEVO_WSTAMP(7);
@@ -717,22 +798,7 @@ __device__ __forceinline__ void fc_policy_body_c(const FcArgs &a, FcSmemC<R> &sm
 #pragma unroll
             for (int u = 0; u < U; ++u) buf[u] = RES ? wp[(size_t)(kq + u) * 64] : load_stream16(wp + (size_t)(kq + u) * 64);
         };
-        auto consume = [&](const float4 (&buf)[U], int kq) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                float4 x[NG];
-#pragma unroll
-                for (int g = 0; g < NG; ++g) x[g] = *reinterpret_cast<const float4 *>(&sm.h1q[kq + u][4 * g + (l & 3)][0]);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].x, buf[u].x, acc[g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].y, buf[u].y, acc[g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].z, buf[u].z, acc[g], 0, 0, 0);
-#pragma unroll
-                for (int g = 0; g < NG; ++g) acc[g] = __builtin_amdgcn_mfma_f32_4x4x1f32(x[g].w, buf[u].w, acc[g], 0, 0, 0);
-            }
-        };
+        auto consume = [&](const float4 (&buf)[U], int kq) { fc2_mfma4_consume<NG, U>(acc, buf, sm.h1q, kq, l); };
         issue(bufA, 0);
 #pragma nounroll
         for (int kq = 0; kq < 128; kq += 2 * U) {
@@ -779,10 +845,7 @@ __device__ __forceinline__ void fc_policy_body_c(const FcArgs &a, FcSmemC<R> &sm
     COEVO_WSTAMP(8);
     COEVO_CSTAMP(12);
     // ---- LayerNorm(256) + ReLU: canonical block b = wave b; R block sums per wave by one packed butterfly ---------------
-    {
-        const float s = packed_totals<R>(u, l);
-        if (l < R) sm.red[w][l] = s;   // (red / red2 live outside the union: no wave still needs the old contents)
-    }
+    ln_block_sums<R>(u, sm.red, w, l);   // (red / red2 live outside the union: no wave still needs the old contents)
     __syncthreads();  // also: every wave is done reading h1q, the tail image may overwrite it below
     {
         const float tot = ((sm.red[0][lr] + sm.red[1][lr]) + sm.red[2][lr]) + sm.red[3][lr];
@@ -798,19 +861,7 @@ __device__ __forceinline__ void fc_policy_body_c(const FcArgs &a, FcSmemC<R> &sm
 #pragma unroll
     for (int j = 0; j < 5; ++j) sm.tail.w3s[(t + 256 * j) >> 8][(t + 256 * j) & 255] = w3r[j];
     __syncthreads();
-    {
-        const float tot = ((sm.red2[0][lr] + sm.red2[1][lr]) + sm.red2[2][lr]) + sm.red2[3][lr];
-        const float rstdv = 1.0f / __builtin_sqrtf(tot * (1.0f / H2) + LN_EPS);
-        bool bad = false;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float rstd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rstdv), r));
-            const float y = __builtin_fmaf(u[r] * rstd, p_g2, p_be2);
-            if (r < nrows) bad = bad || bad_post_relu(y);
-            sm.tail.h2[r][t] = relu_keep_nan(y);
-        }
-        if (bad) st |= COEVO_ST_BAD_FC2;
-    }
+    st = ln256_relu_store<R>(u, ln256_rstd(sm.red2, lr), nrows, p_g2, p_be2, sm.tail.h2, st);
     __syncthreads();
     COEVO_STAMP(4);
 
@@ -818,20 +869,10 @@ __device__ __forceinline__ void fc_policy_body_c(const FcArgs &a, FcSmemC<R> &sm
     if (w == 0) {
         if (l < R * NACT) {
             const int r = l / NACT, o = l % NACT;
-            float y = p_b3;
-            const float4 *wr = reinterpret_cast<const float4 *>(&sm.tail.w3s[o][0]);
-            const float4 *xr = reinterpret_cast<const float4 *>(&sm.tail.h2[r][0]);
             // (the small-launch form has registers to spare: 16 k-quads of both operands requested at a time, so that the
             // 256-step chain waits for LDS four times instead of sixteen)
             constexpr int OUT_UNROLL = FC2 == FC2_DPP ? 16 : 4;
-#pragma unroll OUT_UNROLL
-            for (int k = 0; k < H2 / 4; ++k) {
-                const float4 wv = wr[k], xv = xr[k];
-                y = __builtin_fmaf(wv.x, xv.x, y);
-                y = __builtin_fmaf(wv.y, xv.y, y);
-                y = __builtin_fmaf(wv.z, xv.z, y);
-                y = __builtin_fmaf(wv.w, xv.w, y);
-            }
+            const float y = out_chain<OUT_UNROLL>(p_b3, &sm.tail.w3s[o][0], &sm.tail.h2[r][0]);
             sm.logit[r][o] = y;
         }
         COEVO_STAMP(5);
@@ -840,22 +881,10 @@ __device__ __forceinline__ void fc_policy_body_c(const FcArgs &a, FcSmemC<R> &sm
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         if (l < nrows) {   // strict '>' scan from -inf
-            int best = -1;
-            float cur = -__builtin_inff();
-#pragma unroll
-            for (int o = 0; o < NACT; ++o) {
-                const float vv = sm.logit[l][o];
-                if (!__builtin_isfinite(vv)) st |= COEVO_ST_BAD_OUT;
-                if (vv > cur) { cur = vv; best = o; }
-            }
-            if (best < 0) { st |= COEVO_ST_NO_ACTION; best = 0; }
-            const int row = row0 + l;
-            if constexpr (MODE == MODE_FUSED) a.act_cur[3 * a.row_game[row] + a.row_slot[row]] = best;  // by (game, slot)
-            else a.actions[row] = best;
-            if (a.logits) {
-#pragma unroll
-                for (int o = 0; o < NACT; ++o) a.logits[(size_t)row * COEVO_LOGIT_STRIDE + o] = sm.logit[l][o];
-            }
+            const FirstMax fm = first_max_action(sm.logit[l], st);
+            const int best = fm.best;
+            st = fm.st;
+            store_action<MODE>(a, row0 + l, best, sm.logit[l]);
         }
     }
     if (st) atomicOr(a.status, st);
@@ -1145,41 +1174,16 @@ __device__ __forceinline__ void fc_policy_mfma_body(const FcArgs &a, FcMfmaSmem 
     // ---- output layer (N = 5: not worth a tile), argmax, status - as in the VALU kernel ----------------------
     if (t < 32 * NACT) {
         const int r = t / NACT, o = t % NACT;
-        float y = p_b3;
-        const float4 *wr = reinterpret_cast<const float4 *>(&sm.w3s[o][0]);
-        const float4 *xr = reinterpret_cast<const float4 *>(&sm.h2[r][0]);
-#pragma unroll 8
-        for (int k = 0; k < H2 / 4; ++k) {
-            const float4 wv = wr[k], xv = xr[k];
-            y = __builtin_fmaf(wv.x, xv.x, y);
-            y = __builtin_fmaf(wv.y, xv.y, y);
-            y = __builtin_fmaf(wv.z, xv.z, y);
-            y = __builtin_fmaf(wv.w, xv.w, y);
-        }
+        const float y = out_chain<8>(p_b3, &sm.w3s[o][0], &sm.h2[r][0]);
         sm.logit[r][o] = y;
     }
     __syncthreads();
     COEVO_STAMP(5);
     if (t < nrows) {
-        int best = -1;
-        float cur = -__builtin_inff();
-#pragma unroll
-        for (int o = 0; o < NACT; ++o) {
-            const float v = sm.logit[t][o];
-            if (!__builtin_isfinite(v)) st |= COEVO_ST_BAD_OUT;
-            if (v > cur) { cur = v; best = o; }
-        }
-        if (best < 0) { st |= COEVO_ST_NO_ACTION; best = 0; }
-        if constexpr (MODE >= MODE_FUSED) {
-            const int row = row0 + t;
-            a.act_cur[3 * a.row_game[row] + a.row_slot[row]] = best;  // by (game, slot)
-        } else {
-            a.actions[row0 + t] = best;
-        }
-        if (a.logits) {
-#pragma unroll
-            for (int o = 0; o < NACT; ++o) a.logits[(size_t)(row0 + t) * COEVO_LOGIT_STRIDE + o] = sm.logit[t][o];
-        }
+        const FirstMax fm = first_max_action(sm.logit[t], st);
+        const int best = fm.best;
+        st = fm.st;
+        store_action<MODE>(a, row0 + t, best, sm.logit[t]);
     }
     if (st) atomicOr(a.status, st);
     COEVO_STAMP(6);
@@ -1216,7 +1220,6 @@ static_assert(sizeof(FcMfma16Smem) <= 40960, "four workgroups per CU");
 template <int MODE>
 __device__ __forceinline__ void fc_policy_mfma16_body(const FcArgs &a, FcMfma16Smem &sm, const coevo_fc_task &task)
 {
-    typedef float f32x4_acc __attribute__((ext_vector_type(4)));
     typedef unsigned u32x2_s __attribute__((ext_vector_type(2)));
     COEVO_STAMP(0);
     const int t = threadIdx.x, w = t >> 6, l = t & 63, lc = l & 15, lg = l >> 4;
@@ -1470,41 +1473,16 @@ __device__ __forceinline__ void fc_policy_mfma16_body(const FcArgs &a, FcMfma16S
     // ---- output layer, argmax, status - as in the other bodies ------------------------------------------------
     if (t < 16 * NACT) {
         const int r = t / NACT, o = t % NACT;
-        float y = p_b3;
-        const float4 *wr = reinterpret_cast<const float4 *>(&sm.w3s[o][0]);
-        const float4 *xr = reinterpret_cast<const float4 *>(&sm.h2[r][0]);
-#pragma unroll 8
-        for (int k = 0; k < H2 / 4; ++k) {
-            const float4 wv = wr[k], xv = xr[k];
-            y = __builtin_fmaf(wv.x, xv.x, y);
-            y = __builtin_fmaf(wv.y, xv.y, y);
-            y = __builtin_fmaf(wv.z, xv.z, y);
-            y = __builtin_fmaf(wv.w, xv.w, y);
-        }
+        const float y = out_chain<8>(p_b3, &sm.w3s[o][0], &sm.h2[r][0]);
         sm.logit[r][o] = y;
     }
     __syncthreads();
     COEVO_STAMP(5);
     if (t < nrows) {
-        int best = -1;
-        float cur = -__builtin_inff();
-#pragma unroll
-        for (int o = 0; o < NACT; ++o) {
-            const float v = sm.logit[t][o];
-            if (!__builtin_isfinite(v)) st |= COEVO_ST_BAD_OUT;
-            if (v > cur) { cur = v; best = o; }
-        }
-        if (best < 0) { st |= COEVO_ST_NO_ACTION; best = 0; }
-        if constexpr (MODE >= MODE_FUSED) {
-            const int row = row0 + t;
-            a.act_cur[3 * a.row_game[row] + a.row_slot[row]] = best;  // by (game, slot)
-        } else {
-            a.actions[row0 + t] = best;
-        }
-        if (a.logits) {
-#pragma unroll
-            for (int o = 0; o < NACT; ++o) a.logits[(size_t)(row0 + t) * COEVO_LOGIT_STRIDE + o] = sm.logit[t][o];
-        }
+        const FirstMax fm = first_max_action(sm.logit[t], st);
+        const int best = fm.best;
+        st = fm.st;
+        store_action<MODE>(a, row0 + t, best, sm.logit[t]);
     }
     if (st) atomicOr(a.status, st);
     COEVO_STAMP(6);
@@ -1610,6 +1588,40 @@ __global__ void sync_clear_kernel(int32_t *w, int n)
     if (i < n) w[i] = 0;
 }
 
+// a row's game out of its LDS record gs[0..17], and the fields a world step moves (positions, velocities) back
+__device__ __forceinline__ void game_from_lds(const double *gs, MpeGame &s)
+{
+    s.ax = gs[0]; s.ay = gs[1]; s.bx = gs[2]; s.by = gs[3]; s.cx = gs[4]; s.cy = gs[5];
+    s.avx = gs[6]; s.avy = gs[7]; s.bvx = gs[8]; s.bvy = gs[9]; s.cvx = gs[10]; s.cvy = gs[11];
+    s.l0x = gs[12]; s.l0y = gs[13]; s.l1x = gs[14]; s.l1y = gs[15]; s.gx = gs[16]; s.gy = gs[17];
+}
+__device__ __forceinline__ void game_moved_to_lds(double *gs, const MpeGame &s)
+{
+    gs[0] = s.ax; gs[1] = s.ay; gs[2] = s.bx; gs[3] = s.by; gs[4] = s.cx; gs[5] = s.cy;
+    gs[6] = s.avx; gs[7] = s.avy; gs[8] = s.bvx; gs[9] = s.bvy; gs[10] = s.cvx; gs[11] = s.cvy;
+}
+
+// Bounded wait until the three tagged action words of a game (tp[0..2]) all carry `tag`; gives up early when somebody raised
+// the abort word.  False: timed out, or somebody else did - the caller raises COEVO_ST_SYNC_TIMEOUT and the abort word.
+struct TaggedWords { bool ok; int w0, w1, w2; };
+__device__ __forceinline__ TaggedWords wait_tagged_actions(const int32_t *tp, const int32_t *abort_word, int tag)
+{
+    int w0 = 0, w1 = 0, w2 = 0;
+    bool ok = false;
+    for (int it = 0; it < COEVO_SYNC_SPINS; ++it) {
+        w0 = __hip_atomic_load(tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w1 = __hip_atomic_load(tp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w2 = __hip_atomic_load(tp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ok = (w0 >> 8) == tag && (w1 >> 8) == tag && (w2 >> 8) == tag;
+        if (ok) break;
+        // (the abort word is ONE word for everybody - agent-scope loads are served by memory, and a thousand
+        // lanes on one line queue up: looked at every 16th poll only)
+        if ((it & 15) == 15 && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+        __builtin_amdgcn_s_sleep(1);
+    }
+    return {ok, w0, w1, w2};
+}
+
 template <int R>
 __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, PersistArgs pa)
 {
@@ -1617,7 +1629,6 @@ __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, Pers
     static_assert(sizeof(FcSmemP<R>) <= 80 * 1024, "two workgroups per CU");
     constexpr int NG = FcSmemP<R>::NG;
     constexpr int US = COEVO_SMALL_U;
-    typedef float f32x4_acc __attribute__((ext_vector_type(4)));
     const int t = threadIdx.x, w = t >> 6, l = t & 63;
     const bool heavy = (int)blockIdx.x < a.n_heavy;   // workgroup-uniform
     const coevo_fc_task task = heavy ? a.tasks[blockIdx.x] : a.light_tasks[(int)blockIdx.x - a.n_heavy];
@@ -1682,26 +1693,12 @@ __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, Pers
             if (l < nrows) {
                 const int g = sm.rowinfo[l][0], slot = sm.rowinfo[l][1], limit = sm.rowinfo[l][2];
                 MpeGame s;
-                s.ax = sm.gs[l][0]; s.ay = sm.gs[l][1]; s.bx = sm.gs[l][2]; s.by = sm.gs[l][3]; s.cx = sm.gs[l][4]; s.cy = sm.gs[l][5];
-                s.avx = sm.gs[l][6]; s.avy = sm.gs[l][7]; s.bvx = sm.gs[l][8]; s.bvy = sm.gs[l][9]; s.cvx = sm.gs[l][10];
-                s.cvy = sm.gs[l][11]; s.l0x = sm.gs[l][12]; s.l0y = sm.gs[l][13]; s.l1x = sm.gs[l][14]; s.l1y = sm.gs[l][15];
-                s.gx = sm.gs[l][16]; s.gy = sm.gs[l][17];
+                game_from_lds(sm.gs[l], s);
                 if (c > 0) {
                     const int32_t *tp = tags + (size_t)((c - 1) & 1) * 3 * N + 3 * (size_t)(g + zero);
-                    int w0 = 0, w1 = 0, w2 = 0;
-                    bool ok = false;
-                    for (int it = 0; it < COEVO_SYNC_SPINS; ++it) {
-                        w0 = __hip_atomic_load(tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        w1 = __hip_atomic_load(tp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        w2 = __hip_atomic_load(tp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok = (w0 >> 8) == c && (w1 >> 8) == c && (w2 >> 8) == c;
-                        if (ok) break;
-                        // (the abort word is ONE word for everybody - agent-scope loads are served by memory, and a thousand
-                        // lanes on one line queue up: looked at every 16th poll only)
-                        if ((it & 15) == 15 && __hip_atomic_load(pa.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    if (!ok) {   // timed out, or somebody else did: everybody leaves
+                    const TaggedWords tw = wait_tagged_actions(tp, pa.sync, c);
+                    const int w0 = tw.w0, w1 = tw.w1, w2 = tw.w2;
+                    if (!tw.ok) {   // timed out, or somebody else did: everybody leaves
                         st |= COEVO_ST_SYNC_TIMEOUT;
                         __hip_atomic_store(pa.sync, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         sm.ctl[0] = 1;
@@ -1722,9 +1719,7 @@ __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, Pers
                             if (stepped) { a_a1 = a_a1 + r_adv; rg_prev = r_good; }
                             sm.gs[l][18] = rg_prev; sm.gs[l][19] = a_adv; sm.gs[l][20] = a_a0; sm.gs[l][21] = a_a1;
                         }
-                        sm.gs[l][0] = s.ax; sm.gs[l][1] = s.ay; sm.gs[l][2] = s.bx; sm.gs[l][3] = s.by; sm.gs[l][4] = s.cx;
-                        sm.gs[l][5] = s.cy; sm.gs[l][6] = s.avx; sm.gs[l][7] = s.avy; sm.gs[l][8] = s.bvx; sm.gs[l][9] = s.bvy;
-                        sm.gs[l][10] = s.cvx; sm.gs[l][11] = s.cvy;
+                        game_moved_to_lds(sm.gs[l], s);
                     }
                 }
                 mpe_obs_from_game(s, slot, o);
@@ -1776,49 +1771,12 @@ __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, Pers
         float v[2 * R];
 #pragma unroll
         for (int r = 0; r < R; ++r) { v[2 * r] = c0[r >> 2][r & 3]; v[2 * r + 1] = c1[r >> 2][r & 3]; }
-        {
-            const float s = packed_totals<2 * R>(v, l);
-            if (l < 2 * R) sm.red[w][l] = s;
-        }
+        ln_block_sums<2 * R>(v, sm.red, w, l);
         __syncthreads();
         const int lr = l < R ? l : R - 1;
-        {
-            float tot = sm.red[0][2 * lr];
-#pragma unroll
-            for (int b = 1; b < 8; ++b) tot = tot + sm.red[b & 3][2 * lr + (b >> 2)];
-            const float meanv = tot * (1.0f / H1);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float m = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(meanv), r));
-                v[2 * r] = v[2 * r] - m;
-                v[2 * r + 1] = v[2 * r + 1] - m;
-            }
-        }
-        {
-            float sq[2 * R];
-#pragma unroll
-            for (int j = 0; j < 2 * R; ++j) sq[j] = v[j] * v[j];
-            const float s = packed_totals<2 * R>(sq, l);
-            if (l < 2 * R) sm.red2[w][l] = s;
-        }
+        ln_center<R, 2>(v, sm.red, sm.red2, w, l, lr);
         __syncthreads();
-        {
-            float tot = sm.red2[0][2 * lr];
-#pragma unroll
-            for (int b = 1; b < 8; ++b) tot = tot + sm.red2[b & 3][2 * lr + (b >> 2)];
-            const float rstdv = 1.0f / __builtin_sqrtf(tot * (1.0f / H1) + LN_EPS);
-            bool bad = false;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float rstd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rstdv), r));
-                const float y0 = __builtin_fmaf(v[2 * r] * rstd, p_g1a, p_be1a);
-                const float y1 = __builtin_fmaf(v[2 * r + 1] * rstd, p_g1b, p_be1b);
-                if (r < nrows) bad = bad || bad_post_relu(y0) || bad_post_relu(y1);
-                sm.h1r[r][t] = relu_keep_nan(y0);
-                sm.h1r[r][t + 256] = relu_keep_nan(y1);
-            }
-            if (bad) st |= COEVO_ST_BAD_FC1;
-        }
+        st = ln512_relu_store<R, true>(sm, v, lr, nrows, p_g1a, p_g1b, p_be1a, p_be1b, st);
         asm volatile("" : "+v"(st));
         __syncthreads();
 
@@ -1855,10 +1813,7 @@ __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, Pers
             }
         }
         // ---- LayerNorm(256) + ReLU ------------------------------------------------------------------------------------------
-        {
-            const float s = packed_totals<R>(u, l);
-            if (l < R) sm.red[w][l] = s;
-        }
+        ln_block_sums<R>(u, sm.red, w, l);
         __syncthreads();
         {
             const float tot = ((sm.red[0][lr] + sm.red[1][lr]) + sm.red[2][lr]) + sm.red[3][lr];
@@ -1873,18 +1828,9 @@ __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, Pers
         }
         __syncthreads();
         {
-            const float tot = ((sm.red2[0][lr] + sm.red2[1][lr]) + sm.red2[2][lr]) + sm.red2[3][lr];
-            const float rstdv = 1.0f / __builtin_sqrtf(tot * (1.0f / H2) + LN_EPS);
+            const float rstdv = ln256_rstd(sm.red2, lr);
             const float p_g2 = sm.p2[1][t], p_be2 = sm.p2[2][t];
-            bool bad = false;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float rstd = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rstdv), r));
-                const float y = __builtin_fmaf(u[r] * rstd, p_g2, p_be2);
-                if (r < nrows) bad = bad || bad_post_relu(y);
-                sm.h2[r][t] = relu_keep_nan(y);
-            }
-            if (bad) st |= COEVO_ST_BAD_FC2;
+            st = ln256_relu_store<R>(u, rstdv, nrows, p_g2, p_be2, sm.h2, st);
         }
         asm volatile("" : "+v"(st));
         __syncthreads();
@@ -1893,32 +1839,16 @@ __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, Pers
         if (w == 0) {
             if (l < R * NACT) {
                 const int r = l / NACT, o = l % NACT;
-                float y = sm.pb3[o];
-                const float4 *wr = reinterpret_cast<const float4 *>(&sm.w3s[o][0]);
-                const float4 *xr = reinterpret_cast<const float4 *>(&sm.h2[r][0]);
-#pragma unroll 8
-                for (int k = 0; k < H2 / 4; ++k) {
-                    const float4 wv = wr[k], xv = xr[k];
-                    y = __builtin_fmaf(wv.x, xv.x, y);
-                    y = __builtin_fmaf(wv.y, xv.y, y);
-                    y = __builtin_fmaf(wv.z, xv.z, y);
-                    y = __builtin_fmaf(wv.w, xv.w, y);
-                }
+                const float y = out_chain<8>(sm.pb3[o], &sm.w3s[o][0], &sm.h2[r][0]);
                 sm.logit[r][o] = y;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             if (l < nrows) {   // strict '>' scan from -inf
-                int best = -1;
-                float cur = -__builtin_inff();
-#pragma unroll
-                for (int o = 0; o < NACT; ++o) {
-                    const float vv = sm.logit[l][o];
-                    if (!__builtin_isfinite(vv)) st |= COEVO_ST_BAD_OUT;
-                    if (vv > cur) { cur = vv; best = o; }
-                }
-                if (best < 0) { st |= COEVO_ST_NO_ACTION; best = 0; }
+                const FirstMax fm = first_max_action(sm.logit[l], st);
+                const int best = fm.best;
+                st = fm.st;
                 const int g = sm.rowinfo[l][0], slot = sm.rowinfo[l][1];
                 __hip_atomic_store(tags + (size_t)(c & 1) * 3 * N + 3 * (size_t)(g + zero) + slot, ((c + 1) << 8) | best, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
@@ -1948,18 +1878,9 @@ __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, Pers
     if (pa.rewards && w == 0 && l < nrows && sm.rowinfo[l][1] == COEVO_SLOT_ADVERSARY && !sm.ctl[0]) {
         const int g = sm.rowinfo[l][0], limit = sm.rowinfo[l][2], cyc = pa.n_cycles - 1;
         const int32_t *tp = tags + (size_t)(cyc & 1) * 3 * N + 3 * (size_t)g;
-        int w0 = 0, w1 = 0, w2 = 0;
-        bool ok = false;
-        for (int it = 0; it < COEVO_SYNC_SPINS; ++it) {
-            w0 = __hip_atomic_load(tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            w1 = __hip_atomic_load(tp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            w2 = __hip_atomic_load(tp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = (w0 >> 8) == cyc + 1 && (w1 >> 8) == cyc + 1 && (w2 >> 8) == cyc + 1;
-            if (ok) break;
-            if ((it & 15) == 15 && __hip_atomic_load(pa.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (!ok) {
+        const TaggedWords tw = wait_tagged_actions(tp, pa.sync, cyc + 1);
+        const int w0 = tw.w0, w1 = tw.w1, w2 = tw.w2;
+        if (!tw.ok) {
             st |= COEVO_ST_SYNC_TIMEOUT;
             __hip_atomic_store(pa.sync, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
@@ -1970,10 +1891,7 @@ __global__ __launch_bounds__(256, 2) void fc_rollout_small_kernel(FcArgs a, Pers
             if (t0 + 1 < limit) a_a0 = a_a0 + rg_prev;
             if (t0 + 2 < limit) {
                 MpeGame s;
-                s.ax = sm.gs[l][0]; s.ay = sm.gs[l][1]; s.bx = sm.gs[l][2]; s.by = sm.gs[l][3]; s.cx = sm.gs[l][4]; s.cy = sm.gs[l][5];
-                s.avx = sm.gs[l][6]; s.avy = sm.gs[l][7]; s.bvx = sm.gs[l][8]; s.bvy = sm.gs[l][9]; s.cvx = sm.gs[l][10];
-                s.cvy = sm.gs[l][11]; s.l0x = sm.gs[l][12]; s.l0y = sm.gs[l][13]; s.l1x = sm.gs[l][14]; s.l1y = sm.gs[l][15];
-                s.gx = sm.gs[l][16]; s.gy = sm.gs[l][17];
+                game_from_lds(sm.gs[l], s);
                 double r_good, r_adv;
                 mpe_world_step(s, w0 & 0xff, w1 & 0xff, w2 & 0xff, a.pos_first, r_good, r_adv);
                 a_a1 = a_a1 + r_adv;
@@ -2015,18 +1933,40 @@ __global__ __launch_bounds__(256, 2) void fc_cycle_kernel(FcArgs a)
     stamp_end(a.stamps);
 }
 
+// The row-count instantiations of the per-individual kernels: f(R) is called with R = 1, 2, 5 or 8 as a compile-time
+// constant (std::integral_constant), the smallest that holds `rows`
+template <class F>
+static void dispatch_rows(int rows, F &&f)
+{
+    if (rows <= 1) f(std::integral_constant<int, 1>{});
+    else if (rows <= 2) f(std::integral_constant<int, 2>{});
+    else if (rows <= 5) f(std::integral_constant<int, 5>{});
+    else f(std::integral_constant<int, 8>{});
+}
+
+// compute units of the device that is current at the first call, asked once (every device of a process is assumed to be
+// the same part); 0: the query failed
+static int device_cu_count()
+{
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            return 0;
+        cus = n;
+    }
+    return cus;
+}
+
 template <int MODE>
 static int launch_fc(const FcArgs &a, int n_tasks, int max_rows, hipStream_t s)
 {
     if (n_tasks <= 0) return COEVO_OK;
-    if (max_rows <= 1)
-        hipLaunchKernelGGL((fc_policy_kernel<1, MODE>), dim3(n_tasks), dim3(256), 0, s, a);
-    else if (max_rows <= 2)
-        hipLaunchKernelGGL((fc_policy_kernel<2, MODE>), dim3(n_tasks), dim3(256), 0, s, a);
-    else if (max_rows <= 5)
-        hipLaunchKernelGGL((fc_policy_kernel<5, MODE>), dim3(n_tasks), dim3(256), 0, s, a);
-    else if (max_rows <= 8)
-        hipLaunchKernelGGL((fc_policy_kernel<8, MODE>), dim3(n_tasks), dim3(256), 0, s, a);
+    if (max_rows <= 8)
+        dispatch_rows(max_rows, [&](auto R) {
+            hipLaunchKernelGGL((fc_policy_kernel<decltype(R)::value, MODE>), dim3(n_tasks), dim3(256), 0, s, a);
+        });
     else
         hipLaunchKernelGGL((fc_policy_mfma_kernel<MODE>), dim3(n_tasks), dim3(256), 0, s, a);
     COEVO_HIP_CHECK(hipGetLastError());
@@ -2110,14 +2050,8 @@ extern "C" int coevo_mpe_cycle_kernel_form(int n_heavy, int n_light, int heavy_m
 {
     if (n_heavy <= 0 || n_light <= 0 || light_max_rows < 1 || light_max_rows > 8) return COEVO_ERR_ARG;
     // workgroup slots of the 32-row kernel: two per CU (<= 256 registers, ~73 KiB LDS)
-    static int slots = 0;
-    if (slots == 0) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            return COEVO_ERR_HIP;
-        slots = 2 * cus;
-    }
+    const int slots = 2 * coevo::device_cu_count();
+    if (slots <= 0) return COEVO_ERR_HIP;
     const int conc = concurrent_launches > 1 ? concurrent_launches : 1;
     const int wgs = (n_heavy + n_light) * conc;
     // every task of <= 8 rows and no more workgroups in flight than CUs: the small-launch kernel (COEVO_SMALL_KERNEL=0: A/B).
@@ -2141,27 +2075,25 @@ extern "C" int coevo_mpe_persistent_fits(int n_heavy, int n_light, int heavy_max
     if (n_heavy < 0 || n_light < 0 || n_heavy + n_light <= 0) return COEVO_ERR_ARG;
     if ((n_light > 0 && (light_max_rows < 1 || light_max_rows > 8)) || (n_heavy > 0 && heavy_max_rows < 1)) return COEVO_ERR_ARG;
     if (n_heavy > 0 && heavy_max_rows > 8) return 0;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        return COEVO_ERR_HIP;
+    const int cus = coevo::device_cu_count();
+    if (cus <= 0) return COEVO_ERR_HIP;
     // what the runtime says the instantiation's residency is (two per CU as built; asked, not assumed: a launch that is not
     // all resident would wait for itself)
     const int hr = n_heavy > 0 ? heavy_max_rows : 0, lr = n_light > 0 ? light_max_rows : 0, rows = hr > lr ? hr : lr;
-    static int per_cu[4] = {-1, -1, -1, -1};
-    const int slot = rows <= 1 ? 0 : rows <= 2 ? 1 : rows <= 5 ? 2 : 3;
-    if (per_cu[slot] < 0) {
-        int n = 0;
-        const hipError_t e =
-            slot == 0   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, coevo::fc_rollout_small_kernel<1>, 256, 0)
-            : slot == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, coevo::fc_rollout_small_kernel<2>, 256, 0)
-            : slot == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, coevo::fc_rollout_small_kernel<5>, 256, 0)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, coevo::fc_rollout_small_kernel<8>, 256, 0);
-        if (e != hipSuccess) return COEVO_ERR_HIP;
-        per_cu[slot] = n > 2 ? 2 : n;   // (never more than the two the kernel was sized for)
-    }
+    static int per_cu_of[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};   // by the instantiation's R
+    int per_cu = -1;
+    coevo::dispatch_rows(rows, [&](auto R) {
+        constexpr int RR = decltype(R)::value;
+        if (per_cu_of[RR] < 0) {
+            int n = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, coevo::fc_rollout_small_kernel<RR>, 256, 0) == hipSuccess)
+                per_cu_of[RR] = n > 2 ? 2 : n;   // (never more than the two the kernel was sized for)
+        }
+        per_cu = per_cu_of[RR];
+    });
+    if (per_cu < 0) return COEVO_ERR_HIP;
     const int conc = concurrent_launches > 1 ? concurrent_launches : 1;
-    return (n_heavy + n_light) * conc <= per_cu[slot] * cus ? 1 : 0;
+    return (n_heavy + n_light) * conc <= per_cu * cus ? 1 : 0;
 }
 
 extern "C" int coevo_mpe_persistent_sync_words(int n_games) { return n_games > 0 ? 4 + 6 * n_games : COEVO_ERR_ARG; }
@@ -2199,10 +2131,9 @@ extern "C" int coevo_mpe_rollout_persistent(const float *slab, const coevo_fc_ta
     const int hr = n_heavy > 0 ? heavy_max_rows : 0, lr = n_light > 0 ? light_max_rows : 0;
     const int rows = hr > lr ? hr : lr;
     const dim3 grid(n_heavy + n_light), block(256);
-    if (rows <= 1) hipLaunchKernelGGL((coevo::fc_rollout_small_kernel<1>), grid, block, 0, s, a, pa);
-    else if (rows <= 2) hipLaunchKernelGGL((coevo::fc_rollout_small_kernel<2>), grid, block, 0, s, a, pa);
-    else if (rows <= 5) hipLaunchKernelGGL((coevo::fc_rollout_small_kernel<5>), grid, block, 0, s, a, pa);
-    else hipLaunchKernelGGL((coevo::fc_rollout_small_kernel<8>), grid, block, 0, s, a, pa);
+    coevo::dispatch_rows(rows, [&](auto R) {
+        hipLaunchKernelGGL((coevo::fc_rollout_small_kernel<decltype(R)::value>), grid, block, 0, s, a, pa);
+    });
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }
@@ -2227,40 +2158,26 @@ extern "C" int coevo_mpe_policy_cycle_merged(const float *slab, const coevo_fc_t
     const int form = coevo_mpe_cycle_kernel_form(n_heavy, n_light, heavy_max_rows, light_max_rows, concurrent_launches);
     if (form < 0) return form;
     hipStream_t s = (hipStream_t)stream;
-    if (form == COEVO_CYCLE_FORM_SMALL) {
-        const int rows = heavy_max_rows > light_max_rows ? heavy_max_rows : light_max_rows;
-        const dim3 grid_s(n_heavy + n_light), block_s(256);
-        if (rows <= 1) hipLaunchKernelGGL((coevo::fc_cycle_small_kernel<1>), grid_s, block_s, 0, s, a);
-        else if (rows <= 2) hipLaunchKernelGGL((coevo::fc_cycle_small_kernel<2>), grid_s, block_s, 0, s, a);
-        else if (rows <= 5) hipLaunchKernelGGL((coevo::fc_cycle_small_kernel<5>), grid_s, block_s, 0, s, a);
-        else hipLaunchKernelGGL((coevo::fc_cycle_small_kernel<8>), grid_s, block_s, 0, s, a);
-        COEVO_HIP_CHECK(hipGetLastError());
-        return COEVO_OK;
-    }
-    // (when not everything fits - Co-ES with 3000 nets - the 32-row tiles with two nets per streaming workgroup are
-    // ahead: 109 vs 106 generations/s)
-    if (form == COEVO_CYCLE_FORM_LEAN16) {
-        // the lean kernel: four workgroups per CU hold everything at one net per streaming workgroup
-        const dim3 grid16(n_heavy + n_light), block16(256);
-        if (light_max_rows <= 1) hipLaunchKernelGGL((coevo::fc_cycle16_kernel<1>), grid16, block16, 0, s, a);
-        else if (light_max_rows <= 2) hipLaunchKernelGGL((coevo::fc_cycle16_kernel<2>), grid16, block16, 0, s, a);
-        else if (light_max_rows <= 5) hipLaunchKernelGGL((coevo::fc_cycle16_kernel<5>), grid16, block16, 0, s, a);
-        else hipLaunchKernelGGL((coevo::fc_cycle16_kernel<8>), grid16, block16, 0, s, a);
-        COEVO_HIP_CHECK(hipGetLastError());
-        return COEVO_OK;
-    }
     const bool pair = form == COEVO_CYCLE_FORM_TILE32_PAIRED;
+    // (only the paired 32-row form carries two nets per streaming workgroup: n_heavy + n_light workgroups in every other form)
     const dim3 grid(n_heavy + (pair ? (n_light + 1) / 2 : n_light)), block(256);
-#define COEVO_LAUNCH_CYCLE(RR)                                                                    \
-    do {                                                                                          \
-        if (pair) hipLaunchKernelGGL((coevo::fc_cycle_kernel<RR, 2>), grid, block, 0, s, a);      \
-        else hipLaunchKernelGGL((coevo::fc_cycle_kernel<RR, 1>), grid, block, 0, s, a);           \
-    } while (0)
-    if (light_max_rows <= 1) COEVO_LAUNCH_CYCLE(1);
-    else if (light_max_rows <= 2) COEVO_LAUNCH_CYCLE(2);
-    else if (light_max_rows <= 5) COEVO_LAUNCH_CYCLE(5);
-    else COEVO_LAUNCH_CYCLE(8);
-#undef COEVO_LAUNCH_CYCLE
+    if (form == COEVO_CYCLE_FORM_SMALL) {
+        coevo::dispatch_rows(heavy_max_rows > light_max_rows ? heavy_max_rows : light_max_rows, [&](auto R) {
+            hipLaunchKernelGGL((coevo::fc_cycle_small_kernel<decltype(R)::value>), grid, block, 0, s, a);
+        });
+    } else if (form == COEVO_CYCLE_FORM_LEAN16) {
+        // the lean kernel: four workgroups per CU hold everything at one net per streaming workgroup
+        coevo::dispatch_rows(light_max_rows, [&](auto R) {
+            hipLaunchKernelGGL((coevo::fc_cycle16_kernel<decltype(R)::value>), grid, block, 0, s, a);
+        });
+    } else {
+        // (when not everything fits - Co-ES with 3000 nets - the 32-row tiles with two nets per streaming workgroup are
+        // ahead: 109 vs 106 generations/s)
+        coevo::dispatch_rows(light_max_rows, [&](auto R) {
+            if (pair) hipLaunchKernelGGL((coevo::fc_cycle_kernel<decltype(R)::value, 2>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((coevo::fc_cycle_kernel<decltype(R)::value, 1>), grid, block, 0, s, a);
+        });
+    }
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }
@@ -2276,19 +2193,16 @@ extern "C" int coevo_fc_forward_merged(const float *slab, const coevo_fc_task *h
     if (!slab || !heavy_tasks || !light_tasks || !obs || !actions || !status) return COEVO_ERR_ARG;
     if (n_heavy <= 0 || n_light <= 0 || heavy_max_rows < 1 || heavy_max_rows > 16 || light_max_rows < 1 || light_max_rows > 8)
         return COEVO_ERR_ARG;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        return COEVO_ERR_HIP;
+    const int cus = coevo::device_cu_count();
+    if (cus <= 0) return COEVO_ERR_HIP;
     if (n_heavy + n_light > 4 * cus) return COEVO_ERR_ARG;
     coevo::FcArgs a{slab, heavy_tasks, obs, nullptr, nullptr, nullptr, 0, actions, logits, status, nullptr, nullptr, nullptr,
                     nullptr, nullptr, 0, 0, light_tasks, n_heavy, n_light};
     const dim3 grid(n_heavy + n_light), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (light_max_rows <= 1) hipLaunchKernelGGL((coevo::fc_cycle16_kernel<1, coevo::MODE_OBS>), grid, block, 0, s, a);
-    else if (light_max_rows <= 2) hipLaunchKernelGGL((coevo::fc_cycle16_kernel<2, coevo::MODE_OBS>), grid, block, 0, s, a);
-    else if (light_max_rows <= 5) hipLaunchKernelGGL((coevo::fc_cycle16_kernel<5, coevo::MODE_OBS>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((coevo::fc_cycle16_kernel<8, coevo::MODE_OBS>), grid, block, 0, s, a);
+    coevo::dispatch_rows(light_max_rows, [&](auto R) {
+        hipLaunchKernelGGL((coevo::fc_cycle16_kernel<decltype(R)::value, coevo::MODE_OBS>), grid, block, 0, s, a);
+    });
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }

@@ -1,6 +1,9 @@
 """Fault bits, ties, signed zeros and subnormals in EVERY fp32 policy-forward body of csrc/fc_forward.hip, against the oracle.
 
-The forward, its COEVO_ST_* fault detection and its first-maximum argmax are written out once per body; the nets of
+The bodies share the output chain, the first-maximum argmax with its BAD_OUT / NO_ACTION bits, the action store and (the two
+lean forms) most of the packed LayerNorm passes as helpers; the observation entry, fc1, fc2 and the BAD_INPUT / BAD_FC1 /
+BAD_FC2 detection of the tile bodies are still written out once per body, and a helper is inlined into every body's own
+register budget, so the nets of
 tests/fc_edge_nets.py (ties, -0, +-inf, NaN, variance 0, subnormal fc1 / fc2 weights) go through each of them.  Expected
 logits, actions and status words are always rp.fc_forward's / rp.play_game_status's (oracle/coevo_oracle.c); finite values,
 infinities and the sign of zero are compared as bits, NaN by NaN-ness (x86 and gfx950 have different default NaNs), and the
