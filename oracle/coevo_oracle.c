@@ -446,6 +446,21 @@ void oracle_philox_normal4(uint64_t seed, uint32_t stream_lo, uint32_t stream_hi
     box_muller(o[2], o[3], &z[2], &z[3]);
 }
 
+/* n_quads consecutive quads from q_first on (the 32-bit quad counter wraps); out = [n_quads][4] */
+void oracle_philox_normals(uint64_t seed, uint32_t stream_lo, uint32_t stream_hi, uint32_t q_first, int64_t n_quads,
+                           float *out)
+{
+    for (int64_t i = 0; i < n_quads; ++i)
+        oracle_philox_normal4(seed, stream_lo, stream_hi, q_first + (uint32_t)i, out + 4 * i);
+}
+
+/* the transform alone, for raw generator words (a, b): u1 = (2 (a >> 9) + 1) / 2^24, u2 = (b >> 8) / 2^24 */
+void oracle_box_muller(uint32_t a, uint32_t b, float out[2]) { box_muller(a, b, &out[0], &out[1]); }
+void oracle_box_muller_n(const uint32_t *a, const uint32_t *b, int64_t n, float *out) /* out = [n][2] */
+{
+    for (int64_t i = 0; i < n; ++i) oracle_box_muller(a[i], b[i], out + 2 * i);
+}
+
 /* child[p] = parent[p] + sigma*z[p]  (noise rounded first, then added - agent.py:28-29).
  * skip = list of [off,len) segments left untouched (LayerNorm affine for ES, agent.py:51-53 via
  * MPE/fcnetwork.py:185-199). */

@@ -63,6 +63,9 @@ def lib():
         L.oracle_diversity.restype = C.c_double
         L.oracle_diversity.argtypes = [fp, fp, C.c_int, C.c_size_t, ip, ip, C.c_int, fp]
         L.oracle_philox_normal4.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, fp]
+        L.oracle_philox_normals.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, fp]
+        L.oracle_box_muller.argtypes = [C.c_uint32, C.c_uint32, fp]
+        L.oracle_box_muller_n.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64, fp]
         L.oracle_philox4x32.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.oracle_noise_rounds.restype = C.c_int
         L.oracle_perturb_philox.argtypes = [fp, fp, C.c_int, C.c_float, C.c_uint64, C.c_uint32, C.c_uint32,
@@ -254,6 +257,27 @@ def diversity(individual_es, population_es):
 
 
 # ------------------------------------------------------------------ Co-GA
+def philox_normals(seed, stream_lo, stream_hi, q_first, n_quads):
+    """-> fp32 [n_quads][4]: the standard normals of quads q_first, q_first + 1, ... (mod 2^32) of one stream"""
+    out = np.empty((int(n_quads), 4), dtype=np.float32)
+    lib().oracle_philox_normals(int(seed), int(stream_lo), int(stream_hi), int(q_first) & 0xffffffff, int(n_quads), _fp(out))
+    return out
+
+
+def box_muller(a, b):
+    """the transform on raw generator words: uint32 arrays a, b -> fp32 [n][2] (z0 = r cos, z1 = r sin)"""
+    a = np.ascontiguousarray(np.atleast_1d(a), dtype=np.uint32)
+    b = np.ascontiguousarray(np.atleast_1d(b), dtype=np.uint32)
+    assert a.shape == b.shape and a.ndim == 1
+    out = np.empty((len(a), 2), dtype=np.float32)
+    if len(a) == 1:
+        lib().oracle_box_muller(int(a[0]), int(b[0]), _fp(out))
+    else:
+        u32p = C.POINTER(C.c_uint32)
+        lib().oracle_box_muller_n(a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), len(a), _fp(out))
+    return out
+
+
 def perturb_philox_flat(flat, sigma, seed, stream_lo, stream_hi, skip_segments=(), negate=False):
     """child = parent +- sigma*eps(seed, stream, canonical index) over any flat parameter vector (FCNetwork or DeepQN)"""
     flat = np.ascontiguousarray(flat, dtype=np.float32)
