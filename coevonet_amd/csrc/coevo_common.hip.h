@@ -36,6 +36,21 @@ __host__ __device__ constexpr int64_t fc_off_w3(int D) { return fc_off_b2(D) + 3
 __host__ __device__ constexpr int64_t fc_off_b3(int D) { return fc_off_w3(D) + NACT * H2; }
 __host__ __device__ constexpr int64_t fc_params(int D) { return fc_off_b3(D) + NACT; }
 __host__ __device__ constexpr int64_t fc_stride(int D) { return (fc_params(D) + 63) / 64 * 64; }
+// the LayerNorm affine parameters: g1, be1 behind b1 and g2, be2 behind b2
+__host__ __device__ constexpr int64_t fc_off_g1(int D) { return fc_off_b1(D) + H1; }
+__host__ __device__ constexpr int64_t fc_off_g2(int D) { return fc_off_b2(D) + H2; }
+__host__ __device__ inline bool fc_slab_is_layernorm(int64_t s, int D)
+{
+    const int64_t g1 = fc_off_g1(D), g2 = fc_off_g2(D);
+    return (s >= g1 && s < g1 + 2 * H1) || (s >= g2 && s < g2 + 2 * H2);
+}
+static inline bool fc_dim_ok(int D) { return D == 8 || D == 10; }
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// The streaming kernels give a thread one 16-byte piece (four slab positions) of a net, 256 pieces to a workgroup:
+// the first slab position of the thread's piece in workgroup bx, and the workgroups that cover `stride` floats.
+__device__ __forceinline__ int64_t quad_first(int64_t bx) { return (bx * 256 + threadIdx.x) * 4; }
+__host__ __device__ constexpr unsigned quad_blocks(int64_t stride) { return (unsigned)((stride / 4 + 255) / 256); }
 
 // slab position -> canonical flat index (torch parameters() order: fc1.w[512][D], fc1.b, ln1.w, ln1.b,
 // fc2.w[256][512], fc2.b, ln2.w, ln2.b, output.w[5][256], output.b).  Only W1 and W2 are re-tiled.
@@ -355,6 +370,17 @@ __device__ inline double block_sum_f64(double v, double *scratch)
     const double tot = ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
     __syncthreads();
     return tot;
+}
+
+// the n_blocks fp64 partials of one net on ONE wavefront: lane-strided sums, then the xor tree (a fixed order); every lane
+// returns the total.  The caller rounds: (float)sqrt for fp32 nets, f16_of_f64(sqrt) for fp16 nets.
+__device__ __forceinline__ double wave_sum_partials(const double *partial, int n_blocks)
+{
+    double v = 0.0;
+    for (int b = threadIdx.x; b < n_blocks; b += 64) v += partial[b];
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
 }
 
 __device__ inline bool bad_post_relu(float y) { return __builtin_isnan(y) || (__builtin_isinf(y) && y > 0.0f); }

@@ -722,7 +722,6 @@ __global__ __launch_bounds__(64) void dqn_out_kernel(const float *slab, const co
 
 using namespace coevo;
 
-static bool dqn_shape_ok(int C, int n) { return C >= 1 && C <= 6 && n >= 1 && n <= COEVO_DQN_LOGIT_STRIDE; }
 
 extern "C" int64_t coevo_dqn_param_count(int C, int n_actions)
 {

@@ -272,11 +272,10 @@ __global__ __launch_bounds__(64) void dqn16_out_kernel(const uint32_t *slab, con
 
 using namespace coevo;
 
-static bool dqn16_shape_ok(int C, int n) { return C >= 1 && C <= 6 && n >= 1 && n <= COEVO_DQN_LOGIT_STRIDE; }
 
 extern "C" int64_t coevo_dqn16_slab_stride(int C, int n_actions)
 {
-    return dqn16_shape_ok(C, n_actions) ? dqn16_layout(C, n_actions).stride : COEVO_ERR_ARG;
+    return dqn_shape_ok(C, n_actions) ? dqn16_layout(C, n_actions).stride : COEVO_ERR_ARG;
 }
 
 extern "C" int64_t coevo_dqn16_workspace_bytes(int n_rows_total)
@@ -286,7 +285,7 @@ extern "C" int64_t coevo_dqn16_workspace_bytes(int n_rows_total)
 
 static int dqn16_pack_launch(float *flat, uint32_t *slab, int n, int C, int n_actions, bool to_slab, void *stream)
 {
-    if (!flat || !slab || n <= 0 || !dqn16_shape_ok(C, n_actions)) return COEVO_ERR_ARG;
+    if (!flat || !slab || n <= 0 || !dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;
     const dim3 grid((unsigned)((dqn16_layout(C, n_actions).stride + 255) / 256), (unsigned)n);
     hipLaunchKernelGGL(dqn16_pack_kernel, grid, dim3(256), 0, (hipStream_t)stream, flat, slab, C, n_actions, to_slab);
     COEVO_HIP_CHECK(hipGetLastError());
@@ -308,7 +307,7 @@ extern "C" int coevo_dqn16_forward_argmax(const void *slab, const coevo_dqn_task
                                           float *logits, int32_t *status, void *workspace, void *stream)
 {
     if (!slab || !tasks || !frames || !actions || !status || !workspace) return COEVO_ERR_ARG;
-    if (n_tasks <= 0 || n_rows_total <= 0 || !dqn16_shape_ok(C, n_actions)) return COEVO_ERR_ARG;   // (any bit or-ed into C fails here)
+    if (n_tasks <= 0 || n_rows_total <= 0 || !dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;   // (any bit or-ed into C fails here)
     if (max_rows_per_task < 1 || max_rows_per_task > DQ16_RMAX) return COEVO_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(slab) & 15) return COEVO_ERR_ARG;
     const uint32_t *sl = static_cast<const uint32_t *>(slab);

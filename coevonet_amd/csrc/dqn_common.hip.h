@@ -169,4 +169,7 @@ __device__ __forceinline__ int dqn_out_row(const float *net, const DqnLayout L, 
     return __float_as_int(lg[63]);
 }
 
+// the DeepQN shapes every entry point accepts: 1 .. 6 input channels, 1 .. COEVO_DQN_LOGIT_STRIDE actions
+static inline bool dqn_shape_ok(int C, int n) { return C >= 1 && C <= 6 && n >= 1 && n <= COEVO_DQN_LOGIT_STRIDE; }
+
 }  // namespace coevo

@@ -239,10 +239,9 @@ __global__ __launch_bounds__(256) void synth_step_kernel(int32_t *gstate, double
 
 using namespace coevo;
 
-static bool dqn_shape_ok2(int C, int n) { return C >= 1 && C <= 6 && n >= 1 && n <= COEVO_DQN_LOGIT_STRIDE; }
 
 static int64_t dqn_perturb_grid(const DqnLayout &L, int tiled) { return (L.stride / 4 + (tiled ? dqn_perturb_shift(L) : 0) + 255) / 256; }
-static bool dqn_carg_ok(int c_arg, int n) { return !(c_arg & ~(0xff | COEVO_DQN_FC1_TILED)) && dqn_shape_ok2(dqn_channels(c_arg), n); }
+static bool dqn_carg_ok(int c_arg, int n) { return !(c_arg & ~(0xff | COEVO_DQN_FC1_TILED)) && dqn_shape_ok(dqn_channels(c_arg), n); }
 
 extern "C" int64_t coevo_dqn_perturb_blocks(int c_arg, int n_actions)
 {
@@ -306,7 +305,7 @@ extern "C" int coevo_synth_step(int32_t *game_state, double *acc, int n_games, c
                                 uint8_t *frames, int C, int n_actions, uint64_t seed, void *stream)
 {
     if (!game_state || !acc || !game_ordinal0 || !limit || n_games <= 0 || t < 0 || t > 65535) return COEVO_ERR_ARG;
-    if (!dqn_shape_ok2(C, n_actions)) return COEVO_ERR_ARG;
+    if (!dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;
     if (t > 0 && (!row_prev || !actions_prev)) return COEVO_ERR_ARG;
     if (frames && !row_cur) return COEVO_ERR_ARG;
     hipLaunchKernelGGL(synth_step_kernel<false>, dim3(n_games), dim3(256), 0, (hipStream_t)stream, game_state, acc, n_games,
@@ -324,7 +323,7 @@ extern "C" int coevo_dqn_out_synth_step(int32_t *game_state, double *acc, int n_
                                         const void *workspace, int32_t *status, void *stream)
 {
     if (!game_state || !acc || !game_ordinal0 || !limit || n_games <= 0 || t < 1 || t > 65535) return COEVO_ERR_ARG;
-    if (!dqn_shape_ok2(C, n_actions) || !row_prev || !actions_prev || (frames && !row_cur)) return COEVO_ERR_ARG;
+    if (!dqn_shape_ok(C, n_actions) || !row_prev || !actions_prev || (frames && !row_cur)) return COEVO_ERR_ARG;
     if (!slab || !tasks_prev || n_tasks_prev <= 0 || n_rows_total <= 0 || !workspace || !status) return COEVO_ERR_ARG;
     const float *hid = static_cast<const float *>(workspace) + (size_t)n_rows_total * DQ_FC1_IN;   // (deepqn.hip's layout)
     hipLaunchKernelGGL(synth_step_kernel<true>, dim3(n_games), dim3(256), 0, (hipStream_t)stream, game_state, acc, n_games,

@@ -227,13 +227,11 @@ __global__ __launch_bounds__(256) void fc16_policy_kernel(Fc16Args a)
 
 using namespace coevo;
 
-static bool fc16_dim_ok(int D) { return D == 8 || D == 10; }
-
-extern "C" int64_t coevo_fc16_slab_stride(int D) { return fc16_dim_ok(D) ? f16_stride(D) : COEVO_ERR_ARG; }
+extern "C" int64_t coevo_fc16_slab_stride(int D) { return fc_dim_ok(D) ? f16_stride(D) : COEVO_ERR_ARG; }
 
 static int fc16_pack_launch(const float *flat, uint32_t *slab, int n, int D, bool to_slab, void *stream)
 {
-    if (!flat || !slab || n <= 0 || !fc16_dim_ok(D)) return COEVO_ERR_ARG;
+    if (!flat || !slab || n <= 0 || !fc_dim_ok(D)) return COEVO_ERR_ARG;
     const int64_t threads = fc_params(D) + (f16_stride(D) - f16_used(D));
     const dim3 grid((unsigned)((threads + 255) / 256), (unsigned)n);
     hipLaunchKernelGGL(fc16_pack_kernel, grid, dim3(256), 0, (hipStream_t)stream, flat, slab, D, to_slab);

@@ -150,11 +150,9 @@ __global__ __launch_bounds__(256) void fc16_es_apply_kernel(uint32_t *theta, con
 
 using namespace coevo;
 
-static bool es16_dim_ok(int D) { return D == 8 || D == 10; }
-static bool es16_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 constexpr int ES16_MAX_CHUNKS = 64;
 
-extern "C" int64_t coevo_es16_partial_floats(int D) { return es16_dim_ok(D) ? es16_partial_floats(D) : COEVO_ERR_ARG; }
+extern "C" int64_t coevo_es16_partial_floats(int D) { return fc_dim_ok(D) ? es16_partial_floats(D) : COEVO_ERR_ARG; }
 
 extern "C" int coevo_es16_fitness(const double *rewards, const int32_t *game_idx, int slot, int n, const float *score,
                                   float *fitness, void *stream)
@@ -169,8 +167,8 @@ extern "C" int coevo_es16_fitness(const double *rewards, const int32_t *game_idx
 extern "C" int coevo_es16_partial(int D, const float *fitness, int n_total, int chunks_total, const float *sigma_dev,
                                   uint64_t seed, uint32_t stream_lo_first, uint32_t stream_hi, float *partial, void *stream)
 {
-    if (!fitness || !sigma_dev || !partial || !es16_dim_ok(D) || n_total < 1) return COEVO_ERR_ARG;
-    if (chunks_total < 1 || chunks_total > ES16_MAX_CHUNKS || !es16_aligned16(partial)) return COEVO_ERR_ARG;
+    if (!fitness || !sigma_dev || !partial || !fc_dim_ok(D) || n_total < 1) return COEVO_ERR_ARG;
+    if (chunks_total < 1 || chunks_total > ES16_MAX_CHUNKS || !aligned16(partial)) return COEVO_ERR_ARG;
     const dim3 grid((unsigned)f16_perturb_blocks(D), (unsigned)chunks_total);
     hipLaunchKernelGGL(fc16_es_partial_kernel, grid, dim3(256), 0, (hipStream_t)stream, D, fitness, n_total, chunks_total,
                        sigma_dev, seed, stream_lo_first, stream_hi, partial);
@@ -181,9 +179,9 @@ extern "C" int coevo_es16_partial(int D, const float *fitness, int n_total, int 
 extern "C" int coevo_es16_apply(void *theta16_net, const float *partial, int chunks_total, int D, int n_total,
                                 const float *sigma_dev, double lr, void *stream)
 {
-    if (!theta16_net || !partial || !sigma_dev || !es16_dim_ok(D) || n_total < 1) return COEVO_ERR_ARG;
+    if (!theta16_net || !partial || !sigma_dev || !fc_dim_ok(D) || n_total < 1) return COEVO_ERR_ARG;
     if (chunks_total < 1 || chunks_total > ES16_MAX_CHUNKS) return COEVO_ERR_ARG;
-    if (!es16_aligned16(theta16_net) || !es16_aligned16(partial)) return COEVO_ERR_ARG;
+    if (!aligned16(theta16_net) || !aligned16(partial)) return COEVO_ERR_ARG;
     hipLaunchKernelGGL(fc16_es_apply_kernel, dim3((unsigned)f16_perturb_blocks(D)), dim3(256), 0, (hipStream_t)stream,
                        static_cast<uint32_t *>(theta16_net), partial, chunks_total, D, n_total, sigma_dev, lr);
     COEVO_HIP_CHECK(hipGetLastError());

@@ -22,6 +22,7 @@
 #include "coevo_common.hip.h"
 #include "fc16_layout.hip.h"
 #include "fc16_pieces.hip.h"
+#include "promote_roles.hip.h"
 #include "philox.hip.h"
 
 namespace coevo {
@@ -121,32 +122,16 @@ __global__ __launch_bounds__(256) void fc16_distance_kernel(const uint32_t *ref_
     if (threadIdx.x == 0) dist_partial[(size_t)n * gridDim.x + bx] = tot;
 }
 
-// dist[first + c] = f16(sqrt(sum_b partial[c][b])), dist_finalize_kernel's order (lane-strided sums, then the xor tree);
-// head: dist[first - 1] = *head
+// dist[first + c] = f16(sqrt(sum_b partial[c][b])), dist_finalize_kernel's order; head: dist[first - 1] = *head
 __global__ __launch_bounds__(64) void fc16_dist_finalize_kernel(const double *partial, int n_blocks, float *dist, int first,
                                                                  const float *head)
 {
-    const int c = blockIdx.x, l = threadIdx.x;
-    double v = 0.0;
-    for (int b = l; b < n_blocks; b += 64) v += partial[(size_t)c * n_blocks + b];
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
-    if (l == 0) {
+    const int c = blockIdx.x;
+    const double v = wave_sum_partials(partial + (size_t)c * n_blocks, n_blocks);
+    if (threadIdx.x == 0) {
         dist[first + c] = f16_of_f64(sqrt(v));
         if (c == 0 && head) dist[first - 1] = *head;
     }
-}
-
-// dst[dst_first + c] = src[src_idx[c]], whole 16-byte words of the stride
-__global__ __launch_bounds__(256) void fc16_gather_kernel(const uint32_t *src_slab, const int32_t *src_idx,
-                                                           uint32_t *dst_slab, int dst_first, int D)
-{
-    const int c = blockIdx.y;
-    const int u = blockIdx.x * 256 + (int)threadIdx.x;
-    if (u >= f16_pieces(D)) return;
-    const int64_t stride = f16_stride(D);
-    const uint4 v = reinterpret_cast<const uint4 *>(src_slab + (int64_t)src_idx[c] * stride)[u];
-    reinterpret_cast<uint4 *>(dst_slab + (int64_t)(dst_first + c) * stride)[u] = v;
 }
 
 // ---- elites -> elite buffer, HoF FIFO push, best -> pop[0] for up to three roles in one launch: ga_promote_kernel of
@@ -157,12 +142,11 @@ struct Ga16PromoteArgs {
     coevo_ga16_promote_role role[3];
     int E, hof;
 };
-constexpr int PROMOTE16_MAX_E = 8, PROMOTE16_MAX_HOF = 16;
 
 template <int I>
 __device__ __forceinline__ void promote16_hof_shift(uint4 *hof, int64_t pitch, int n)
 {
-    if constexpr (I < PROMOTE16_MAX_HOF) {
+    if constexpr (I < PROMOTE_MAX_HOF) {
         const uint4 v = hof[(int64_t)(I < n ? I : n - 1) * pitch];
         promote16_hof_shift<I + 1>(hof, pitch, n);
         hof[(int64_t)(I < n ? I - 1 : n - 1) * pitch] = v;   // (a surplus level rewrites the last slot; the caller overwrites it)
@@ -173,7 +157,7 @@ __device__ __forceinline__ void promote16_hof_shift(uint4 *hof, int64_t pitch, i
 template <int K>
 __device__ __forceinline__ uint4 promote16_elites(const uint4 *pop, const int32_t *order, uint4 *elite, int64_t pitch, int E)
 {
-    if constexpr (K < PROMOTE16_MAX_E) {
+    if constexpr (K < PROMOTE_MAX_E) {
         const int kc = K < E ? K : E - 1;
         const uint4 v = pop[(int64_t)order[kc] * pitch];
         promote16_elites<K + 1>(pop, order, elite, pitch, E);
@@ -186,31 +170,23 @@ __device__ __forceinline__ uint4 promote16_elites(const uint4 *pop, const int32_
 
 __global__ __launch_bounds__(256) void ga16_promote_kernel(Ga16PromoteArgs a)
 {
-    // (field-wise selects: indexing the by-value argument array dynamically copies it to scratch)
     const unsigned y = blockIdx.y;
-#define PROMOTE16_SEL(f) (y == 0 ? a.role[0].f : (y == 1 ? a.role[1].f : a.role[2].f))
-    void *pop_v = PROMOTE16_SEL(pop), *hof_v = PROMOTE16_SEL(hof), *elite_v = PROMOTE16_SEL(elite);
-    const int32_t *order = PROMOTE16_SEL(order);
-    const int D = PROMOTE16_SEL(D), from_pop = PROMOTE16_SEL(elites_from_pop), to_pop0 = PROMOTE16_SEL(best_to_pop0);
-#undef PROMOTE16_SEL
+    const PromoteRole R = PROMOTE_ROLE(a, y);
     const int u = blockIdx.x * 256 + (int)threadIdx.x;
-    if (u >= f16_pieces(D)) return;
-    const int64_t pitch = f16_pieces(D);   // 16-byte pieces between consecutive nets
-    uint4 *pop = static_cast<uint4 *>(pop_v) + u, *hof = static_cast<uint4 *>(hof_v) + u, *elite = static_cast<uint4 *>(elite_v) + u;
-    const uint4 e0 = from_pop ? promote16_elites<0>(pop, order, elite, pitch, a.E) : elite[0];
+    if (u >= f16_pieces(R.D)) return;
+    const int64_t pitch = f16_pieces(R.D);   // 16-byte pieces between consecutive nets
+    uint4 *pop = static_cast<uint4 *>(R.pop) + u, *hof = static_cast<uint4 *>(R.hof) + u, *elite = static_cast<uint4 *>(R.elite) + u;
+    const uint4 e0 = R.from_pop ? promote16_elites<0>(pop, R.order, elite, pitch, a.E) : elite[0];
     promote16_hof_shift<1>(hof, pitch, a.hof);
     hof[(int64_t)(a.hof - 1) * pitch] = e0;
-    if (to_pop0) pop[0] = e0;
+    if (R.to_pop0) pop[0] = e0;
 }
 
 }  // namespace coevo
 
 using namespace coevo;
 
-static bool fc16_dim_ok(int D) { return D == 8 || D == 10; }
-static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-extern "C" int64_t coevo_fc16_perturb_blocks(int D) { return fc16_dim_ok(D) ? f16_perturb_blocks(D) : COEVO_ERR_ARG; }
+extern "C" int64_t coevo_fc16_perturb_blocks(int D) { return fc_dim_ok(D) ? f16_perturb_blocks(D) : COEVO_ERR_ARG; }
 
 extern "C" int coevo_fc16_perturb_dist(const void *parent_slab, const int32_t *parent_idx, void *child_slab, int child_first,
                                        int n_children, int D, const float *sigma_dev, uint64_t seed,
@@ -218,7 +194,7 @@ extern "C" int coevo_fc16_perturb_dist(const void *parent_slab, const int32_t *p
                                        const void *dist_ref, double *dist_partial, void *stream)
 {
     if ((dist_ref == nullptr) != (dist_partial == nullptr)) return COEVO_ERR_ARG;
-    if (!parent_slab || !parent_idx || !child_slab || !sigma_dev || !fc16_dim_ok(D)) return COEVO_ERR_ARG;
+    if (!parent_slab || !parent_idx || !child_slab || !sigma_dev || !fc_dim_ok(D)) return COEVO_ERR_ARG;
     if (!aligned16(parent_slab) || !aligned16(child_slab) || !aligned16(dist_ref)) return COEVO_ERR_ARG;
     if (n_children < 0 || child_first < 0 || n_children > 65535 || (flags & ~COEVO_PERTURB_SKIP_LAYERNORM)) return COEVO_ERR_ARG;
     if (n_children == 0) return COEVO_OK;
@@ -233,7 +209,7 @@ extern "C" int coevo_fc16_perturb_dist(const void *parent_slab, const int32_t *p
 
 extern "C" int coevo_fc16_distance(const void *ref_net, const void *pop_slab, int n, int D, double *dist_partial, void *stream)
 {
-    if (!ref_net || !pop_slab || !dist_partial || !fc16_dim_ok(D) || n < 0 || n > 65535) return COEVO_ERR_ARG;
+    if (!ref_net || !pop_slab || !dist_partial || !fc_dim_ok(D) || n < 0 || n > 65535) return COEVO_ERR_ARG;
     if (!aligned16(ref_net) || !aligned16(pop_slab)) return COEVO_ERR_ARG;
     if (n == 0) return COEVO_OK;
     const dim3 grid((unsigned)f16_perturb_blocks(D), (unsigned)n);
@@ -256,32 +232,19 @@ extern "C" int coevo_fc16_distance_finalize(const double *dist_partial, int n_bl
 extern "C" int coevo_fc16_gather(const void *src_slab, const int32_t *src_idx, void *dst_slab, int dst_first, int n, int D,
                                  void *stream)
 {
-    if (!src_slab || !src_idx || !dst_slab || !fc16_dim_ok(D) || n < 0 || dst_first < 0 || n > 65535) return COEVO_ERR_ARG;
+    if (!src_slab || !src_idx || !dst_slab || !fc_dim_ok(D) || n < 0 || dst_first < 0 || n > 65535) return COEVO_ERR_ARG;
     if (!aligned16(src_slab) || !aligned16(dst_slab)) return COEVO_ERR_ARG;
-    if (n == 0) return COEVO_OK;
-    const dim3 grid((unsigned)f16_perturb_blocks(D), (unsigned)n);
-    hipLaunchKernelGGL(fc16_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, static_cast<const uint32_t *>(src_slab),
-                       src_idx, static_cast<uint32_t *>(dst_slab), dst_first, D);
-    COEVO_HIP_CHECK(hipGetLastError());
-    return COEVO_OK;
+    // whole 16-byte pieces of the stride: fc_gather_kernel's copy, f16_pieces(D) pieces per net
+    return coevo_net_gather(static_cast<const float *>(src_slab), src_idx, static_cast<float *>(dst_slab), dst_first, n,
+                            f16_stride(D), stream);
 }
-
-static_assert(sizeof(coevo_ga16_promote_role) == 48, "layout mirrored by coevonet_amd/lib.py GaPromoteRole");
 
 extern "C" int coevo_ga16_promote(const coevo_ga16_promote_role *roles, int n_roles, int E, int hof, void *stream)
 {
-    if (!roles || n_roles < 1 || n_roles > 3 || E < 1 || E > PROMOTE16_MAX_E || hof < 1 || hof > PROMOTE16_MAX_HOF)
-        return COEVO_ERR_ARG;
     Ga16PromoteArgs a{};
+    if (!promote_roles(a, roles, n_roles, E, hof, true)) return COEVO_ERR_ARG;
     int max_blocks = 0;
-    for (int r = 0; r < n_roles; ++r) {
-        const coevo_ga16_promote_role &R = roles[r];
-        if (!R.pop || !R.hof || !R.elite || !fc16_dim_ok(R.D) || (R.elites_from_pop && !R.order)) return COEVO_ERR_ARG;
-        if (!aligned16(R.pop) || !aligned16(R.hof) || !aligned16(R.elite)) return COEVO_ERR_ARG;
-        a.role[r] = R;
-        if (f16_perturb_blocks(R.D) > max_blocks) max_blocks = f16_perturb_blocks(R.D);
-    }
-    a.E = E; a.hof = hof;
+    for (int r = 0; r < n_roles; ++r) max_blocks = std::max(max_blocks, f16_perturb_blocks(roles[r].D));
     hipLaunchKernelGGL(ga16_promote_kernel, dim3((unsigned)max_blocks, (unsigned)n_roles), dim3(256), 0, (hipStream_t)stream, a);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;

@@ -11,16 +11,10 @@
 // A child is one streaming pass: read parent (L2/Infinity-Cache resident elite), write child once.
 #include "coevo_common.hip.h"
 #include "dqn_common.hip.h"
+#include "promote_roles.hip.h"
 #include "philox.hip.h"
 
 namespace coevo {
-
-// is slab position s a LayerNorm affine parameter?
-__device__ inline bool fc_slab_is_layernorm(int64_t s, int D)
-{
-    const int64_t g1 = fc_off_b1(D) + H1, g2 = fc_off_b2(D) + H2;
-    return (s >= g1 && s < g1 + 2 * H1) || (s >= g2 && s < g2 + 2 * H2);
-}
 
 // Standard normals for the four slab positions s0..s0+3 (s0 % 4 == 0).  Everywhere except W1t the four positions
 // map to four consecutive canonical indices inside one Philox block, so one block serves them; W1t (3.7 % of a
@@ -58,7 +52,7 @@ __device__ __forceinline__ void fc_perturb_block(const float *parent_slab, const
     const uint32_t slo = antithetic ? (ind >> 1) : ind;
     const bool negate = antithetic && (ind & 1u);
     const int64_t stride = fc_stride(D), P = fc_params(D);
-    const int64_t s0 = ((int64_t)bx * 256 + threadIdx.x) * 4;
+    const int64_t s0 = quad_first(bx);
     double d2 = 0.0;
     if (s0 < stride) {
         const float sigma = *sigma_dev;
@@ -132,7 +126,7 @@ __global__ __launch_bounds__(256) void fc_perturb_multi_kernel(PerturbJobs jobs,
 {
     __shared__ double scratch[4];
     const coevo_fc_perturb_job &jb = jobs.j[blockIdx.z];
-    const int nblocks = (int)((fc_stride(jb.D) / 4 + 255) / 256);
+    const int nblocks = (int)quad_blocks(fc_stride(jb.D));
     if ((int)blockIdx.x >= nblocks || (int)blockIdx.y >= jb.n_children) return;   // workgroup-uniform
     fc_perturb_block(jb.parent_slab, jb.parent_idx, jb.child_slab, jb.child_first, jb.D, jb.sigma_dev, seed,
                      jb.stream_lo_first, jb.stream_hi, skip_layernorm, gen_dev, jb.dist_ref, jb.dist_partial, blockIdx.y,
@@ -152,7 +146,7 @@ __global__ __launch_bounds__(256) void fc_rebuild_elites_kernel(const float *eli
     if (gen_dev) stream_hi_prev += 4u * (uint32_t)(*gen_dev - 1);
     const int e = blockIdx.y;
     const int64_t stride = fc_stride(D), P = fc_params(D);
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const int64_t s0 = quad_first(blockIdx.x);
     if (s0 >= stride) return;
     const int id = order[e];
     float *dst = elite_new + (int64_t)e * stride;
@@ -176,7 +170,7 @@ __global__ __launch_bounds__(256) void fc_gather_kernel(const float *src_slab, c
                                                          float *dst_slab, int dst_first, int64_t stride)
 {
     const int c = blockIdx.y;
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const int64_t s0 = quad_first(blockIdx.x);
     if (s0 >= stride) return;
     const float4 v = *reinterpret_cast<const float4 *>(src_slab + (int64_t)src_idx[c] * stride + s0);
     *reinterpret_cast<float4 *>(dst_slab + (int64_t)(dst_first + c) * stride + s0) = v;
@@ -184,7 +178,8 @@ __global__ __launch_bounds__(256) void fc_gather_kernel(const float *src_slab, c
 
 // ---- elites -> elite buffer, HoF FIFO push, best -> pop[0] for up to three roles in ONE launch (instead of five net
 // copies per role).  A thread owns one 16-byte piece of every net it touches: it reads its piece of all sources first,
-// so the in-place HoF shift and a best individual that already sits in pop[0] need no second buffer.
+// so the in-place HoF shift and a best individual that already sits in pop[0] need no second buffer.  What this launch
+// shares with ga16_promote_kernel (fc16_offspring.hip) is in promote_roles.hip.h.
 struct GaPromoteArgs {
     coevo_ga_promote_role role[3];
     int E, hof;
@@ -198,7 +193,6 @@ struct GaPromoteArgs {
     int32_t *tick;               // NULL, or the generation counter this launch increments (nothing in it reads the counter
                                  // after the first instructions of its blocks: see ga_promote_kernel)
 };
-constexpr int PROMOTE_MAX_E = 8, PROMOTE_MAX_HOF = 16;
 
 // A thread's 16-byte pieces are held in the frames of a compile-time recursion - every load on the way down, every store
 // on the way back - not in arrays: as float4 e[8], h[16] filled by unrolled loops the compiler left both in scratch
@@ -217,14 +211,14 @@ __device__ __forceinline__ void promote_hof_shift(float *hof, int64_t stride, in
 
 // elite[k] = src[idx(k)] for k < E (k descending on the way back); returns src[idx(0)]
 template <int K>
-__device__ __forceinline__ float4 promote_elites(const float *src, const int32_t *order, float *elite, bool store,
-                                                 int64_t stride, int64_t s0, int E)
+__device__ __forceinline__ float4 promote_elites(const float *src, const int32_t *order, float *elite, int64_t stride, int64_t s0,
+                                                 int E)
 {
     if constexpr (K < PROMOTE_MAX_E) {
         const int kc = K < E ? K : E - 1;
         const float4 v = *reinterpret_cast<const float4 *>(src + (int64_t)(order ? order[kc] : kc) * stride + s0);
-        promote_elites<K + 1>(src, order, elite, store, stride, s0, E);
-        if (store) *reinterpret_cast<float4 *>(elite + (int64_t)kc * stride + s0) = v;
+        promote_elites<K + 1>(src, order, elite, stride, s0, E);
+        *reinterpret_cast<float4 *>(elite + (int64_t)kc * stride + s0) = v;
         return v;
     } else {
         return make_float4(0.f, 0.f, 0.f, 0.f);
@@ -263,56 +257,43 @@ __device__ __forceinline__ float4 promote_rebuild(float *elite, const int32_t *o
 
 __global__ __launch_bounds__(256) void ga_promote_kernel(GaPromoteArgs a)
 {
-    // (field-wise scalar selects: indexing the by-value argument array dynamically copies it to scratch)
     const unsigned y = blockIdx.y;
-#define PROMOTE_SEL(f) (y == 0 ? a.role[0].f : (y == 1 ? a.role[1].f : a.role[2].f))
-    float *pop = PROMOTE_SEL(pop), *hof = PROMOTE_SEL(hof), *elite = PROMOTE_SEL(elite);
-    const int32_t *order = PROMOTE_SEL(order);
-    const int D = PROMOTE_SEL(D), from_pop = PROMOTE_SEL(elites_from_pop), to_pop0 = PROMOTE_SEL(best_to_pop0);
-#undef PROMOTE_SEL
-    const int64_t stride = fc_stride(D);
+    const PromoteRole R = PROMOTE_ROLE(a, y);
+    float *pop = static_cast<float *>(R.pop), *hof = static_cast<float *>(R.hof), *elite = static_cast<float *>(R.elite);
+    const int64_t stride = fc_stride(R.D);
+    // (written out, not quad_first: through the function this kernel's instructions and SGPR count move)
     const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (s0 >= stride) return;
     // every source piece is read before the first store that could alias it (a best individual that already sits in
     // pop[0], the in-place HoF shift)
     float4 e0;
-    if (a.sigma && !from_pop) {
+    if (a.sigma && !R.from_pop) {
         uint32_t shi = a.stream_hi_prev + y;
         if (a.gen_dev) shi += 4u * (uint32_t)(*a.gen_dev - 1);
-        e0 = promote_rebuild<0>(elite, order, stride, s0, a.E, D, a.sigma[y], a.seed, shi);
+        e0 = promote_rebuild<0>(elite, R.order, stride, s0, a.E, R.D, a.sigma[y], a.seed, shi);
     } else {
-        e0 = from_pop ? promote_elites<0>(pop, order, elite, true, stride, s0, a.E)
-                      : *reinterpret_cast<const float4 *>(elite + s0);
+        e0 = R.from_pop ? promote_elites<0>(pop, R.order, elite, stride, s0, a.E)
+                        : *reinterpret_cast<const float4 *>(elite + s0);
     }
     promote_hof_shift<1>(hof, stride, s0, a.hof);
     *reinterpret_cast<float4 *>(hof + (int64_t)(a.hof - 1) * stride + s0) = e0;
-    if (to_pop0) *reinterpret_cast<float4 *>(pop + s0) = e0;
+    if (R.to_pop0) *reinterpret_cast<float4 *>(pop + s0) = e0;
     // the generation counter's tick (coevo_ga_promote_tick: only without gen_dev - no block of this launch reads the counter)
     if (a.tick && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.tick += 1;
 }
 
-// theta[p] += lr/(n*sigma) * sum_i fitness[i] * (pert_i[p] - theta[p]), i ascending, one fmaf per term.
-// The perturbation is read back from the materialised perturbed nets (one coalesced streaming pass over n*4P bytes)
-// instead of being regenerated: 0.3 ms instead of 2 ms per role at n = 1000.  LayerNorm entries are never perturbed
-// (their difference is exactly 0) and are skipped.
-__global__ __launch_bounds__(256) void es_update_kernel(float *theta, const float *pert_slab, int D,
-                                                         const float *fitness, int n, const float *sigma_dev, float lr)
+// sum over the individuals i = lo .. hi - 1, ascending, of fitness[i] * (pert_i - theta) at the thread's four slab positions,
+// one fmaf per term starting from 0; pp = the thread's quad of individual 0, the nets `stride` floats apart.
+// The perturbed nets are read exactly once: non-temporal, and 16 rows in flight per lane (only stride/1024 = 137
+// workgroups exist per chunk - the sum over i is sequential by definition - so the memory-level parallelism comes from depth)
+__device__ __forceinline__ float4 es_chunk_sum(float4 tv, const float *pp, int64_t stride, const float *fitness, int lo, int hi)
 {
-    const int64_t stride = fc_stride(D), P = fc_params(D);
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (s0 >= stride) return;
-    const float sigma = *sigma_dev;
-    const float scale = lr / ((float)n * sigma);
-    const float4 tv = *reinterpret_cast<const float4 *>(theta + s0);
     const float th[4] = {tv.x, tv.y, tv.z, tv.w};
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    const float *pp = pert_slab + s0;
-    int i = 0;
-    // the perturbed nets are read exactly once: non-temporal, and 16 rows in flight per lane (only stride/1024 = 137
-    // workgroups exist - the sum over i is sequential by definition - so the memory-level parallelism comes from depth)
     typedef float f32x4_nt __attribute__((ext_vector_type(4)));
     constexpr int UE = 16;
-    for (; i + UE <= n; i += UE) {
+    int i = lo;
+    for (; i + UE <= hi; i += UE) {
         float4 pv[UE];
 #pragma unroll
         for (int u = 0; u < UE; ++u) {
@@ -328,7 +309,7 @@ __global__ __launch_bounds__(256) void es_update_kernel(float *theta, const floa
             acc[3] = __builtin_fmaf(f, pv[u].w - th[3], acc[3]);
         }
     }
-    for (; i < n; ++i) {
+    for (; i < hi; ++i) {
         const float4 pv = *reinterpret_cast<const float4 *>(pp + (int64_t)i * stride);
         const float f = fitness[i];
         acc[0] = __builtin_fmaf(f, pv.x - th[0], acc[0]);
@@ -336,13 +317,36 @@ __global__ __launch_bounds__(256) void es_update_kernel(float *theta, const floa
         acc[2] = __builtin_fmaf(f, pv.z - th[2], acc[2]);
         acc[3] = __builtin_fmaf(f, pv.w - th[3], acc[3]);
     }
+    return make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
+
+// the update's last step: theta + scale * sum at the four slab positions from s0, except where skip(s) keeps theta's word
+template <class Skip>
+__device__ __forceinline__ float4 es_step_quad(float4 tv, float4 av, float scale, int64_t s0, const Skip &skip)
+{
+    const float th[4] = {tv.x, tv.y, tv.z, tv.w}, acc[4] = {av.x, av.y, av.z, av.w};
     float out[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int64_t s = s0 + c;
-        out[c] = (s < P && !fc_slab_is_layernorm(s, D)) ? th[c] + scale * acc[c] : th[c];
-    }
-    *reinterpret_cast<float4 *>(theta + s0) = make_float4(out[0], out[1], out[2], out[3]);
+    for (int c = 0; c < 4; ++c) out[c] = skip(s0 + c) ? th[c] : th[c] + scale * acc[c];
+    return make_float4(out[0], out[1], out[2], out[3]);
+}
+
+// theta[p] += lr/(n*sigma) * sum_i fitness[i] * (pert_i[p] - theta[p]), i ascending, one fmaf per term.
+// The perturbation is read back from the materialised perturbed nets (one coalesced streaming pass over n*4P bytes)
+// instead of being regenerated: 0.3 ms instead of 2 ms per role at n = 1000.  LayerNorm entries are never perturbed
+// (their difference is exactly 0) and are skipped.
+__global__ __launch_bounds__(256) void es_update_kernel(float *theta, const float *pert_slab, int D,
+                                                         const float *fitness, int n, const float *sigma_dev, float lr)
+{
+    const int64_t stride = fc_stride(D), P = fc_params(D);
+    const int64_t s0 = quad_first(blockIdx.x);
+    if (s0 >= stride) return;
+    const float sigma = *sigma_dev;
+    const float scale = lr / ((float)n * sigma);
+    const float4 tv = *reinterpret_cast<const float4 *>(theta + s0);
+    const float4 av = es_chunk_sum(tv, pert_slab + s0, stride, fitness, 0, n);
+    *reinterpret_cast<float4 *>(theta + s0) =
+        es_step_quad(tv, av, scale, s0, [=](int64_t s) { return s >= P || fc_slab_is_layernorm(s, D); });
 }
 
 // K5 in two steps.  Step 1: partial[c][p] = sum over the individuals i of chunk c (global chunk gc = chunk_first + c
@@ -354,42 +358,13 @@ __global__ __launch_bounds__(256) void es_partial_kernel(const float *theta, con
                                                           int64_t stride, const float *fitness_all, int n_total,
                                                           int chunks_total, int chunk_first, float *partial)
 {
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const int64_t s0 = quad_first(blockIdx.x);
     if (s0 >= stride) return;
     const int gc = chunk_first + blockIdx.y;
     const int i_lo = (int)((int64_t)gc * n_total / chunks_total), i_hi = (int)((int64_t)(gc + 1) * n_total / chunks_total);
     const float4 tv = *reinterpret_cast<const float4 *>(theta + s0);
-    const float th[4] = {tv.x, tv.y, tv.z, tv.w};
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     const float *pp = pert_slab + s0 - (int64_t)ind_first * stride;  // indexed by the GLOBAL individual
-    typedef float f32x4_nt __attribute__((ext_vector_type(4)));
-    constexpr int UE = 16;
-    int i = i_lo;
-    for (; i + UE <= i_hi; i += UE) {
-        float4 pv[UE];
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            const f32x4_nt v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_nt *>(pp + (int64_t)(i + u) * stride));
-            pv[u] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-#pragma unroll
-        for (int u = 0; u < UE; ++u) {
-            const float f = fitness_all[i + u];
-            acc[0] = __builtin_fmaf(f, pv[u].x - th[0], acc[0]);
-            acc[1] = __builtin_fmaf(f, pv[u].y - th[1], acc[1]);
-            acc[2] = __builtin_fmaf(f, pv[u].z - th[2], acc[2]);
-            acc[3] = __builtin_fmaf(f, pv[u].w - th[3], acc[3]);
-        }
-    }
-    for (; i < i_hi; ++i) {
-        const float4 pv = *reinterpret_cast<const float4 *>(pp + (int64_t)i * stride);
-        const float f = fitness_all[i];
-        acc[0] = __builtin_fmaf(f, pv.x - th[0], acc[0]);
-        acc[1] = __builtin_fmaf(f, pv.y - th[1], acc[1]);
-        acc[2] = __builtin_fmaf(f, pv.z - th[2], acc[2]);
-        acc[3] = __builtin_fmaf(f, pv.w - th[3], acc[3]);
-    }
-    *reinterpret_cast<float4 *>(partial + (int64_t)blockIdx.y * stride + s0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    *reinterpret_cast<float4 *>(partial + (int64_t)blockIdx.y * stride + s0) = es_chunk_sum(tv, pp, stride, fitness_all, i_lo, i_hi);
 }
 
 // partial of global chunk c lives at partials + (c / chunks_per_block) * block_stride + (c % chunks_per_block) * stride
@@ -407,7 +382,7 @@ __global__ __launch_bounds__(256) void es_apply_kernel(float *theta, const float
                                                         int chunks_per_block, int64_t block_stride, int64_t stride,
                                                         SlabSkip skip, int n_total, const float *sigma_dev, float lr)
 {
-    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const int64_t s0 = quad_first(blockIdx.x);
     if (s0 >= stride) return;
     const float sigma = *sigma_dev;
     const float scale = lr / ((float)n_total * sigma);
@@ -418,14 +393,7 @@ __global__ __launch_bounds__(256) void es_apply_kernel(float *theta, const float
         tot.x = tot.x + v.x; tot.y = tot.y + v.y; tot.z = tot.z + v.z; tot.w = tot.w + v.w;
     }
     const float4 tv = *reinterpret_cast<const float4 *>(theta + s0);
-    const float th[4] = {tv.x, tv.y, tv.z, tv.w}, ac[4] = {tot.x, tot.y, tot.z, tot.w};
-    float out[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int64_t s = s0 + c;
-        out[c] = skip(s) ? th[c] : th[c] + scale * ac[c];
-    }
-    *reinterpret_cast<float4 *>(theta + s0) = make_float4(out[0], out[1], out[2], out[3]);
+    *reinterpret_cast<float4 *>(theta + s0) = es_step_quad(tv, tot, scale, s0, skip);
 }
 
 __global__ __launch_bounds__(256) void fc_pack_kernel(const float *flat, float *slab, int D, bool to_slab)
@@ -444,8 +412,6 @@ __global__ __launch_bounds__(256) void fc_pack_kernel(const float *flat, float *
 }  // namespace coevo
 
 using namespace coevo;
-
-static bool fc_dim_ok(int D) { return D == 8 || D == 10; }
 
 extern "C" int64_t coevo_fc_param_count(int D) { return fc_dim_ok(D) ? fc_params(D) : COEVO_ERR_ARG; }
 extern "C" int64_t coevo_fc_slab_stride(int D) { return fc_dim_ok(D) ? fc_stride(D) : COEVO_ERR_ARG; }
@@ -469,10 +435,32 @@ extern "C" int coevo_fc_unpack(const float *slab, float *flat, int n, int D, voi
     return COEVO_OK;
 }
 
+extern "C" int64_t coevo_fc_perturb_blocks(int D) { return fc_dim_ok(D) ? (int64_t)quad_blocks(fc_stride(D)) : COEVO_ERR_ARG; }
+
+// what one breeding job (the arguments of one coevo_fc_perturb_dist call) must satisfy
+static bool perturb_job_ok(const coevo_fc_perturb_job &j)
+{
+    if ((j.dist_ref == nullptr) != (j.dist_partial == nullptr)) return false;
+    if (!j.parent_slab || !j.parent_idx || !j.child_slab || !j.sigma_dev || !fc_dim_ok(j.D)) return false;
+    return j.n_children >= 0 && j.child_first >= 0 && j.n_children <= 65535;
+}
+
 extern "C" int coevo_fc_perturb_dist(const float *parent_slab, const int32_t *parent_idx, float *child_slab,
                                      int child_first, int n_children, int D, const float *sigma_dev, uint64_t seed,
                                      uint32_t stream_lo_first, uint32_t stream_hi, int skip_layernorm,
-                                     const int32_t *gen_dev, const float *dist_ref, double *dist_partial, void *stream);
+                                     const int32_t *gen_dev, const float *dist_ref, double *dist_partial, void *stream)
+{
+    const coevo_fc_perturb_job j{parent_slab, parent_idx, child_slab, sigma_dev, dist_ref, dist_partial,
+                                 child_first, n_children, D, stream_lo_first, stream_hi, 0};
+    if (!perturb_job_ok(j) || skip_layernorm < 0 || skip_layernorm > 3) return COEVO_ERR_ARG;
+    if (n_children == 0) return COEVO_OK;
+    const dim3 grid(quad_blocks(fc_stride(D)), (unsigned)n_children);
+    hipLaunchKernelGGL(fc_perturb_kernel, grid, dim3(256), 0, (hipStream_t)stream, parent_slab, parent_idx,
+                       child_slab, child_first, D, sigma_dev, seed, stream_lo_first, stream_hi, skip_layernorm, gen_dev,
+                       dist_ref, dist_partial);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
 
 extern "C" int coevo_fc_perturb(const float *parent_slab, const int32_t *parent_idx, float *child_slab,
                                 int child_first, int n_children, int D, const float *sigma_dev, uint64_t seed,
@@ -500,26 +488,6 @@ extern "C" int coevo_fc_perturb_flags(const float *parent_slab, const int32_t *p
                                  stream_lo_first, stream_hi, flags, nullptr, nullptr, nullptr, stream);
 }
 
-extern "C" int64_t coevo_fc_perturb_blocks(int D) { return fc_dim_ok(D) ? (fc_stride(D) / 4 + 255) / 256 : COEVO_ERR_ARG; }
-
-extern "C" int coevo_fc_perturb_dist(const float *parent_slab, const int32_t *parent_idx, float *child_slab,
-                                     int child_first, int n_children, int D, const float *sigma_dev, uint64_t seed,
-                                     uint32_t stream_lo_first, uint32_t stream_hi, int skip_layernorm,
-                                     const int32_t *gen_dev, const float *dist_ref, double *dist_partial, void *stream)
-{
-    if ((dist_ref == nullptr) != (dist_partial == nullptr)) return COEVO_ERR_ARG;
-    if (!parent_slab || !parent_idx || !child_slab || !sigma_dev || !fc_dim_ok(D)) return COEVO_ERR_ARG;
-    if (n_children < 0 || child_first < 0 || n_children > 65535 || skip_layernorm < 0 || skip_layernorm > 3)
-        return COEVO_ERR_ARG;
-    if (n_children == 0) return COEVO_OK;
-    const dim3 grid((unsigned)((fc_stride(D) / 4 + 255) / 256), (unsigned)n_children);
-    hipLaunchKernelGGL(fc_perturb_kernel, grid, dim3(256), 0, (hipStream_t)stream, parent_slab, parent_idx,
-                       child_slab, child_first, D, sigma_dev, seed, stream_lo_first, stream_hi, skip_layernorm, gen_dev,
-                       dist_ref, dist_partial);
-    COEVO_HIP_CHECK(hipGetLastError());
-    return COEVO_OK;
-}
-
 extern "C" int coevo_fc_perturb_dist_multi(const coevo_fc_perturb_job *jobs, int n_jobs, uint64_t seed, int skip_layernorm,
                                            const int32_t *gen_dev, void *stream)
 {
@@ -528,11 +496,9 @@ extern "C" int coevo_fc_perturb_dist_multi(const coevo_fc_perturb_job *jobs, int
     unsigned gx = 0, gy = 0;
     for (int i = 0; i < n_jobs; ++i) {
         const coevo_fc_perturb_job &j = jobs[i];
-        if ((j.dist_ref == nullptr) != (j.dist_partial == nullptr)) return COEVO_ERR_ARG;
-        if (!j.parent_slab || !j.parent_idx || !j.child_slab || !j.sigma_dev || !fc_dim_ok(j.D)) return COEVO_ERR_ARG;
-        if (j.n_children < 0 || j.child_first < 0 || j.n_children > 65535) return COEVO_ERR_ARG;
+        if (!perturb_job_ok(j)) return COEVO_ERR_ARG;
         pj.j[i] = j;
-        const unsigned nb = (unsigned)((fc_stride(j.D) / 4 + 255) / 256);
+        const unsigned nb = quad_blocks(fc_stride(j.D));
         gx = nb > gx ? nb : gx;
         gy = (unsigned)j.n_children > gy ? (unsigned)j.n_children : gy;
     }
@@ -550,9 +516,24 @@ extern "C" int coevo_fc_rebuild_elites(const float *elite_prev, const int32_t *o
     if (!elite_prev || !order || !elite_new || !sigma_prev_dev || !fc_dim_ok(D) || E <= 0 || E > 65535)
         return COEVO_ERR_ARG;
     if (elite_prev == elite_new) return COEVO_ERR_ARG;  // elite e reads several previous elites: never in place
-    const dim3 grid((unsigned)((fc_stride(D) / 4 + 255) / 256), (unsigned)E);
+    const dim3 grid(quad_blocks(fc_stride(D)), (unsigned)E);
     hipLaunchKernelGGL(fc_rebuild_elites_kernel, grid, dim3(256), 0, (hipStream_t)stream, elite_prev, order, elite_new,
                        E, D, sigma_prev_dev, seed, stream_hi_prev, gen_dev);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+/* dst[dst_first + i] = src[src_idx[i]] for nets of any layout (stride floats apart, a multiple of 4) */
+extern "C" int coevo_net_gather(const float *src_slab, const int32_t *src_idx, float *dst_slab, int dst_first, int n,
+                                int64_t stride_floats, void *stream)
+{
+    if (!src_slab || !src_idx || !dst_slab || n < 0 || dst_first < 0 || n > 65535 || stride_floats <= 0 ||
+        (stride_floats & 3))
+        return COEVO_ERR_ARG;
+    if (n == 0) return COEVO_OK;
+    const dim3 grid(quad_blocks(stride_floats), (unsigned)n);
+    hipLaunchKernelGGL(fc_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, src_slab, src_idx, dst_slab,
+                       dst_first, stride_floats);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }
@@ -562,16 +543,21 @@ extern "C" int coevo_fc_gather(const float *src_slab, const int32_t *src_idx, fl
 {
     if (!src_slab || !src_idx || !dst_slab || !fc_dim_ok(D) || n < 0 || dst_first < 0 || n > 65535)
         return COEVO_ERR_ARG;
-    if (n == 0) return COEVO_OK;
-    const dim3 grid((unsigned)((fc_stride(D) / 4 + 255) / 256), (unsigned)n);
-    hipLaunchKernelGGL(fc_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, src_slab, src_idx, dst_slab,
-                       dst_first, fc_stride(D));
-    COEVO_HIP_CHECK(hipGetLastError());
-    return COEVO_OK;
+    return coevo_net_gather(src_slab, src_idx, dst_slab, dst_first, n, fc_stride(D), stream);
 }
 
 static int ga_promote_launch(const coevo_ga_promote_role *roles, int n_roles, int E, int hof, const float *sigma,
-                             uint64_t seed, uint32_t stream_hi_prev, const int32_t *gen_dev, int32_t *tick, void *stream);
+                             uint64_t seed, uint32_t stream_hi_prev, const int32_t *gen_dev, int32_t *tick, void *stream)
+{
+    GaPromoteArgs a{};
+    if (!promote_roles(a, roles, n_roles, E, hof, false)) return COEVO_ERR_ARG;
+    a.sigma = sigma; a.seed = seed; a.stream_hi_prev = stream_hi_prev; a.gen_dev = gen_dev; a.tick = tick;
+    unsigned max_blocks = 0;
+    for (int r = 0; r < n_roles; ++r) max_blocks = std::max(max_blocks, quad_blocks(fc_stride(roles[r].D)));
+    hipLaunchKernelGGL(ga_promote_kernel, dim3(max_blocks, (unsigned)n_roles), dim3(256), 0, (hipStream_t)stream, a);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
 
 extern "C" int coevo_ga_promote(const coevo_ga_promote_role *roles, int n_roles, int E, int hof, void *stream)
 {
@@ -602,32 +588,11 @@ extern "C" int coevo_ga_promote_rebuild(const coevo_ga_promote_role *roles, int 
     return ga_promote_launch(roles, n_roles, E, hof, sigma, seed, stream_hi_prev, gen_dev, nullptr, stream);
 }
 
-static int ga_promote_launch(const coevo_ga_promote_role *roles, int n_roles, int E, int hof, const float *sigma,
-                             uint64_t seed, uint32_t stream_hi_prev, const int32_t *gen_dev, int32_t *tick, void *stream)
-{
-    if (!roles || n_roles < 1 || n_roles > 3 || E < 1 || E > PROMOTE_MAX_E || hof < 1 || hof > PROMOTE_MAX_HOF)
-        return COEVO_ERR_ARG;
-    GaPromoteArgs a{};
-    a.sigma = sigma; a.seed = seed; a.stream_hi_prev = stream_hi_prev; a.gen_dev = gen_dev; a.tick = tick;
-    int64_t max_stride = 0;
-    for (int r = 0; r < n_roles; ++r) {
-        const coevo_ga_promote_role &R = roles[r];
-        if (!R.pop || !R.hof || !R.elite || !fc_dim_ok(R.D) || (R.elites_from_pop && !R.order)) return COEVO_ERR_ARG;
-        a.role[r] = R;
-        if (fc_stride(R.D) > max_stride) max_stride = fc_stride(R.D);
-    }
-    a.E = E; a.hof = hof;
-    const dim3 grid((unsigned)((max_stride / 4 + 255) / 256), (unsigned)n_roles);
-    hipLaunchKernelGGL(ga_promote_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    COEVO_HIP_CHECK(hipGetLastError());
-    return COEVO_OK;
-}
-
 extern "C" int coevo_es_update(float *theta_slab_net, const float *pert_slab, int D, const float *fitness, int n,
                                const float *sigma_dev, float lr, void *stream)
 {
     if (!theta_slab_net || !pert_slab || !fitness || !sigma_dev || !fc_dim_ok(D) || n <= 0) return COEVO_ERR_ARG;
-    const dim3 grid((unsigned)((fc_stride(D) / 4 + 255) / 256));
+    const dim3 grid(quad_blocks(fc_stride(D)));
     hipLaunchKernelGGL(es_update_kernel, grid, dim3(256), 0, (hipStream_t)stream, theta_slab_net, pert_slab, D,
                        fitness, n, sigma_dev, lr);
     COEVO_HIP_CHECK(hipGetLastError());
@@ -644,7 +609,7 @@ static int es_partial_launch(const float *theta_net, const float *pert_slab_loca
         return COEVO_ERR_ARG;
     // the caller's nets must start exactly where its first chunk starts
     if ((int64_t)chunk_first * n_total / chunks_total != ind_first) return COEVO_ERR_ARG;
-    const dim3 grid((unsigned)((stride / 4 + 255) / 256), (unsigned)n_chunks);
+    const dim3 grid(quad_blocks(stride), (unsigned)n_chunks);
     hipLaunchKernelGGL(es_partial_kernel, grid, dim3(256), 0, (hipStream_t)stream, theta_net, pert_slab_local, ind_first,
                        stride, fitness_all, n_total, chunks_total, chunk_first, partial);
     COEVO_HIP_CHECK(hipGetLastError());
@@ -658,7 +623,7 @@ static int es_apply_launch(float *theta_net, const float *partials, int chunks_t
     if (!theta_net || !partials || !sigma_dev || n_total <= 0 || chunks_total <= 0 || chunks_per_block <= 0 ||
         block_stride_floats < 0 || (block_stride_floats & 3))
         return COEVO_ERR_ARG;
-    const dim3 grid((unsigned)((stride / 4 + 255) / 256));
+    const dim3 grid(quad_blocks(stride));
     hipLaunchKernelGGL(es_apply_kernel, grid, dim3(256), 0, (hipStream_t)stream, theta_net, partials, chunks_total,
                        chunks_per_block, block_stride_floats, stride, skip, n_total, sigma_dev, lr);
     COEVO_HIP_CHECK(hipGetLastError());
@@ -679,19 +644,17 @@ extern "C" int coevo_es_apply(float *theta_net, const float *partials, int chunk
                               void *stream)
 {
     if (!fc_dim_ok(D)) return COEVO_ERR_ARG;
-    const int64_t g1 = fc_off_b1(D) + H1, g2 = fc_off_b2(D) + H2;  // LayerNorm affine: never perturbed, never updated
+    const int64_t g1 = fc_off_g1(D), g2 = fc_off_g2(D);  // LayerNorm affine: never perturbed, never updated
     const SlabSkip skip{fc_params(D), g1, g1 + 2 * H1, g2, g2 + 2 * H2, 0, 0};
     return es_apply_launch(theta_net, partials, chunks_total, chunks_per_block, block_stride_floats, fc_stride(D), skip,
                            n_total, sigma_dev, lr, stream);
 }
 
-static bool dqn_ok(int C, int n) { return C >= 1 && C <= 6 && n >= 1 && n <= COEVO_DQN_LOGIT_STRIDE; }
-
 extern "C" int coevo_dqn_es_partial(const float *theta_net, const float *pert_slab_local, int ind_first, int C,
                                     int n_actions, const float *fitness_all, int n_total, int chunks_total,
                                     int chunk_first, int n_chunks, float *partial, void *stream)
 {
-    if (!dqn_ok(C, n_actions)) return COEVO_ERR_ARG;
+    if (!dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;
     return es_partial_launch(theta_net, pert_slab_local, ind_first, dqn_layout(C, n_actions).stride, fitness_all,
                              n_total, chunks_total, chunk_first, n_chunks, partial, stream);
 }
@@ -700,28 +663,12 @@ extern "C" int coevo_dqn_es_apply(float *theta_net, const float *partials, int c
                                   int64_t block_stride_floats, int C, int n_actions, int n_total,
                                   const float *sigma_dev, float lr, void *stream)
 {
-    if (!dqn_ok(C, n_actions)) return COEVO_ERR_ARG;
+    if (!dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;
     const DqnLayout L = dqn_layout(C, n_actions);  // BatchNorm affine is not perturbable (Atari/deepqn.py:158-171)
     const SlabSkip skip{L.total, L.b1 + 32, L.w2, L.b2 + 64, L.w3, L.b3 + 64, L.wf};
     return es_apply_launch(theta_net, partials, chunks_total, chunks_per_block, block_stride_floats, L.stride, skip,
                            n_total, sigma_dev, lr, stream);
 }
-
-/* dst[dst_first + i] = src[src_idx[i]] for nets of any layout (stride floats apart, a multiple of 4) */
-extern "C" int coevo_net_gather(const float *src_slab, const int32_t *src_idx, float *dst_slab, int dst_first, int n,
-                                int64_t stride_floats, void *stream)
-{
-    if (!src_slab || !src_idx || !dst_slab || n < 0 || dst_first < 0 || n > 65535 || stride_floats <= 0 ||
-        (stride_floats & 3))
-        return COEVO_ERR_ARG;
-    if (n == 0) return COEVO_OK;
-    const dim3 grid((unsigned)((stride_floats / 4 + 255) / 256), (unsigned)n);
-    hipLaunchKernelGGL(fc_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, src_slab, src_idx, dst_slab,
-                       dst_first, stride_floats);
-    COEVO_HIP_CHECK(hipGetLastError());
-    return COEVO_OK;
-}
-
 
 // ---- the noise contract, exposed: the round count and the generator itself (raw words and the Gaussians built from them),
 // so that a binding / a resumed run can check what it is loading and the tests can hold the generator against published

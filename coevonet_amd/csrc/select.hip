@@ -16,7 +16,8 @@ __global__ __launch_bounds__(256) void fc_distance_kernel(const float *ref_net, 
 {
     __shared__ double scratch[4];
     const int64_t stride = fc_stride(D), P = fc_params(D);
-    const int64_t g1 = fc_off_b1(D) + H1, g2 = fc_off_b2(D) + H2;
+    // (fc_slab_is_layernorm written out with its bounds hoisted: through the function the kernel's register count moves)
+    const int64_t g1 = fc_off_g1(D), g2 = fc_off_g2(D);
     const float *wi = pop_slab + (int64_t)blockIdx.x * stride;
     double acc = 0.0;
     for (int64_t s0 = (int64_t)threadIdx.x * 4; s0 < stride; s0 += 1024) {
@@ -43,12 +44,9 @@ __global__ __launch_bounds__(256) void fc_distance_kernel(const float *ref_net, 
 __global__ __launch_bounds__(64) void dist_finalize_kernel(const double *partial, int n_blocks, float *dist, int first,
                                                             const float *head)
 {
-    const int c = blockIdx.x, l = threadIdx.x;
-    double v = 0.0;
-    for (int b = l; b < n_blocks; b += 64) v += partial[(size_t)c * n_blocks + b];
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
-    if (l == 0) {
+    const int c = blockIdx.x;
+    const double v = wave_sum_partials(partial + (size_t)c * n_blocks, n_blocks);
+    if (threadIdx.x == 0) {
         dist[first + c] = (float)sqrt(v);
         if (c == 0 && head) dist[first - 1] = *head;
     }
@@ -63,10 +61,7 @@ __global__ __launch_bounds__(64) void dist_finalize_multi_kernel(FinalizeJobs jo
     // (the generation counter's tick rides in the generation's last launch: nothing in this launch reads it)
     if (tick && blockIdx.x == 0 && blockIdx.y == 0 && l == 0) *tick += 1;
     if (c >= jb.n) return;
-    double v = 0.0;
-    for (int b = l; b < jb.n_blocks; b += 64) v += jb.dist_partial[(size_t)c * jb.n_blocks + b];
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
+    const double v = wave_sum_partials(jb.dist_partial + (size_t)c * jb.n_blocks, jb.n_blocks);
     if (l == 0) {
         jb.dist[jb.first + c] = (float)sqrt(v);
         if (c == 0 && jb.head) jb.dist[jb.first - 1] = *jb.head;
@@ -320,7 +315,7 @@ extern "C" int coevo_counter_add(int32_t *counter, int value, void *stream)
 extern "C" int coevo_fc_diversity(const float *ref_net, const float *pop_slab, int n, int D, float *dist,
                                   float *score, void *stream)
 {
-    if (!ref_net || !pop_slab || !dist || !score || n <= 0 || (D != 8 && D != 10)) return COEVO_ERR_ARG;
+    if (!ref_net || !pop_slab || !dist || !score || n <= 0 || !fc_dim_ok(D)) return COEVO_ERR_ARG;
     hipLaunchKernelGGL(fc_distance_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ref_net, pop_slab, D, dist);
     hipLaunchKernelGGL(sharing_score_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, dist, n, score);
     COEVO_HIP_CHECK(hipGetLastError());
@@ -329,7 +324,7 @@ extern "C" int coevo_fc_diversity(const float *ref_net, const float *pop_slab, i
 
 extern "C" int coevo_fc_distance(const float *ref_net, const float *pop_slab, int n, int D, float *dist, void *stream)
 {
-    if (!ref_net || !pop_slab || !dist || n <= 0 || (D != 8 && D != 10)) return COEVO_ERR_ARG;
+    if (!ref_net || !pop_slab || !dist || n <= 0 || !fc_dim_ok(D)) return COEVO_ERR_ARG;
     hipLaunchKernelGGL(fc_distance_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ref_net, pop_slab, D, dist);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
@@ -343,20 +338,6 @@ extern "C" int coevo_fc_distance_finalize(const double *partial, int n_blocks, i
                        head);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
-}
-
-static int finalize_multi_launch(const coevo_fc_finalize_job *jobs, int n_jobs, int32_t *tick, void *stream);
-
-extern "C" int coevo_fc_distance_finalize_multi(const coevo_fc_finalize_job *jobs, int n_jobs, void *stream)
-{
-    return finalize_multi_launch(jobs, n_jobs, nullptr, stream);
-}
-
-// ... with the generation counter's tick (coevo_counter_add(counter, 1)) in the same launch: the last launch of a generation
-extern "C" int coevo_fc_distance_finalize_multi_tick(const coevo_fc_finalize_job *jobs, int n_jobs, int32_t *counter, void *stream)
-{
-    if (!counter) return COEVO_ERR_ARG;
-    return finalize_multi_launch(jobs, n_jobs, counter, stream);
 }
 
 static int finalize_multi_launch(const coevo_fc_finalize_job *jobs, int n_jobs, int32_t *tick, void *stream)
@@ -374,6 +355,18 @@ static int finalize_multi_launch(const coevo_fc_finalize_job *jobs, int n_jobs, 
     hipLaunchKernelGGL(dist_finalize_multi_kernel, dim3(nmax > 0 ? nmax : 1, n_jobs), dim3(64), 0, (hipStream_t)stream, fj, tick);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
+}
+
+extern "C" int coevo_fc_distance_finalize_multi(const coevo_fc_finalize_job *jobs, int n_jobs, void *stream)
+{
+    return finalize_multi_launch(jobs, n_jobs, nullptr, stream);
+}
+
+// ... with the generation counter's tick (coevo_counter_add(counter, 1)) in the same launch: the last launch of a generation
+extern "C" int coevo_fc_distance_finalize_multi_tick(const coevo_fc_finalize_job *jobs, int n_jobs, int32_t *counter, void *stream)
+{
+    if (!counter) return COEVO_ERR_ARG;
+    return finalize_multi_launch(jobs, n_jobs, counter, stream);
 }
 
 extern "C" int coevo_gather_f32(float *dst, const float *src, const int32_t *idx, int n, void *stream)
@@ -413,7 +406,27 @@ extern "C" int coevo_rank_desc(const float *fitness, int n, int32_t *order, void
 }
 
 static int ga_select_launch(const coevo_ga_select_role *roles, int n_roles, int pop, int games_per_individual, int hof,
-                            const double *gathered, int n_local, const coevo_ga_adapt_args *adapt, void *stream);
+                            const double *gathered, int n_local, const coevo_ga_adapt_args *adapt, void *stream)
+{
+    if (!roles || n_roles < 1 || n_roles > 3 || pop <= 0 || pop > 4096 || hof <= 0 || games_per_individual <= 0)
+        return COEVO_ERR_ARG;
+    coevo::GaSelectArgs a{};
+    for (int r = 0; r < n_roles; ++r) {
+        const coevo_ga_select_role &R = roles[r];
+        if ((!gathered && (!R.dist || !R.rewards)) || !R.diversity || !R.fitness || !R.order || R.slot < 0 || R.slot > 2 ||
+            R.game_first < 0)
+            return COEVO_ERR_ARG;
+        a.role[r] = R;
+    }
+    a.gathered = gathered; a.n_local = n_local; a.n_roles = n_roles;
+    a.pop = pop; a.games_per_individual = games_per_individual; a.hof = hof;
+    a.n_roles_launched = n_roles;
+    if (adapt) { a.adapt = *adapt; a.with_adapt = 1; }
+    hipLaunchKernelGGL(coevo::ga_select_kernel, dim3(n_roles + (adapt ? 1 : 0), (pop + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
 
 extern "C" int coevo_ga_select(const coevo_ga_select_role *roles, int n_roles, int pop, int games_per_individual,
                                int hof, void *stream)
@@ -443,29 +456,6 @@ extern "C" int coevo_ga_select_gathered(const coevo_ga_select_role *roles, int n
 {
     if (!gathered || n_local <= 0 || pop % n_local) return COEVO_ERR_ARG;
     return ga_select_launch(roles, n_roles, pop, 1, hof, gathered, n_local, nullptr, stream);
-}
-
-static int ga_select_launch(const coevo_ga_select_role *roles, int n_roles, int pop, int games_per_individual, int hof,
-                            const double *gathered, int n_local, const coevo_ga_adapt_args *adapt, void *stream)
-{
-    if (!roles || n_roles < 1 || n_roles > 3 || pop <= 0 || pop > 4096 || hof <= 0 || games_per_individual <= 0)
-        return COEVO_ERR_ARG;
-    coevo::GaSelectArgs a{};
-    for (int r = 0; r < n_roles; ++r) {
-        const coevo_ga_select_role &R = roles[r];
-        if ((!gathered && (!R.dist || !R.rewards)) || !R.diversity || !R.fitness || !R.order || R.slot < 0 || R.slot > 2 ||
-            R.game_first < 0)
-            return COEVO_ERR_ARG;
-        a.role[r] = R;
-    }
-    a.gathered = gathered; a.n_local = n_local; a.n_roles = n_roles;
-    a.pop = pop; a.games_per_individual = games_per_individual; a.hof = hof;
-    a.n_roles_launched = n_roles;
-    if (adapt) { a.adapt = *adapt; a.with_adapt = 1; }
-    hipLaunchKernelGGL(coevo::ga_select_kernel, dim3(n_roles + (adapt ? 1 : 0), (pop + 255) / 256), dim3(256), 0,
-                       (hipStream_t)stream, a);
-    COEVO_HIP_CHECK(hipGetLastError());
-    return COEVO_OK;
 }
 
 extern "C" int coevo_version(void) { return COEVO_VERSION; }

@@ -11,6 +11,7 @@ import torch
 from coevonet_amd import lib as L
 from coevonet_amd.ga_half import HalfGAEngine
 from oracle import ref_port as rp
+from tests import breed_cases as bc
 from tests import ga16_checker as gk
 from tests.test_fp16_gpu import random_flat
 from tests.util import sha
@@ -327,6 +328,102 @@ def test_gather_and_promote_against_numpy(E, hof):
         want = dst.copy()
         want[2:5] = src[[3, 0, 3]]
         assert np.array_equal(td.cpu().numpy(), want)
+
+
+# ---------------------------------------------------------------------------------------------- promotion and gather, corners
+# coevo_ga16_promote is coevo_ga_promote on 16-byte pieces of fp16 slabs (the same compile-time recursions, role selection and
+# host checks: csrc/promote_roles.hip.h; tests/test_breed_edges_gpu.py holds the fp32 launch), and coevo_fc16_gather runs the
+# copy kernel of coevo_net_gather: the fp32 suite's corners here, on raw 32-bit words compared as integers, against list
+# operations - never against the fp32 launch.
+ROLE_D16 = (10, 10, 8)
+GUARD = 0x5A5A5A5A
+
+
+class Region16:
+    """n fp16-slab nets of raw words between one guard net on each side.  Net i carries, besides random words, an fp32 NaN
+    whose halves are an fp16 NaN and an fp16 subnormal (0x7fc00001 + i), a negative one (0xffc00000 + i), an fp32 subnormal
+    (1 + i) and a pair of fp16 NaN halves (0x7e007e01 + i), each in every fifth word."""
+
+    def __init__(self, n, D, rng):
+        self.n, self.stride = n, L.fc16_slab_stride(D)
+        w = rng.integers(0, 2 ** 32, size=(n + 2, self.stride), dtype=np.uint64).astype(np.uint32)
+        for i in range(n):
+            for k, pattern in enumerate((0x7FC00001, 0xFFC00000, 1, 0x7E007E01)):
+                w[1 + i, k::5] = pattern + i
+        w[0] = w[-1] = GUARD
+        self.t = torch.from_numpy(w.view(np.int32)).to(DEV)
+        self.p = self.t.data_ptr() + 4 * self.stride
+        self.before = w[1:-1].copy()
+
+    def rows(self):
+        """-> the n nets as uint32 rows, after asserting the guard nets"""
+        a = self.t.cpu().numpy().view(np.uint32)
+        assert (a[0] == GUARD).all() and (a[-1] == GUARD).all(), "a guard net was written"
+        return a[1:-1]
+
+
+def promote16_case(E, hof, n_roles, variant):
+    n_pop = 10
+    rng = np.random.default_rng(1000 * E + 10 * hof + n_roles)
+    roles, checks = (L.GaPromoteRole * n_roles)(), []
+    for r in range(n_roles):
+        D = ROLE_D16[r]
+        kind = (r + variant) % 3
+        pop, hofs, elite = Region16(n_pop, D, rng), Region16(hof, D, rng), Region16(E, D, rng)
+        if kind == 0:      # the best already sits in pop[0] and is written back onto itself; the rest distinct
+            ids, from_pop, to_pop0 = [0] + list(1 + rng.permutation(n_pop - 1)[:E - 1]), 1, 1
+        elif kind == 1:    # pop's last net is the best, an id repeats, pop[0] is left alone
+            ids, from_pop, to_pop0 = [n_pop - 1] + [3] * (E - 1), 1, 0
+            if E > 2:
+                ids[2] = n_pop - 1
+        else:              # the elites are in place already: read, not written; no order at all
+            ids, from_pop, to_pop0 = None, 0, 1
+        order = dev_i32(ids) if ids is not None else None
+        roles[r] = L.GaPromoteRole(pop.p, hofs.p, elite.p, L._p(order), D, from_pop, to_pop0, 0)
+        checks.append((ids, from_pop, to_pop0, pop, hofs, elite, order))
+    L.call("coevo_ga16_promote", roles, n_roles, E, hof)
+    torch.cuda.synchronize()
+    for r, (ids, from_pop, to_pop0, pop, hofs, elite, _) in enumerate(checks):
+        want_p, want_h, want_e = bc.promote(list(pop.before), list(hofs.before), list(elite.before), ids, E, from_pop, to_pop0)
+        for name, got, want in (("pop", pop.rows(), want_p), ("hof", hofs.rows(), want_h), ("elite", elite.rows(), want_e)):
+            assert len(got) == len(want)
+            for k in range(len(want)):
+                assert np.array_equal(got[k], want[k]), (variant, r, name, k)
+
+
+@pytest.mark.parametrize("n_roles", [1, 2, 3])
+@pytest.mark.parametrize("E,hof", [(1, 1), (1, 16), (8, 1), (8, 16), (3, 2)])
+def test_promote16_corners_vs_list_operations(E, hof, n_roles):
+    """every (E, hof) corner of the compile-time recursions on fp16 slabs, one to three roles of mixed width (the D = 8 role's
+    surplus workgroup leaves without writing: its regions end in guard nets), the three aliasing kinds of the fp32 suite's
+    promote_case; words that are NaN or subnormal as fp32 and as fp16 halves travel as integers"""
+    for variant in range(3 if n_roles == 1 else 2):
+        promote16_case(E, hof, n_roles, variant)
+
+
+@pytest.mark.parametrize("D", [10, 8])
+def test_gather16_edges(D):
+    """coevo_fc16_gather: n = 0 writes nothing, a repeated index, dst_first > 0, every destination region between guard nets;
+    bad arguments return ERR_ARG and write nothing"""
+    rng = np.random.default_rng(40 + D)
+    lib, st = L.load(), L._stream()
+    src, dst = Region16(4, D, rng), Region16(6, D, rng)
+    idx = dev_i32([3, 0, 3, 1])
+    assert lib.coevo_fc16_gather(src.p, L._p(idx), dst.p, 2, 0, D, st) == 0
+    bad = [(None, L._p(idx), dst.p, 0, 1, D), (src.p, None, dst.p, 0, 1, D), (src.p, L._p(idx), None, 0, 1, D),
+           (src.p, L._p(idx), dst.p, 0, 1, 9), (src.p, L._p(idx), dst.p, 0, -1, D), (src.p, L._p(idx), dst.p, 0, 65536, D),
+           (src.p, L._p(idx), dst.p, -1, 1, D), (src.p + 4, L._p(idx), dst.p, 0, 1, D), (src.p, L._p(idx), dst.p + 8, 0, 1, D)]
+    for args in bad:
+        assert lib.coevo_fc16_gather(*args, st) == -1, args
+    torch.cuda.synchronize()
+    assert np.array_equal(dst.rows(), dst.before) and np.array_equal(src.rows(), src.before)
+    L.call("coevo_fc16_gather", src.p, L._p(idx), dst.p, 2, 4, D)      # dst[2 .. 5] = src[3, 0, 3, 1]: up to the guard net
+    L.call("coevo_fc16_gather", src.p, idx.data_ptr() + 4, dst.p, 0, 1, D)   # dst[0] = src[0]
+    torch.cuda.synchronize()
+    want = dst.before.copy()
+    want[2:6] = src.before[[3, 0, 3, 1]]
+    want[0] = src.before[0]
+    assert np.array_equal(dst.rows(), want) and np.array_equal(src.rows(), src.before)
 
 
 # ---------------------------------------------------------------------------------------------- whole generations
