@@ -1,0 +1,195 @@
+// Float16 Co-GA breeding on the fp16 DeepQN slab of dqn16_layout.hip.h: offspring with their stale-agent distance fused in, and
+// the distance of nets that are already in a slab.  The finalize is coevo_fc16_distance_finalize (fc16_offspring.hip: its
+// n_blocks is generic); gather, HoF push and elites are coevo_net_gather with the stride in words.
+//
+// Replaces, for args.precision == "float16" (reference file:line): AtariAgent.clone + Agent.mutate (Atari/atari_agent.py:27-30,
+// agent.py:25-29: half_param.data += torch.normal(0, sigma, size) for EVERY parameter - the BatchNorm affine is half in
+// DeepQN, Atari/deepqn.py:24-37) and np.linalg.norm(a16 - b16) of diversity_penalty on get_weights_ES() = all parameters
+// (utils/game_logic_functions.py:12-37).
+//
+// The float16 DeepQN breeding contract (DESIGN.md 6a "Float16 DeepQN breeding"):
+//   mutation   child = f16(f32(parent) + noise), noise = sigma * eps(seed, stream, p) rounded to fp32 first, p the canonical
+//              parameters() index (coevo_dqn_param_count's order): the number the fp32 child of the same stream draws
+//              (coevo_dqn_perturb).  Round to nearest even, past 65504 -> inf, fp16 subnormals kept.
+//   distance   per entry d = f16(f32(a) - f32(b)); d * d accumulated in fp64: the eight (or four) entries of a thread's 16-byte
+//              piece in slab order, then block_sum_f64; one partial per block of 256 pieces; the stride's padding is not
+//              counted.  dist = f16(sqrt(sum of the partials)) in one rounding (coevo_fc16_distance_finalize).
+// A thread owns ONE 16-byte piece of the net.  In the fc1 block ([8][392][64][8] halves, 91 % of the words) that is eight
+// consecutive canonical indices from a multiple of eight = two aligned Philox quads; everywhere else it is four fp32 words that
+// hold fp16 values and map through dqn16_word_to_flat - the conv weights sit in conv16_mfma's lane order, so such a piece can
+// need four Philox blocks (the last one is kept, as in the generic branch of dqn_perturb_kernel).
+#include <hip/hip_runtime.h>
+
+#include "dqn16_layout.hip.h"
+#include "fc16_layout.hip.h"
+#include "philox.hip.h"
+
+namespace coevo {
+
+// Left alone, hipcc folds f16(a + sigma * z) and f16(sigma * z) into v_fma_mix* forms, which round the exact sum once to fp16
+// and skip the fp32 rounding of the contract.  The empty statement makes the fp32 value a value of its own (f16r_after_fma of
+// dqn_conv.hip.h, es16_noise16 of fc16_es.hip).
+__device__ __forceinline__ float dq16_pin(float v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+// child entry = f16(f32(parent) + noise): the sum in fp32, rounded once to half
+__device__ __forceinline__ float dq16_child(float parent, float noise) { return f16r(dq16_pin(parent + dq16_pin(noise))); }
+
+__device__ __forceinline__ int dq16_pieces(const DqnLayout &L) { return (int)(L.stride >> 2); }
+__device__ __forceinline__ bool dq16_fc1_piece(int u, const DqnLayout &L) { return 4 * (int64_t)u >= L.wf && 4 * (int64_t)u < L.bf; }
+
+// squared distance of piece u of net a to the same piece of net b: the piece's entries in slab order, padding left out
+__device__ __forceinline__ double dq16_piece_d2(const uint4 &a, const uint4 &b, int u, const DqnLayout &L)
+{
+    double d2 = 0.0;
+    if (dq16_fc1_piece(u, L)) {
+        _Float16 ha[8], hb[8];
+        __builtin_memcpy(ha, &a, sizeof(ha));
+        __builtin_memcpy(hb, &b, sizeof(hb));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float d = f16r(dq16_pin(dq16_pin((float)ha[i]) - dq16_pin((float)hb[i])));
+            d2 += (double)d * (double)d;
+        }
+    } else {
+        float fa[4], fb[4];
+        __builtin_memcpy(fa, &a, sizeof(fa));
+        __builtin_memcpy(fb, &b, sizeof(fb));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (4 * (int64_t)u + i < L.total) {   // dqn16_word_to_flat >= 0
+                const float d = f16r(dq16_pin(fa[i] - fb[i]));
+                d2 += (double)d * (double)d;
+            }
+        }
+    }
+    return d2;
+}
+
+// grid (coevo_dqn16_perturb_blocks, n_children): workgroup (bx, c) writes pieces 256 bx .. 256 bx + 255 of child c
+__global__ __launch_bounds__(256) void dqn16_perturb_dist_kernel(const uint32_t *parent_slab, const int32_t *parent_idx,
+                                                                  uint32_t *child_slab, int child_first, int C, int n_actions,
+                                                                  const float *sigma_dev, uint64_t seed,
+                                                                  uint32_t stream_lo_first, uint32_t stream_hi, int flags,
+                                                                  const int32_t *gen_dev, int gen_bias,
+                                                                  const uint32_t *dist_ref, double *dist_partial)
+{
+    __shared__ double scratch[4];
+    if (gen_dev) stream_hi += 4u * (uint32_t)(*gen_dev + gen_bias);   // generation-indexed noise stream without a host argument
+    const int c = blockIdx.y, bx = blockIdx.x;
+    const uint32_t slo = stream_lo_first + (uint32_t)c;
+    const DqnLayout L = dqn16_layout(C, n_actions);
+    const int u = bx * 256 + (int)threadIdx.x;
+    double d2 = 0.0;
+    if (u < dq16_pieces(L)) {
+        const uint4 pv = reinterpret_cast<const uint4 *>(parent_slab + (int64_t)parent_idx[c] * L.stride)[u];
+        uint4 ov = pv;
+        if (!(flags & COEVO_DQP_COPY)) {
+            const float sigma = *sigma_dev;
+            if (dq16_fc1_piece(u, L)) {
+                // piece (ob, o, l) = fc1.w[64 ob + l][8 o .. 8 o + 7]: never BatchNorm, never padding
+                const int t = u - (int)(L.wf >> 2), l = t & 63, o = (t >> 6) % DQ16_OCTETS, ob = (t >> 6) / DQ16_OCTETS;
+                const int F_wf = 2048 * C + 69792;   // conv1.w conv1.b conv2.w conv2.b conv3.w conv3.b come first
+                const uint32_t q0 = (uint32_t)((F_wf + (ob * 64 + l) * DQ_FC1_IN + 8 * o) >> 2);
+                float z[8];
+                philox_normal4(seed, slo, stream_hi, q0, z);
+                philox_normal4(seed, slo, stream_hi, q0 + 1u, z + 4);
+                _Float16 hin[8], hout[8];
+                __builtin_memcpy(hin, &pv, sizeof(hin));
+#pragma unroll
+                for (int i = 0; i < 8; ++i) hout[i] = (_Float16)dq16_child(dq16_pin((float)hin[i]), sigma * z[i]);
+                __builtin_memcpy(&ov, hout, sizeof(hout));
+            } else {
+                float in[4], out[4], zz[4];
+                __builtin_memcpy(in, &pv, sizeof(in));
+                int64_t have = -1;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int64_t s = 4 * (int64_t)u + i;
+                    const int64_t p = dqn16_word_to_flat(s, C, n_actions);
+                    out[i] = in[i];
+                    if (p < 0 || ((flags & COEVO_DQP_SKIP_BN) && dqn_slab_is_batchnorm(s, L))) continue;
+                    const int64_t q = p >> 2;
+                    if (q != have) { philox_normal4(seed, slo, stream_hi, (uint32_t)q, zz); have = q; }
+                    const int e = (int)(p & 3);
+                    const float zi = e == 0 ? zz[0] : (e == 1 ? zz[1] : (e == 2 ? zz[2] : zz[3]));   // (no runtime-indexed array)
+                    out[i] = dq16_child(in[i], sigma * zi);
+                }
+                __builtin_memcpy(&ov, out, sizeof(out));
+            }
+        }
+        // a plain store: the rollout reads the child next
+        if (child_slab) reinterpret_cast<uint4 *>(child_slab + (int64_t)(child_first + c) * L.stride)[u] = ov;
+        if (dist_partial) d2 = dq16_piece_d2(ov, reinterpret_cast<const uint4 *>(dist_ref)[u], u, L);
+    }
+    if (dist_partial) {   // uniform over the launch
+        const double tot = block_sum_f64(d2, scratch);
+        if (threadIdx.x == 0) dist_partial[(size_t)c * gridDim.x + bx] = tot;
+    }
+}
+
+// the same partials for nets that are already in a slab (generation 0, uploaded populations): grid (blocks, n)
+__global__ __launch_bounds__(256) void dqn16_distance_kernel(const uint32_t *ref_net, const uint32_t *pop_slab, int C,
+                                                              int n_actions, double *dist_partial)
+{
+    __shared__ double scratch[4];
+    const int n = blockIdx.y, bx = blockIdx.x;
+    const DqnLayout L = dqn16_layout(C, n_actions);
+    const int u = bx * 256 + (int)threadIdx.x;
+    double d2 = 0.0;
+    if (u < dq16_pieces(L))
+        d2 = dq16_piece_d2(reinterpret_cast<const uint4 *>(pop_slab + (int64_t)n * L.stride)[u],
+                           reinterpret_cast<const uint4 *>(ref_net)[u], u, L);
+    const double tot = block_sum_f64(d2, scratch);
+    if (threadIdx.x == 0) dist_partial[(size_t)n * gridDim.x + bx] = tot;
+}
+
+}  // namespace coevo
+
+using namespace coevo;
+
+static unsigned dqn16_blocks(int C, int n) { return quad_blocks(dqn16_layout(C, n).stride); }
+
+extern "C" int64_t coevo_dqn16_perturb_blocks(int C, int n_actions)
+{
+    return dqn_shape_ok(C, n_actions) ? (int64_t)dqn16_blocks(C, n_actions) : COEVO_ERR_ARG;
+}
+
+extern "C" int coevo_dqn16_perturb_dist(const void *parent_slab, const int32_t *parent_idx, void *child_slab, int child_first,
+                                        int n_children, int C, int n_actions, const float *sigma_dev, uint64_t seed,
+                                        uint32_t stream_lo_first, uint32_t stream_hi, int flags, const int32_t *gen_dev,
+                                        int gen_bias, const void *dist_ref, double *dist_partial, void *stream)
+{
+    if ((dist_ref == nullptr) != (dist_partial == nullptr)) return COEVO_ERR_ARG;
+    if (!dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;   // (any bit or-ed into C fails here)
+    if (flags & ~(COEVO_DQP_SKIP_BN | COEVO_DQP_COPY)) return COEVO_ERR_ARG;   // antithetic / from-order: not built for fp16
+    const bool copy = (flags & COEVO_DQP_COPY) != 0;
+    if (!parent_slab || !parent_idx || (!sigma_dev && !copy)) return COEVO_ERR_ARG;
+    if (!child_slab && !(copy && dist_partial)) return COEVO_ERR_ARG;   // NULL child: the distance of existing nets only
+    if (!aligned16(parent_slab) || !aligned16(child_slab) || !aligned16(dist_ref)) return COEVO_ERR_ARG;
+    if (n_children < 0 || child_first < 0 || n_children > 65535) return COEVO_ERR_ARG;
+    if (n_children == 0) return COEVO_OK;
+    const dim3 grid(dqn16_blocks(C, n_actions), (unsigned)n_children);
+    hipLaunchKernelGGL(dqn16_perturb_dist_kernel, grid, dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const uint32_t *>(parent_slab), parent_idx, static_cast<uint32_t *>(child_slab), child_first,
+                       C, n_actions, sigma_dev, seed, stream_lo_first, stream_hi, flags, gen_dev, gen_bias,
+                       static_cast<const uint32_t *>(dist_ref), dist_partial);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_dqn16_distance(const void *ref_net, const void *pop_slab, int n, int C, int n_actions, double *dist_partial,
+                                    void *stream)
+{
+    if (!ref_net || !pop_slab || !dist_partial || !dqn_shape_ok(C, n_actions) || n < 0 || n > 65535) return COEVO_ERR_ARG;
+    if (!aligned16(ref_net) || !aligned16(pop_slab)) return COEVO_ERR_ARG;
+    if (n == 0) return COEVO_OK;
+    const dim3 grid(dqn16_blocks(C, n_actions), (unsigned)n);
+    hipLaunchKernelGGL(dqn16_distance_kernel, grid, dim3(256), 0, (hipStream_t)stream, static_cast<const uint32_t *>(ref_net),
+                       static_cast<const uint32_t *>(pop_slab), C, n_actions, dist_partial);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}

@@ -775,6 +775,33 @@ int coevo_dqn_perturb(const float *parent_slab, const int32_t *parent_idx, float
                       uint32_t stream_lo_first, uint32_t stream_hi, int flags, int E, const int32_t *gen_dev,
                       int gen_bias, const float *dist_ref, double *dist_partial, void *stream);
 /* K5 for the DeepQN layout (see coevo_es_partial / coevo_es_apply): BatchNorm affine is never updated */
+/* Float16 Co-GA breeding on the fp16 DeepQN slab (coevo_dqn16_pack's layout; DESIGN.md 6a "Float16 DeepQN breeding").
+ *   mutation  child = f16(f32(parent) + noise) for EVERY parameter (the BatchNorm affine is half in the reference's float16
+ *             DeepQN), noise = sigma * eps(seed, stream, p) rounded to fp32 first, p the canonical index: the fp16 child
+ *             draws the numbers coevo_dqn_perturb's fp32 child of the same (seed, stream) draws.  Round to nearest even, past
+ *             65504 -> inf, fp16 subnormals kept.  Child c takes stream (stream_lo_first + c, stream_hi_eff), parent
+ *             parent_idx[c] of parent_slab, and is written to net child_first + c of child_slab.
+ *   flags     COEVO_DQP_SKIP_BN (BatchNorm affine untouched), COEVO_DQP_COPY (child = parent; child_slab may then be NULL
+ *             for the distance alone, and sigma_dev may be NULL) or 0; any other bit - COEVO_DQP_ANTITHETIC and
+ *             COEVO_DQP_FROM_ORDER are not built for fp16 - is COEVO_ERR_ARG
+ *   gen_dev != NULL: stream_hi_eff = stream_hi + 4 * (*gen_dev + gen_bias)
+ *   distance  dist_ref / dist_partial (both or neither): per entry d = f16(f32(child) - f32(ref)), d * d summed in fp64 in a
+ *             fixed order over ALL parameters (the stride's padding is not counted), one partial per block of 256 16-byte
+ *             pieces: dist_partial [n_children][coevo_dqn16_perturb_blocks].  coevo_fc16_distance_finalize (n_blocks =
+ *             coevo_dqn16_perturb_blocks) turns them into dist = f16(sqrt(sum)), one rounding.  coevo_dqn16_distance writes
+ *             the same partials, bit for bit, for n nets that are already in a slab.
+ * COEVO_ERR_ARG, with nothing written: a NULL pointer (but for the cases above), C outside 1 .. 6 (any bit or-ed into it
+ * included) or n_actions outside 1 .. 32, a slab or reference pointer that is not 16-byte aligned, a negative count, exactly
+ * one of dist_ref / dist_partial.  A count of 0 is COEVO_OK.  One launch on `stream`, plain stores; synchronises with
+ * nothing.  Gather, HoF push and elites: coevo_net_gather with coevo_dqn16_slab_stride as the stride. */
+int64_t coevo_dqn16_perturb_blocks(int C, int n_actions);
+int coevo_dqn16_perturb_dist(const void *parent_slab, const int32_t *parent_idx, void *child_slab, int child_first,
+                             int n_children, int C, int n_actions, const float *sigma_dev, uint64_t seed,
+                             uint32_t stream_lo_first, uint32_t stream_hi, int flags, const int32_t *gen_dev, int gen_bias,
+                             const void *dist_ref, double *dist_partial, void *stream);
+int coevo_dqn16_distance(const void *ref_net, const void *pop_slab, int n, int C, int n_actions, double *dist_partial,
+                         void *stream);
+/* K5 for the DeepQN layout (see coevo_es_partial / coevo_es_apply): BatchNorm affine is never updated */
 int coevo_dqn_es_partial(const float *theta_net, const float *pert_slab_local, int ind_first, int C, int n_actions,
                          const float *fitness_all, int n_total, int chunks_total, int chunk_first, int n_chunks,
                          float *partial, void *stream);
