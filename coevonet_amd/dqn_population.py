@@ -30,9 +30,8 @@ from . import lib as L
 from .atari_synthetic import SYNTH_SEED
 from .deepqn import DeepQN
 from .genetic_algorithm import N_EVAL, adapt_mutation_power
-from .population import NetTable, SlabIO, slab_layout
+from .population import ROLES2, NetTable, SlabIO, captured, co_ga_games2, eval_gate_limits, mean_eval, slab_layout
 
-ROLES2 = ("first_0", "second_0")
 SIGMA2 = ("mutation_power_agent_0", "mutation_power_agent_1")
 TASK_ROWS = L.DQN_MAX_ROWS
 FRAME = 84 * 84
@@ -340,16 +339,26 @@ class _DQNSlabIO(SlabIO):
 
 
 class DQNGAEngine(_DQNSlabIO):
+    """Device-resident population / HoF / elites of first_0 and second_0 and the generation step: ``load_initial`` ->
+    ``step()`` per generation -> ``eval_only()`` for the last generation's evaluation games.  The body is precision-free: a
+    precision names its slab words and entry points below and its rollout, initial distances and children in three hooks
+    (float16: dqn_ga_half.HalfDQNGAEngine)."""
+    _slab_dtype = torch.float32
+    _stride_entry, _pblocks_entry = "coevo_dqn_slab_stride", "coevo_dqn_perturb_blocks"
+    _finalize_entry = "coevo_fc_distance_finalize"
+    _fc1_tileable = True
+    _saves_sigma_prev = True   # what last generation's children were bred with: a shard rebuilds its elites from it
+
     def __init__(self, pop, hof, elites, C, n_actions, T_train, T_eval, device="cuda", env_seed=SYNTH_SEED,
                  philox_seed=0, shard=(0, 1), gather=None, first_ordinal=1, capacity=1024, sigmas=(0.05, 0.05),
                  sig_min=0.001, sig_max=0.2, adaptive=True, frames="device"):
         assert 1 <= elites <= pop and hof >= 1 and frames in ("device", "host")
         self.frames = frames
         self.pop, self.hof, self.E, self.C, self.n_actions = pop, hof, elites, C, n_actions
-        # the engine's slab keeps fc1 TILED for v_mfma_f32_16x16x4 (its tasks carry 10 / 16 frames; include/coevo.h
+        # the float32 slab keeps fc1 TILED for v_mfma_f32_16x16x4 (its tasks carry 10 / 16 frames; include/coevo.h
         # COEVO_DQN_FC1_TILED; COEVO_DQN_FC1_LAYOUT=streamed keeps the Co-ES layout for A/B runs): every layout-dependent
         # call takes self.Cw
-        self.fc1_tiled = os.environ.get("COEVO_DQN_FC1_LAYOUT", "tiled") != "streamed"
+        self.fc1_tiled = self._fc1_tileable and os.environ.get("COEVO_DQN_FC1_LAYOUT", "tiled") != "streamed"
         self.Cw = C | (L.DQN_FC1_TILED if self.fc1_tiled else 0)
         self.T_train, self.T_eval = int(T_train), int(T_eval)
         self.T = max(self.T_train, self.T_eval)
@@ -361,39 +370,19 @@ class DQNGAEngine(_DQNSlabIO):
         self.lo, self.hi = self.rank * pop // self.world, (self.rank + 1) * pop // self.world
         self.n_local = self.hi - self.lo
         lib = L.load()
-        self.stride = int(lib.coevo_dqn_slab_stride(C, n_actions))
+        self.stride = int(getattr(lib, self._stride_entry)(C, n_actions))   # 32-bit words
         self.P = int(lib.coevo_dqn_param_count(C, n_actions))
+        if self.stride <= 0:
+            raise ValueError(f"{type(self).__name__}: {C} channels / {n_actions} actions is not a DeepQN shape")
         strides = dict.fromkeys(ROLES2, self.stride)
         self.base, total = slab_layout(ROLES2, (("pop", pop), ("hof", hof), ("elite", elites), ("stale", 1), ("hof_tmp", hof),
                                                 ("elite_prev", elites)), strides)
-        self.slab = torch.zeros(total, dtype=torch.float32, device=device)
+        self.slab = torch.zeros(total, dtype=self._slab_dtype, device=device)
         # ---- games of one generation launch (this rank's individuals) + the evaluation games of the previous one
         net = NetTable(self.base, strides)
-        net_off = net.net_off
-
-        h, M = hof, 2 * pop * hof
-        self.per_gen = M + N_EVAL
-        games, ordinal0 = [], []
-        for ph, role in enumerate(ROLES2):
-            for i in range(self.lo, self.hi):
-                for k in range(h):
-                    opp = net("hof", ROLES2[1 - ph], h - 1 - k)
-                    games.append((net("pop", role, i), opp) if ph == 0 else (opp, net("pop", role, i)))
-                    ordinal0.append(first_ordinal + ph * pop * hof + i * hof + k)
-        self.n_main = len(games)
-        for j in range(N_EVAL):  # the best pair = the newest HoF members; generation g-1's games ride in g's launch
-            games.append((net("hof", "first_0", h - 1), net("hof", "second_0", h - 1)))
-            ordinal0.append(first_ordinal - self.per_gen + M + j)
-        # optional (COEVO_DQN_COHORTS=2): two cohorts = the two role phases (contiguous game ranges; the evaluation games
-        # go with the second) on two streams.  Measured on the cfg 4 shard: 12.2 vs 12.6 generations/s for one chain - conv
-        # stack and fc1 both live on the matrix pipe at these row counts, there is nothing complementary to overlap
-        K = int(os.environ.get("COEVO_DQN_COHORTS", "1"))
-        bounds = [0, self.n_main // 2, len(games)] if (K > 1 and self.n_main >= 2) else None
-        if frames == "host":   # env in host memory: the cohorts alternate between the host cores and the GPU
-            bounds = even_bounds(len(games), int(os.environ.get("COEVO_FRAME_COHORTS", "3")))
-        self.ro = (HostFrameRollout if frames == "host" else SynthRollout)(
-            games, net_off, ordinal0, C, n_actions, self.slab, env_seed, self.per_gen, device, bounds=bounds,
-            fc1_tiled=self.fc1_tiled)
+        self.per_gen = 2 * pop * hof + N_EVAL
+        games, ordinal0, self.n_main = co_ga_games2(net, self.lo, self.hi, hof, first_ordinal, pop)
+        self.ro = self._rollout(games, net.net_off, ordinal0, env_seed)
         self.cohorts = len(self.ro.lanes)
         # ---- device-resident loop state ------------------------------------------------------------------------
         f32 = dict(dtype=torch.float32, device=device)
@@ -412,7 +401,7 @@ class DQNGAEngine(_DQNSlabIO):
         self.order = [torch.zeros(pop, **i32) for _ in ROLES2]
         self.best_dist = [torch.zeros(1, **f32) for _ in ROLES2]
         self.last_reward = torch.zeros(2, pop, 3, dtype=torch.float64, device=device)
-        self.pblocks = int(lib.coevo_dqn_perturb_blocks(self.Cw, n_actions))
+        self.pblocks = int(getattr(lib, self._pblocks_entry)(self.Cw, n_actions))
         self.dist_partial = torch.zeros(max(pop, 1) * self.pblocks, dtype=torch.float64, device=device)
         self.parent_idx = torch.tensor([c % elites for c in range(max(pop - 1, 1))], **i32)
         self.iota = torch.arange(max(pop, hof, elites, 2), **i32)
@@ -423,16 +412,43 @@ class DQNGAEngine(_DQNSlabIO):
         self.generation = 0
         self.steps_per_generation = 2 * pop * hof * self.T_train + N_EVAL * self.T_eval
 
+    # ------------------------------------------------------------------------------------------ what a precision fills in
+    def _rollout(self, games, net_off, ordinal0, env_seed):
+        # optional (COEVO_DQN_COHORTS=2): two cohorts = the two role phases (contiguous game ranges; the evaluation games
+        # go with the second) on two streams.  Measured on the cfg 4 shard: 12.2 vs 12.6 generations/s for one chain - conv
+        # stack and fc1 both live on the matrix pipe at these row counts, there is nothing complementary to overlap
+        K = int(os.environ.get("COEVO_DQN_COHORTS", "1"))
+        bounds = [0, self.n_main // 2, len(games)] if (K > 1 and self.n_main >= 2) else None
+        if self.frames == "host":   # env in host memory: the cohorts alternate between the host cores and the GPU
+            bounds = even_bounds(len(games), int(os.environ.get("COEVO_FRAME_COHORTS", "3")))
+        return (HostFrameRollout if self.frames == "host" else SynthRollout)(
+            games, net_off, ordinal0, self.C, self.n_actions, self.slab, env_seed, self.per_gen, self.device, bounds=bounds,
+            fc1_tiled=self.fc1_tiled)
+
+    def _initial_distance(self, r):
+        """partial sums of the distances of role r's population to its stale agent (flag 8: nothing is written but them)"""
+        L.call("coevo_dqn_perturb", self._ptr(r, "pop"), L._p(self.iota), None, 0, self.pop, self.Cw, self.n_actions,
+               None, 0, 0, 0, 8, 1, None, 0, self._ptr(r, "stale"), L._p(self.dist_partial))
+
+    def _breed_children(self, ri, r, c_lo, c_hi, g):
+        """children [c_lo, c_hi) of role r (child c = individual c + 1 from elite[c % E], noise stream (c, 4 x device
+        generation + role index)) + the partial sums of their stale-agent distances"""
+        L.call("coevo_dqn_perturb", self._ptr(r, "elite"), self.parent_idx.data_ptr() + 4 * c_lo,
+               self._ptr(r, "pop"), 1 + c_lo, c_hi - c_lo, self.Cw, self.n_actions,
+               self.sigma32.data_ptr() + 4 * ri, self.philox_seed, c_lo, ri, 0, self.E, g, 0,
+               self._ptr(r, "stale"), L._p(self.dist_partial))
+
+    # ------------------------------------------------------------------------------------------ loading weights
     def load_initial(self, pop_flat, hof_flat):
+        """pop_flat[role] [pop][P], hof_flat[role] [hof][P]; the stale agent of Q3 is the initial pop[pop-1], the object left
+        over from the init loop; the distances of the initial population to it (later: fused into breeding)"""
         for r in ROLES2:
             self.upload(r, "pop", 0, pop_flat[r])
             self.upload(r, "hof", 0, hof_flat[r])
-            self.upload(r, "stale", 0, pop_flat[r][self.pop - 1:self.pop])   # Q3: the object left over from the init loop
-        for ri, r in enumerate(ROLES2):  # distances of the initial population to the stale agent (later: fused into breeding)
-            L.call("coevo_dqn_perturb", self._ptr(r, "pop"), L._p(self.iota), None, 0, self.pop, self.Cw, self.n_actions,
-                   None, 0, 0, 0, 8, 1, None, 0, self._ptr(r, "stale"), L._p(self.dist_partial))
-            L.call("coevo_fc_distance_finalize", L._p(self.dist_partial), self.pblocks, self.pop,
-                   self.dist_all[ri].data_ptr(), 0, None)
+            self.upload(r, "stale", 0, pop_flat[r][self.pop - 1:self.pop])
+        for ri, r in enumerate(ROLES2):
+            self._initial_distance(r)
+            L.call(self._finalize_entry, L._p(self.dist_partial), self.pblocks, self.pop, self.dist_all[ri].data_ptr(), 0, None)
         torch.cuda.current_stream().synchronize()
 
     # ------------------------------------------------------------------------------------------ one generation
@@ -451,7 +467,8 @@ class DQNGAEngine(_DQNSlabIO):
                                        L._p(self.best_dist[ri]), 0 if sharded else ri * self.pop * self.hof, ri)
         L.call("coevo_ga_select", roles, 2, self.pop, 1 if sharded else self.hof, self.hof)
         mn, mx, adaptive = self.loop_args
-        self.sigma32_prev.copy_(self.sigma32)
+        if self._saves_sigma_prev:
+            self.sigma32_prev.copy_(self.sigma32)
         L.call("coevo_ga_adapt_sigma", L._p(ro.acc), self.n_main, g, L._p(self.hist), L._p(self.sig_hist), self.cap,
                L._p(self.sigma64), L._p(self.sigma32), mn, mx, adaptive)
         c_lo, c_hi = (max(self.lo, 1) - 1, self.hi - 1) if sharded else (0, self.pop - 1)  # child c = individual c + 1
@@ -476,55 +493,44 @@ class DQNGAEngine(_DQNSlabIO):
             if self.lo == 0:
                 L.call("coevo_net_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "pop"), 0, 1, self.stride)
             if c_hi > c_lo:
-                L.call("coevo_dqn_perturb", self._ptr(r, "elite"), self.parent_idx.data_ptr() + 4 * c_lo,
-                       self._ptr(r, "pop"), 1 + c_lo, c_hi - c_lo, self.Cw, self.n_actions,
-                       self.sigma32.data_ptr() + 4 * ri, self.philox_seed, c_lo, ri, 0, self.E, g, 0,
-                       self._ptr(r, "stale"), L._p(self.dist_partial))
-                L.call("coevo_fc_distance_finalize", L._p(self.dist_partial), self.pblocks, c_hi - c_lo,
+                self._breed_children(ri, r, c_lo, c_hi, g)
+                L.call(self._finalize_entry, L._p(self.dist_partial), self.pblocks, c_hi - c_lo,
                        self.dist_all[ri].data_ptr(), 1 + c_lo, L._p(self.best_dist[ri]) if c_lo == 0 else None)
             elif self.lo == 0:
                 self.dist_all[ri][0:1].copy_(self.best_dist[ri])
         L.call("coevo_counter_add", g, 1)
+
+    def _generation(self, gen):
+        self.ro.enqueue(self.T, self.gen_dev)
+        self._tail(gen)
 
     def step(self, use_graph=True):
         gen = self.generation
         if gen >= self.cap:
             raise RuntimeError(f"generation {gen} exceeds the device history capacity ({self.cap})")
         if gen <= 1:  # the evaluation games of "generation -1" do not exist: disabled in generation 0 only
-            limits = np.full(self.ro.n_games, self.T_train, dtype=np.int32)
-            limits[self.n_main:] = self.T_eval if gen == 1 else 0
-            self.ro.set_limits(limits)
+            self.ro.set_limits(eval_gate_limits(self.ro.n_games, self.n_main, self.T_train, self.T_eval, gen))
         if self.world == 1 and use_graph and self.cohorts == 1 and self.frames == "device":   # (cohort chains: eager)
             if self._graph is None:
-                torch.cuda.synchronize()
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                    self.ro.enqueue(self.T, self.gen_dev)
-                    self._tail(1)   # (gen only matters to the sharded path)
-                self._graph = gr
+                self._graph = captured(lambda: self._generation(1))   # (gen only matters to the sharded path)
             self._graph.replay()
         else:
-            self.ro.enqueue(self.T, self.gen_dev)
-            self._tail(gen)
+            self._generation(gen)
         self.generation += 1
 
     def eval_only(self):
         """the evaluation games of the last generation (they would ride in the next one): main games disabled"""
         ro = self.ro
-        limits = np.zeros(ro.n_games, dtype=np.int32)
-        limits[self.n_main:] = self.T_eval
-        ro.set_limits(limits)
+        ro.set_limits(eval_gate_limits(ro.n_games, self.n_main, 0, self.T_eval, 1))
         ro.enqueue(self.T_eval, self.gen_dev)
         torch.cuda.synchronize()
         L.raise_on_status(ro.status)
-        r = ro.acc[self.n_main:].cpu().numpy()
-        tot = [0.0, 0.0]
-        for j in range(N_EVAL):
-            for s in range(2):
-                tot[s] += float(r[j, s])
-        limits[:self.n_main] = self.T_train
-        ro.set_limits(limits)
-        return [t / 10 for t in tot]
+        means = mean_eval(ro.acc[self.n_main:].cpu().numpy(), 2)
+        ro.set_limits(eval_gate_limits(ro.n_games, self.n_main, self.T_train, self.T_eval, 1))
+        return means
+
+    def close(self):
+        self.ro.close()
 
 
 class DQNResult:
@@ -767,23 +773,14 @@ class DQNESEngine(_DQNSlabIO):
         # generation when enqueued one by one) - replayed as one hipGraph (the generation index is read from the device)
         if self.eval_graph:
             if self._eval_graph is None:
-                torch.cuda.synchronize()
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                    self.eval_ro.enqueue(self.T_eval, self.gen_dev)
-                self._eval_graph = gr
+                self._eval_graph = captured(lambda: self.eval_ro.enqueue(self.T_eval, self.gen_dev))
             self._eval_graph.replay()
         else:
             self.eval_ro.enqueue(self.T_eval, self.gen_dev)
         torch.cuda.synchronize()
         L.raise_on_status(self.ro.status)
         L.raise_on_status(self.eval_ro.status)
-        r = self.eval_ro.acc.cpu().numpy()
-        tot = [0.0, 0.0]
-        for j in range(N_EVAL):
-            for s in range(2):
-                tot[s] += float(r[j, s])
-        return [t / 10 for t in tot]
+        return mean_eval(self.eval_ro.acc.cpu().numpy(), 2)
 
 
 class DQNESTrainer:

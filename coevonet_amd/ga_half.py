@@ -16,19 +16,21 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .genetic_algorithm import RET_SLOT
 from .mpe.simple_adversary import ENV_SEED
-from .population import N_EVAL, ROLE_D, ROLES, CoGASchedule, NetTable, SlabIO, co_ga_games, slab_layout
+from .population import N_EVAL, ROLE_D, ROLES, CoGASchedule, CoGATail, NetTable, SlabIO, co_ga_games, slab_layout
 from .rollout import DeviceRollout, RolloutPlan, effective_steps
 
 
-class HalfGAEngine(SlabIO, CoGASchedule):
+class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
     """Device-resident float16 population / HoF / elites of the three roles and the per-generation steps.
 
     ``rollout(gen)`` -> ``select()`` -> ``breed(gen, sigmas)`` is one generation; ``run(generations, sigmas)`` loops them.
     Nets go in and out as flat float32 arrays of fp16 values in parameters() order (``FCNetworkHalf.flat()``)."""
     _pack_unpack = ("coevo_fc16_pack", "coevo_fc16_unpack")   # flat arrays carry fp16 values in float32
     one_reset = True   # the whole population is on this GPU: one reset launch for the three phases
+    _promote_entry = "coevo_ga16_promote"
+    _perturb_dist_entry = "coevo_fc16_perturb_dist"
+    _finalize_entry = "coevo_fc16_distance_finalize"
 
     def __init__(self, pop, hof, elites, limit_train=None, limit_eval=None, max_cycles=25, device="cuda",
                  env_seed=ENV_SEED, philox_seed=0, first_ordinal=1, *, adaptive=False, shard=(0, 1), env="device",
@@ -97,12 +99,7 @@ class HalfGAEngine(SlabIO, CoGASchedule):
                 L.call("coevo_fc16_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop,
                        L._p(self.dist[r]), 0, None)
             self._dist_current = True
-        roles = (L.GaSelectRole * 3)()
-        per_phase = self.pop * self.hof
-        for ri, r in enumerate(ROLES):
-            roles[ri] = L.GaSelectRole(L._p(self.dist[r]), L._p(self.ro.rewards), L._p(self.div[r]), L._p(self.fitness[r]),
-                                       L._p(self.order[r]), L._p(self.best_dist[r]), ri * per_phase, RET_SLOT[r])
-        L.call("coevo_ga_select", roles, 3, self.pop, self.hof, self.hof)
+        self._select_roles(lambda ri: L._p(self.ro.rewards), lambda ri: ri * self.pop * self.hof, self.hof)
 
     def breed(self, gen, sigmas):
         """elites -> elite buffer, HoF FIFO, population := [best] + (pop - 1) mutated clones (child c at pop[1 + c] from
@@ -110,21 +107,10 @@ class HalfGAEngine(SlabIO, CoGASchedule):
         are written; the unchanged best keeps the distance it had"""
         for r in ROLES:
             self.sigma[r].fill_(float(sigmas[r]))
-        roles = (L.GaPromoteRole * 3)()
+        self._promote_roles(elites_from_pop=True, best_to_pop0=True)
         for ri, r in enumerate(ROLES):
-            roles[ri] = L.GaPromoteRole(self._ptr(r, "pop"), self._ptr(r, "hof"), self._ptr(r, "elite"), L._p(self.order[r]),
-                                        ROLE_D[r], 1, 1, 0)
-        L.call("coevo_ga16_promote", roles, 3, self.E, self.hof)
-        for ri, r in enumerate(ROLES):
-            L.call("coevo_fc16_perturb_dist", self._ptr(r, "elite"), L._p(self.parent_idx), self._ptr(r, "pop"), 1,
-                   self.pop - 1, ROLE_D[r], L._p(self.sigma[r]), self.philox_seed, 0, gen * 4 + ri, 0, None,
-                   self._ptr(r, "stale"), L._p(self.dist_partial[r]))
-            L.call("coevo_fc16_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop - 1,
-                   L._p(self.dist[r]), 1, L._p(self.best_dist[r]))
+            self._breed_role_children(ri, r, 0, self.pop - 1, gen * 4 + ri, None, L._p(self.sigma[r]))
         self._dist_current = True
-
-    def elite_ids(self):
-        return {r: self.order[r][:self.E].cpu().numpy().astype(int).tolist() for r in ROLES}
 
     def diversity(self):
         """the sharing score of each role in the last select() (float32)"""

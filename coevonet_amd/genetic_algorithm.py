@@ -34,12 +34,11 @@ from . import lib as L
 from .fcnetwork import FCNetwork
 from .game_logic import create_agent
 from .mpe.simple_adversary import ENV_SEED
-from .population import (N_EVAL, ROLE_D, ROLES, CoGASchedule, NetTable, SlabIO, co_ga_games, mean_eval_triple,
-                         slab_layout)
+from .population import (N_EVAL, RET_SLOT, ROLE_D, ROLES, CoGASchedule, CoGATail, NetTable, SlabIO, captured, co_ga_games,
+                         eval_gate_limits, mean_eval_triple, slab_layout)
 from .rollout import DeviceRollout, HostEnvRollout, RolloutPlan, effective_steps
 
 ROLE_SLOT = {"agent_0": 1, "agent_1": 2, "adversary_0": 0}   # env slot the role acts in
-RET_SLOT = {"agent_0": 0, "agent_1": 1, "adversary_0": 2}    # position in play_game's return triple
 SIGMA_ATTR = {"agent_0": "mutation_power_agent_0", "agent_1": "mutation_power_agent_1",
               "adversary_0": "mutation_power_adversary"}
 
@@ -150,7 +149,7 @@ DEVICE_LOOP_COHORTS = 2   # ... in the host-free loop, where their launches are 
 SMALL_SHARD = 80          # ... unless a rank holds fewer individuals per role than this: then one chain
 
 
-class GAEngine(SlabIO, CoGASchedule):
+class GAEngine(SlabIO, CoGASchedule, CoGATail):
     """Device-resident population / HoF / elites of the three roles and the per-generation pipeline.
 
     shard = (rank, world): this process evaluates individuals [lo, hi) of every role (contiguous ranges, all HoF games
@@ -301,11 +300,7 @@ class GAEngine(SlabIO, CoGASchedule):
             self.last_reward[ph, self.lo:self.hi] = dev_rewards[idx]
         if self.world > 1:
             self.gather(self)  # all-gather of dist[role][lo:hi] and last_reward[:, lo:hi]
-        for ph, r in enumerate(ROLES):
-            L.call("coevo_sharing_score", L._p(self.dist[r]), self.pop, L._p(self.div[r]))
-            L.call("coevo_ga_fitness", self.last_reward[ph].data_ptr(), 0, self.pop, 1, self.hof, RET_SLOT[r],
-                   L._p(self.div[r]), L._p(self.fitness[r]))
-            L.call("coevo_rank_desc", L._p(self.fitness[r]), self.pop, L._p(self.order[r]))
+        self._select_unfused(lambda ri: self.last_reward[ri].data_ptr(), lambda ri: 0, 1)
 
     def breed_device(self, gen, sigmas):
         """elites -> elite buffer, HoF FIFO, population := [best] + (pop-1) mutated clones, all on the device.
@@ -322,42 +317,20 @@ class GAEngine(SlabIO, CoGASchedule):
                 self.sigma_prev[r].fill_(float(sigmas[r]))
             self._promote_roles(elites_from_pop=True, best_to_pop0=True)
             for ri, r in enumerate(ROLES):
-                # the children's stale-agent distances (Q3) are accumulated while they are written; individual 0 is the
-                # unchanged best, whose distance is the one it had
-                L.call("coevo_fc_perturb_dist", self._ptr(r, "elite"), L._p(self.parent_idx), self._ptr(r, "pop"), 1,
-                       self.pop - 1, ROLE_D[r], L._p(self.sigma[r]), self.philox_seed, 0, gen * 4 + ri, 0, None,
-                       self._ptr(r, "stale"), L._p(self.dist_partial[r]))
-                L.call("coevo_fc_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop - 1,
-                       L._p(self.dist[r]), 1, L._p(self.best_dist[r]))
+                self._breed_role_children(ri, r, 0, self.pop - 1, gen * 4 + ri, None, L._p(self.sigma[r]))
             self._dist_current = True
             return
         for ri, r in enumerate(ROLES):
-            D = ROLE_D[r]
-            if sharded and gen > 0:
-                L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "elite_prev"), 0, self.E, D)
-                L.call("coevo_fc_rebuild_elites", self._ptr(r, "elite_prev"), L._p(self.order[r]), self._ptr(r, "elite"),
-                       self.E, D, L._p(self.sigma_prev[r]), self.philox_seed, (gen - 1) * 4 + ri, None)
-            else:  # generation 0's population is the host-initialised one, present on every rank
-                L.call("coevo_fc_gather", self._ptr(r, "pop"), L._p(self.order[r]), self._ptr(r, "elite"), 0, self.E, D)
+            # generation 0's population is the host-initialised one, present on every rank
+            self._elites_unfused(r, (L._p(self.sigma_prev[r]), (gen - 1) * 4 + ri, None) if sharded and gen > 0 else None)
             self.sigma[r].fill_(float(sigmas[r]))
             self.sigma_prev[r].fill_(float(sigmas[r]))
-            self._hof_push(r)
-            L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "pop"), 0, 1, D)
+            self._promote_unfused(r)
             c_lo, c_hi = (max(self.lo, 1) - 1, self.hi - 1) if sharded else (0, self.pop - 1)  # child c = individual c+1
-            if c_hi > c_lo:
+            if c_hi > c_lo:   # (the host-driven selection computes the distances itself: children without them)
                 L.call("coevo_fc_perturb", self._ptr(r, "elite"), self.parent_idx.data_ptr() + 4 * c_lo,
-                       self._ptr(r, "pop"), 1 + c_lo, c_hi - c_lo, D, L._p(self.sigma[r]), self.philox_seed, c_lo,
+                       self._ptr(r, "pop"), 1 + c_lo, c_hi - c_lo, ROLE_D[r], L._p(self.sigma[r]), self.philox_seed, c_lo,
                        gen * 4 + ri, 0)
-
-    def _hof_push(self, r):
-        """hof.append(best); hof.pop(0)  (genetic_algorithm.py:270-275)"""
-        D = ROLE_D[r]
-        if self.hof > 1:
-            L.call("coevo_fc_gather", self._ptr(r, "hof"), L._p(self.hof_shift_idx), self._ptr(r, "hof_tmp"), 0,
-                   self.hof - 1, D)
-            L.call("coevo_fc_gather", self._ptr(r, "hof_tmp"), L._p(self.iota), self._ptr(r, "hof"), 0,
-                   self.hof - 1, D)
-        L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "hof"), self.hof - 1, 1, D)
 
     def breed_host_reference(self, env, args, sigmas):
         """mutate_elites as the reference runs it (genetic_algorithm.py:32-48): per role, per child a fresh net is
@@ -365,10 +338,8 @@ class GAEngine(SlabIO, CoGASchedule):
         keep = []
         self._dist_current = False
         for r in ROLES:
-            D = ROLE_D[r]
-            L.call("coevo_fc_gather", self._ptr(r, "pop"), L._p(self.order[r]), self._ptr(r, "elite"), 0, self.E, D)
-            self._hof_push(r)
-            L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "pop"), 0, 1, D)
+            self._elites_unfused(r)
+            self._promote_unfused(r)
         elite_flat = {r: self.download(r, "elite", 0, self.E) for r in ROLES}
         for r in ROLES:
             children = np.empty((self.pop - 1, self.P[r]), dtype=np.float32)
@@ -381,9 +352,6 @@ class GAEngine(SlabIO, CoGASchedule):
             if self.pop > 1:
                 keep.append(self.upload(r, "pop", 1, children))
         torch.cuda.current_stream().synchronize()
-
-    def elite_ids(self):
-        return {r: self.order[r][:self.E].cpu().numpy().astype(int).tolist() for r in ROLES}
 
     # ------------------------------------------------------------------ whole generation on the device, one graph
     def setup_device_loop(self, args, capacity):
@@ -425,18 +393,16 @@ class GAEngine(SlabIO, CoGASchedule):
         return (self.world == 1 and self.rng_mode == "device_philox" and self.pop > 1 and self.E <= 8 and self.hof <= 16
                 and self.pop <= 4096)
 
-    def _select_roles(self, rewards_ptr_of, game_first_of, games_per_individual):
-        roles = (L.GaSelectRole * 3)()
-        for ri, r in enumerate(ROLES):
-            roles[ri] = L.GaSelectRole(L._p(self.dist[r]), rewards_ptr_of(ri), L._p(self.div[r]), L._p(self.fitness[r]),
-                                       L._p(self.order[r]), L._p(self.best_dist[r]), game_first_of(ri), RET_SLOT[r])
-        L.call("coevo_ga_select", roles, 3, self.pop, games_per_individual, self.hof)
-
     def _adapt_args(self, with_prev=False):
         mn, mx, adaptive = self.loop_args
         return L.GaAdaptArgs(L._p(self.ro.rewards), L._p(self.gen_dev), L._p(self.hist), L._p(self.sig_hist),
                              L._p(self.sigma64), L._p(self.sigma32), L._p(self.sigma32_prev) if with_prev else None, mn, mx,
                              self.n_main, self.cap, adaptive, 0)
+
+    def _adapt_sigma(self):
+        mn, mx, adaptive = self.loop_args
+        L.call("coevo_ga_adapt_sigma", L._p(self.ro.rewards), self.n_main, L._p(self.gen_dev), L._p(self.hist),
+               L._p(self.sig_hist), self.cap, L._p(self.sigma64), L._p(self.sigma32), mn, mx, adaptive)
 
     def _select_adapt_roles(self, rewards_ptr_of, game_first_of, games_per_individual, gathered=None, with_prev=False):
         """selection of the three roles + the sigma rule (evaluation means, adaptive mutation power) in ONE launch"""
@@ -449,17 +415,6 @@ class GAEngine(SlabIO, CoGASchedule):
         ad = self._adapt_args(with_prev)
         L.call("coevo_ga_select_adapt", roles, 3, self.pop, games_per_individual, self.hof,
                L._p(gathered) if gathered is not None else None, self.n_local if gathered is not None else 0, L.C.byref(ad))
-
-    def _promote_roles(self, elites_from_pop, best_to_pop0, tick=False):
-        roles = (L.GaPromoteRole * 3)()
-        for ri, r in enumerate(ROLES):
-            roles[ri] = L.GaPromoteRole(self._ptr(r, "pop"), self._ptr(r, "hof"), self._ptr(r, "elite"),
-                                        L._p(self.order[r]), ROLE_D[r], 1 if elites_from_pop else 0,
-                                        1 if best_to_pop0 else 0, 0)
-        if tick:   # + the generation counter's increment: the last launch of the generation's tail
-            L.call("coevo_ga_promote_tick", roles, 3, self.E, self.hof, L._p(self.gen_dev))
-            return
-        L.call("coevo_ga_promote", roles, 3, self.E, self.hof)
 
     def enqueue_generation(self):
         """reset -> 25 cycles -> rewards -> sharing/fitness/rank -> evaluation means + adaptive sigma -> HoF push and
@@ -483,10 +438,8 @@ class GAEngine(SlabIO, CoGASchedule):
     def _enqueue_selection_and_breeding(self, breed=True):
         """(Measured: running the three roles' chains as parallel graph branches gains 1 % in the split loop and costs
         30 % inside the single whole-generation graph - this runtime schedules branched graphs badly; kept serial.)"""
-        ro, M = self.ro, 3 * self.pop * self.hof
-        per_gen, per_phase = M + N_EVAL, self.pop * self.hof
+        ro, per_phase = self.ro, self.pop * self.hof
         g = L._p(self.gen_dev)
-        mn, mx, adaptive = self.loop_args
         if self.fused_tail:
             # selection + sigma rule in one launch, promotion (+ the counter's tick when nothing follows) in one: the tail of a
             # pipelined generation is closing step -> these two (round 4: five launches)
@@ -495,26 +448,14 @@ class GAEngine(SlabIO, CoGASchedule):
             if not (self.pop > 1 and breed):
                 return
         else:
-            for ph, r in enumerate(ROLES):
-                L.call("coevo_sharing_score", L._p(self.dist[r]), self.pop, L._p(self.div[r]))
-                L.call("coevo_ga_fitness", L._p(ro.rewards), ph * per_phase, self.pop, self.hof, self.hof, RET_SLOT[r],
-                       L._p(self.div[r]), L._p(self.fitness[r]))
-                L.call("coevo_rank_desc", L._p(self.fitness[r]), self.pop, L._p(self.order[r]))
-            L.call("coevo_ga_adapt_sigma", L._p(ro.rewards), self.n_main, g, L._p(self.hist), L._p(self.sig_hist), self.cap,
-                   L._p(self.sigma64), L._p(self.sigma32), mn, mx, adaptive)
+            self._select_unfused(lambda ri: L._p(ro.rewards), lambda ri: ri * per_phase, self.hof)
+            self._adapt_sigma()
         for ri, r in enumerate(ROLES):
-            D = ROLE_D[r]
             if not self.fused_tail:
-                L.call("coevo_fc_gather", self._ptr(r, "pop"), L._p(self.order[r]), self._ptr(r, "elite"), 0, self.E, D)
-                self._hof_push(r)
-                L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "pop"), 0, 1, D)
-                L.call("coevo_gather_f32", L._p(self.best_dist[r]), L._p(self.dist[r]), L._p(self.order[r]), 1)
+                self._elites_unfused(r)
+                self._promote_unfused(r, best_dist=True)
             if self.pop > 1 and breed:
-                L.call("coevo_fc_perturb_dist", self._ptr(r, "elite"), L._p(self.parent_idx), self._ptr(r, "pop"), 1,
-                       self.pop - 1, D, self.sigma32.data_ptr() + 4 * ri, self.philox_seed, 0, ri, 0, g,
-                       self._ptr(r, "stale"), L._p(self.dist_partial[r]))
-                L.call("coevo_fc_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop - 1,
-                       L._p(self.dist[r]), 1, L._p(self.best_dist[r]))
+                self._breed_role_children(ri, r, 0, self.pop - 1, ri, g, self.sigma32.data_ptr() + 4 * ri)
         L.call("coevo_counter_add", g, 1)
 
     # ------------------------------------------------------------------ pipelined generation (cohort by cohort)
@@ -585,11 +526,7 @@ class GAEngine(SlabIO, CoGASchedule):
         assert self.world == 1 and self.env_mode == "device" and self.fused_tail and self.K > 1
         self._enqueue_cohort_chains(gen)
         if self._tail_graph is None:
-            torch.cuda.synchronize()
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                self._enqueue_selection_and_breeding(breed=False)
-            self._tail_graph = gr
+            self._tail_graph = captured(lambda: self._enqueue_selection_and_breeding(breed=False))
         self._tail_graph.replay()
         self._breeding_pending = self.pop > 1
         self.generation_enqueued = gen + 1
@@ -599,11 +536,7 @@ class GAEngine(SlabIO, CoGASchedule):
         then, on the caller's stream, the closing step of the rollout"""
         ro = self.ro
         if gen <= 1:  # the evaluation games of "generation -1" do not exist: disabled in generation 0 only
-            limits = np.zeros(self.plan.n_games, dtype=np.int32)
-            limits[:self.n_main] = self.T_train
-            if gen == 1:
-                limits[self.n_main:] = self.T_eval
-            ro.set_limits(limits)
+            ro.set_limits(eval_gate_limits(self.plan.n_games, self.n_main, self.T_train, self.T_eval, gen))
         main = torch.cuda.current_stream()
         if getattr(self, "_cohort_streams", None) is None:
             # cohort 0 on the caller's stream, the others on the rollout context's own lane streams (streams from
@@ -662,12 +595,8 @@ class GAEngine(SlabIO, CoGASchedule):
             self._breeding_pending = self.n_local > 0 and self.pop > 1
             self.generation_enqueued = gen + 1
             return
-        if gen <= 1:
-            limits = np.zeros(self.plan.n_games, dtype=np.int32)
-            limits[:self.n_main] = self.T_train
-            if gen == 1:
-                limits[self.n_main:] = self.T_eval
-            ro.set_limits(limits)
+        if gen <= 1:  # the evaluation games of "generation -1" do not exist: disabled in generation 0 only
+            ro.set_limits(eval_gate_limits(self.plan.n_games, self.n_main, self.T_train, self.T_eval, gen))
         base = self._ordinal_base(gen)
         per_phase = self.n_local * self.hof
         segs = [(ph * per_phase, per_phase, base + ph * self.pop * self.hof + self.lo * self.hof) for ph in range(3)]
@@ -701,88 +630,55 @@ class GAEngine(SlabIO, CoGASchedule):
             key = (bool(breed), packed)
             graphs = self.__dict__.setdefault("_sharded_tail_graphs", {})
             if key not in graphs:
-                torch.cuda.synchronize()
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                    self._sharded_tail_post(gen, breed=breed, gen_from_device=True, packed=packed)
-                graphs[key] = gr
+                graphs[key] = captured(lambda: self._sharded_tail_post(gen, breed=breed, gen_from_device=True, packed=packed))
             graphs[key].replay()
             return
         self._sharded_tail_post(gen, breed, gen_from_device=False, packed=packed)
 
     def _sharded_tail_post(self, gen, breed, gen_from_device, packed=False):
-        ro = self.ro
         g = L._p(self.gen_dev)
-        mn, mx, adaptive = self.loop_args
         if packed:
             # selection off the gathered buffer + the sigma rule (which also saves the sigma the evaluated children were bred
             # with) in one launch; promotion with the elites rebuilt from that sigma in one; then the rank's children and
             # their distances (+ the counter's tick): four launches behind the collective
             self._select_adapt_roles(None, None, 1, gathered=self.pack_all, with_prev=True)
-            pr = (L.GaPromoteRole * 3)()
-            for ri, r in enumerate(ROLES):
-                pr[ri] = L.GaPromoteRole(self._ptr(r, "pop"), self._ptr(r, "hof"), self._ptr(r, "elite"), L._p(self.order[r]),
-                                         ROLE_D[r], 1 if gen == 0 else 0, 1 if self.lo == 0 else 0, 0)
-            if gen == 0:   # generation 0's population is the host-initialised one, present on every rank
-                L.call("coevo_ga_promote", pr, 3, self.E, self.hof)
-            else:
-                L.call("coevo_ga_promote_rebuild", pr, 3, self.E, self.hof, L._p(self.sigma32_prev), self.philox_seed,
-                       0 if gen_from_device else (gen - 1) * 4, g if gen_from_device else None)
+            # generation 0's population is the host-initialised one, present on every rank
+            self._promote_roles(elites_from_pop=(gen == 0), best_to_pop0=(self.lo == 0), rebuild=None if gen == 0 else (
+                (0, g) if gen_from_device else ((gen - 1) * 4, None)))
             if breed:   # K = 1: the rank's children now, their distances + the counter's tick in the last launch
                 self._breed_cohort(0, gen, gen_dev=g if gen_from_device else None, tick=True)
             else:
                 L.call("coevo_counter_add", g, 1)
             return
-        if self.fused_tail:
-            self._select_roles(lambda ri: self.last_reward[ri].data_ptr(), lambda ri: 0, 1)
-        else:
-            for ph, r in enumerate(ROLES):
-                L.call("coevo_sharing_score", L._p(self.dist[r]), self.pop, L._p(self.div[r]))
-                L.call("coevo_ga_fitness", self.last_reward[ph].data_ptr(), 0, self.pop, 1, self.hof, RET_SLOT[r],
-                       L._p(self.div[r]), L._p(self.fitness[r]))
-                L.call("coevo_rank_desc", L._p(self.fitness[r]), self.pop, L._p(self.order[r]))
+        (self._select_roles if self.fused_tail else self._select_unfused)(
+            lambda ri: self.last_reward[ri].data_ptr(), lambda ri: 0, 1)
         self.sigma32_prev.copy_(self.sigma32)  # what last generation's children were bred with (elite rebuild)
-        L.call("coevo_ga_adapt_sigma", L._p(ro.rewards), self.n_main, g, L._p(self.hist), L._p(self.sig_hist), self.cap,
-               L._p(self.sigma64), L._p(self.sigma32), mn, mx, adaptive)
+        self._adapt_sigma()
         c_lo, c_hi = max(self.lo, 1) - 1, self.hi - 1  # child c = individual c + 1
         for ri, r in enumerate(ROLES):
-            D = ROLE_D[r]
             if gen > 0:
-                L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "elite_prev"), 0, self.E, D)
-                L.call("coevo_fc_rebuild_elites", self._ptr(r, "elite_prev"), L._p(self.order[r]), self._ptr(r, "elite"),
-                       self.E, D, self.sigma32_prev.data_ptr() + 4 * ri, self.philox_seed,
-                       ri if gen_from_device else (gen - 1) * 4 + ri, g if gen_from_device else None)
+                self._elites_unfused(r, (self.sigma32_prev.data_ptr() + 4 * ri, ri if gen_from_device else (gen - 1) * 4 + ri,
+                                         g if gen_from_device else None))
             elif not self.fused_tail:  # generation 0's population is the host-initialised one, present on every rank
-                L.call("coevo_fc_gather", self._ptr(r, "pop"), L._p(self.order[r]), self._ptr(r, "elite"), 0, self.E, D)
-            if not self.fused_tail:
-                self._hof_push(r)
-                L.call("coevo_gather_f32", L._p(self.best_dist[r]), L._p(self.dist[r]), L._p(self.order[r]), 1)
+                self._elites_unfused(r)
+            if not self.fused_tail:   # (here the best's distance is read BEFORE the best goes to pop[0]: this site's own order)
+                self._promote_unfused(r, best_to_pop0=False, best_dist=True)
                 if self.lo == 0:
-                    L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "pop"), 0, 1, D)
+                    self._best_to_pop0(r)
         if self.fused_tail:
             self._promote_roles(elites_from_pop=(gen == 0), best_to_pop0=(self.lo == 0))
         for ri, r in enumerate(ROLES):
-            D = ROLE_D[r]
             if not breed:
                 break
             if c_hi > c_lo:
-                L.call("coevo_fc_perturb_dist", self._ptr(r, "elite"), self.parent_idx.data_ptr() + 4 * c_lo,
-                       self._ptr(r, "pop"), 1 + c_lo, c_hi - c_lo, D, self.sigma32.data_ptr() + 4 * ri,
-                       self.philox_seed, c_lo, gen * 4 + ri, 0, None, self._ptr(r, "stale"),
-                       L._p(self.dist_partial[r]))
-                L.call("coevo_fc_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], c_hi - c_lo,
-                       L._p(self.dist[r]), 1 + c_lo, L._p(self.best_dist[r]) if c_lo == 0 else None)
+                self._breed_role_children(ri, r, c_lo, c_hi, gen * 4 + ri, None, self.sigma32.data_ptr() + 4 * ri)
             elif self.lo == 0:  # a shard that holds only the unchanged best
                 self.dist[r][0:1].copy_(self.best_dist[r])
         L.call("coevo_counter_add", g, 1)
 
     def replay_generation(self, gen):
         if gen <= 1:  # the evaluation games of "generation -1" do not exist: disabled in generation 0 only
-            limits = np.zeros(self.plan.n_games, dtype=np.int32)
-            limits[:self.n_main] = self.T_train
-            if gen == 1:
-                limits[self.n_main:] = self.T_eval
-            self.ro.set_limits(limits)
+            self.ro.set_limits(eval_gate_limits(self.plan.n_games, self.n_main, self.T_train, self.T_eval, gen))
         if self.ro.use_graph and self.ro.n_cohorts > 1 and self.fused_tail and self.pipelined:
             return self.replay_generation_pipelined(gen)
         if self.ro.use_graph and self.ro.n_cohorts > 1:
@@ -790,14 +686,7 @@ class GAEngine(SlabIO, CoGASchedule):
             # captured graph this runtime schedules them no better than one chain): the resets and the selection /
             # breeding tail are two small graphs, the rollout between them is one C call
             if self._gen_graph is None:
-                torch.cuda.synchronize()
-                parts = []
-                for fn in (self._enqueue_resets, self._enqueue_selection_and_breeding):
-                    gr = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                        fn()
-                    parts.append(gr)
-                self._gen_graph = parts
+                self._gen_graph = [captured(self._enqueue_resets), captured(self._enqueue_selection_and_breeding)]
             self._gen_graph[0].replay()
             self.ro.enqueue(self.n_cycles)
             self._gen_graph[1].replay()
@@ -806,11 +695,7 @@ class GAEngine(SlabIO, CoGASchedule):
             if self._gen_graph is None:
                 self._gen_graph = {}
             if key not in self._gen_graph:
-                torch.cuda.synchronize()
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                    self.enqueue_generation()
-                self._gen_graph[key] = gr
+                self._gen_graph[key] = captured(self.enqueue_generation)
                 # the capture did not execute anything: the counter still holds `gen`
             self._gen_graph[key].replay()
             if self.ro.time_light:

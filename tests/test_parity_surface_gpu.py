@@ -115,6 +115,12 @@ def test_ga_device_loop_matches_oracle_port(pop, cohorts, gens):
                         max_evaluation_steps=9 if long_run else 75, mutation_power_agent_0=0.05,
                         mutation_power_agent_1=0.08, mutation_power_adversary=0.03, max_mutation_power=0.1,
                         min_mutation_power=0.02, coevo_cohorts=cohorts)}
+    _device_loop_vs_oracle_port(cfg, pop, cohorts, gens, long_run)
+
+
+def _device_loop_vs_oracle_port(cfg, pop, cohorts, gens, long_run=False, drop=("coevo_cohorts",)):
+    """a device-resident loop of genetic_algorithm_train against rp.ga_train: elite ids, every game's rewards, evaluation
+    means, the sigma trajectory, the final Hall of Fame and population; `drop`: the keys of cfg["args"] the oracle does not take"""
     args, env, res = _ga(cfg, "device_philox")
     eng = res.engine
     assert eng.K == cohorts and eng.ro.n_cohorts == cohorts
@@ -124,7 +130,8 @@ def test_ga_device_loop_matches_oracle_port(pop, cohorts, gens):
         inds = np.unique((games % (pop * eng.hof)) // eng.hof)
         assert np.array_equal(inds, np.arange(lo_k, hi_k))
     oargs = copy.deepcopy(cfg["args"])
-    oargs.pop("coevo_cohorts")
+    for key in drop:
+        oargs.pop(key)
     _seed(cfg["seed"])
     oargs = Bag(algorithm="GA", **oargs)
     want = rp.ga_train(oargs, noise="philox", philox_seed=0)
@@ -144,6 +151,22 @@ def test_ga_device_loop_matches_oracle_port(pop, cohorts, gens):
         assert [sha(x) for x in eng.download(role, "hof", 0, hof)] == [sha(x) for x in want[-1]["hof"][role]]
         assert [sha(x) for x in eng.download(role, "pop", 0, pop)] == \
             [sha(x) for x in [want[-1]["elites"][role][0]] + _children(want[-1], role, oargs, gens - 1, pop)]
+    return eng
+
+
+@pytest.mark.parametrize("pop,hof,T", [(10, 3, 40), (6, 17, 30)])
+def test_ga_forced_sharded_loop_matches_oracle_port(pop, hof, T):
+    """GAEngine.step_sharded on one GPU (coevo_force_sharded_loop: one rank of one, the separate exchange without its
+    collective), two generations, with test_ga_device_loop_matches_oracle_port's assertions.  (10, 3, 40): the fused tail;
+    (6, 17, 30): a Hall of Fame deeper than 16, the launch-per-step tail.  Generation 1 rebuilds the elites from generation
+    0's elites and noise instead of gathering them."""
+    cfg = {"seed": 5,
+           "args": dict(generations=2, population=pop, hof_size=hof, elites_number=2, fitness_sharing=True,
+                        max_timesteps_per_episode=T, max_evaluation_steps=T, mutation_power_agent_0=0.05,
+                        mutation_power_agent_1=0.08, mutation_power_adversary=0.03, max_mutation_power=0.1,
+                        min_mutation_power=0.02, coevo_force_sharded_loop=True)}
+    eng = _device_loop_vs_oracle_port(cfg, pop, 1, 2, drop=("coevo_force_sharded_loop",))
+    assert eng.sharded_run and eng.fused_tail == (hof <= 16)
 
 
 def _children(rec, role, args, gen, pop):

@@ -112,6 +112,26 @@ def test_co_ga_seat_of_every_game_by_closed_formula(lo, hi, hof):
     assert games[n_main:] == [(("hof", "adversary_0", newest), ("hof", "agent_0", newest), ("hof", "agent_1", newest))] * N_EVAL
 
 
+@pytest.mark.parametrize("lo,hi,hof,pop", [(0, 3, 2, 3), (2, 4, 3, 6)])
+def test_co_ga_two_role_seat_and_ordinal_of_every_game_by_closed_formula(lo, hi, hof, pop):
+    """the two-role restriction of genetic_algorithm.py:119-301: phase `role`, individual i, k-th game against the other role's
+    Hall of Fame member hof - 1 - k (newest first, Q2), the role in its own seat; game (phase, i, k) of generation 0 is reset
+    under ordinal first + (phase pop + i) hof + k of the seeded stream, whichever shard plays it; the evaluation games of the
+    newest pair take the ordinals behind the PREVIOUS generation's main games (they ride in the next launch)"""
+    first = 7
+    games, ordinal0, n_main = P.co_ga_games2(Seats(), lo, hi, hof, first, pop)
+    n, per_gen = hi - lo, 2 * pop * hof + N_EVAL
+    assert n_main == 2 * n * hof and len(games) == len(ordinal0) == n_main + N_EVAL
+    for g, (f0, s0) in enumerate(games[:n_main]):
+        ph, i, k = g // (n * hof), lo + g % (n * hof) // hof, g % hof
+        own, opp = ("pop", P.ROLES2[ph], i), ("hof", P.ROLES2[1 - ph], hof - 1 - k)
+        assert (f0, s0) == ((own, opp) if ph == 0 else (opp, own)), g
+        assert ordinal0[g] == first + (ph * pop + i) * hof + k, g
+    assert games[n_main:] == [(("hof", "first_0", hof - 1), ("hof", "second_0", hof - 1))] * N_EVAL
+    assert ordinal0[n_main:] == [first - per_gen + 2 * pop * hof + j for j in range(N_EVAL)]
+    assert P.ROLES2 == ("first_0", "second_0")
+
+
 @pytest.mark.parametrize("n", [1, 3, 4])
 def test_co_es_seat_of_every_game_by_closed_formula(n):
     """evolutionary_strategy.py:236-251 of the reference: game 3j + role seats perturbed net j of that role (rank-local index)
@@ -180,6 +200,30 @@ def test_mean_eval_triple_keeps_the_python_float_accumulation_order():
     assert P.mean_eval_triple(np.vstack([rows, [[9.0, 9.0, 9.0]]])) == want
 
 
+def test_mean_eval_is_the_triple_mean_at_any_number_of_slots():
+    import numpy as np
+    rows = np.array([[1e16, 3.0, 0.1], [1.0, 1e16, 0.2], [-1e16, 1.0, 0.3], [1.0, -1e16, 0.1], [1e16, 1.0, 0.7],
+                     [1.0, 1e-3, 0.1], [-1e16, 7.0, 0.9], [0.5, 2.0 ** -30, 0.1], [3.0, 1e16, 0.3], [1.0, -1e16, 0.1]])
+    want = [0.0, 0.0]
+    for g in range(N_EVAL):
+        for s in range(2):
+            want[s] += float(rows[g, s])
+    got = P.mean_eval(rows, 2)
+    assert got == [t / 10 for t in want] and all(type(x) is float for x in got)
+    assert P.mean_eval(rows, 3) == P.mean_eval_triple(rows) and P.mean_eval(rows, 3)[:2] == got
+    assert P.mean_eval(np.vstack([rows, [[9.0, 9.0, 9.0]]]), 2) == got   # only the N_EVAL rows count
+
+
+@pytest.mark.parametrize("gen,eval_limit", [(0, 0), (1, 20), (2, 20)])
+def test_eval_gate_limits_disable_the_evaluation_games_in_generation_0_only(gen, eval_limit):
+    """the evaluation games in generation g's launch are those of generation g - 1: none in generation 0"""
+    import numpy as np
+    limits = P.eval_gate_limits(7 + N_EVAL, 7, 30, 20, gen)
+    assert limits.dtype == np.int32 and limits.tolist() == [30] * 7 + [eval_limit] * N_EVAL
+    # the flush of the last evaluation games: main games disabled
+    assert P.eval_gate_limits(7 + N_EVAL, 7, 0, 20, 1).tolist() == [0] * 7 + [20] * N_EVAL
+
+
 def test_the_engines_share_the_functions_instead_of_copies():
     from coevonet_amd import dqn_population, es_half, evolutionary_strategy, ga_half, genetic_algorithm
     for cls in (genetic_algorithm.GAEngine, ga_half.HalfGAEngine):
@@ -198,6 +242,27 @@ def test_the_engines_share_the_functions_instead_of_copies():
     for cls in (dqn_population.DQNGAEngine, dqn_population.DQNESEngine):
         assert issubclass(cls, P.SlabIO) and cls._ptr is P.SlabIO._ptr and cls.download is P.SlabIO.download
     assert not hasattr(dqn_population, "_SlabMixin")
+    # the Co-GA tail: one mixin for the fully connected engines, one DeepQN engine body for both precisions
+    from coevonet_amd import dqn_ga_half
+    for cls in (genetic_algorithm.GAEngine, ga_half.HalfGAEngine):
+        assert issubclass(cls, P.CoGATail) and cls.elite_ids is P.CoGASchedule.elite_ids
+        for name in ("_select_roles", "_select_unfused", "_promote_roles", "_promote_unfused", "_hof_push",
+                     "_breed_role_children"):
+            assert getattr(cls, name) is getattr(P.CoGATail, name), name
+    assert ga_half.HalfGAEngine._promote_entry == "coevo_ga16_promote" != P.CoGATail._promote_entry
+    assert genetic_algorithm.RET_SLOT is P.RET_SLOT and not hasattr(ga_half, "RET_SLOT")
+    D32, D16 = dqn_population.DQNGAEngine, dqn_ga_half.HalfDQNGAEngine
+    assert issubclass(D16, D32) and dqn_population.ROLES2 is P.ROLES2
+    for name in ("step", "_tail", "eval_only", "load_initial", "upload"):
+        assert getattr(D16, name) is getattr(D32, name), name
+    for name in ("_rollout", "_initial_distance", "_breed_children", "_finalize_entry", "_slab_dtype", "_pack_unpack"):
+        assert getattr(D16, name) is not getattr(D32, name), name
+    import inspect
+    for mod in (dqn_population, dqn_ga_half):   # both take their table from co_ga_games2: neither module builds one
+        src = inspect.getsource(mod).split("class DQNESEngine")[0]
+        assert "ordinal0.append" not in src and "games.append" not in src
+    assert dqn_population.co_ga_games2 is P.co_ga_games2 and "co_ga_games2(" in inspect.getsource(D32.__init__)
+    assert "co_ga_games2" not in inspect.getsource(dqn_ga_half) and D16.__init__ is not D32.__init__
     for mod in (genetic_algorithm, ga_half, evolutionary_strategy, es_half):
         assert (mod.ROLES, mod.ROLE_D, mod.N_EVAL) == (P.ROLES, P.ROLE_D, P.N_EVAL)
 
