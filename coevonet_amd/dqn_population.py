@@ -29,8 +29,8 @@ import torch
 from . import lib as L
 from .atari_synthetic import SYNTH_SEED
 from .deepqn import DeepQN
-from .genetic_algorithm import N_EVAL, adapt_mutation_power
-from .population import ROLES2, NetTable, SlabIO, captured, co_ga_games2, eval_gate_limits, mean_eval, slab_layout
+from .population import (ES_CHUNKS, N_EVAL, ROLES2, CoESUpdate, NetTable, SlabIO, adapt_mutation_power2, captured, co_es_games2,
+                         co_ga_games2, eval_gate_limits, mean_eval, shard_and_gather, slab_layout)
 
 SIGMA2 = ("mutation_power_agent_0", "mutation_power_agent_1")
 TASK_ROWS = L.DQN_MAX_ROWS
@@ -561,9 +561,7 @@ class DQNGATrainer:
         self.env, self.args, self.collect = env, args, collect
         C, n = _env_shape(env, args)
         pop_flat, hof_flat = dqn_initial_population(args.population, args.hof_size, C, n)
-        shard, gather = (0, 1), None
-        if dist_ctx is not None and dist_ctx.world > 1:
-            shard, gather = (dist_ctx.rank, dist_ctx.world), dist_ctx.gather_ga2
+        shard, gather = shard_and_gather(dist_ctx, "gather_ga2")
         self.first_ordinal = getattr(env, "n_resets", 1)
         self.eng = DQNGAEngine(args.population, args.hof_size, args.elites_number, C, n,
                                args.max_timesteps_per_episode, args.max_evaluation_steps,
@@ -609,12 +607,7 @@ class DQNGATrainer:
             for s, r in enumerate(ROLES2):
                 res.rewards[r].append(ev[s])
             if args.adaptive:  # the last generation's rule on the host (its evaluation never rode in a next launch)
-                keep = getattr(args, "mutation_power_adversary", 0.0)
-                h = {"agent_0": res.rewards["first_0"], "agent_1": res.rewards["second_0"],
-                     "adversary_0": [0.0] * len(res.rewards["first_0"])}
-                args.mutation_power_adversary = 0.0
-                adapt_mutation_power(args, self.gen - 1, h)
-                args.mutation_power_adversary = keep
+                adapt_mutation_power2(args, self.gen - 1, res.rewards, zero_adversary=True)
             res.sigma_after.append([args.mutation_power_agent_0, args.mutation_power_agent_1])
         if hasattr(self.env, "n_resets"):
             self.env.n_resets = self.first_ordinal + self.gen * eng.per_gen
@@ -647,40 +640,29 @@ def es_cohort_bounds(n_local, K):
     return [2 * (k * n_local // K) for k in range(K)] + [2 * n_local] if K > 1 else None
 
 
-class DQNESEngine(_DQNSlabIO):
+class DQNESEngine(_DQNSlabIO, CoESUpdate):
+    _roles, _by_number = ROLES2, True   # (lists by role number; sigma: one tensor [2])
+    _partial_entry, _apply_entry = "coevo_dqn_es_partial", "coevo_dqn_es_apply"
+
     def __init__(self, pop, C, n_actions, T_train, T_eval, device="cuda", env_seed=SYNTH_SEED, philox_seed=0,
-                 shard=(0, 1), gather=None, first_ordinal=1, antithetic=False, centered_rank=False, chunks=8,
+                 shard=(0, 1), gather=None, first_ordinal=1, antithetic=False, centered_rank=False, chunks=ES_CHUNKS,
                  frames="device"):
         assert frames in ("device", "host")
         self.frames = frames
-        self.pop, self.C, self.n_actions, self.device = pop, C, n_actions, device
+        self.C, self.n_actions, self.device = C, n_actions, device
         self.Cw = C   # the streamed fc1 layout (one frame per task: v_mfma_f32_4x4x1, lane = output)
         self.T_train, self.T_eval = int(T_train), int(T_eval)
         self.philox_seed = int(philox_seed)
-        self.rank, self.world = shard
-        self.gather = gather
-        self.antithetic, self.centered_rank, self.chunks = bool(antithetic), bool(centered_rank), int(chunks)
-        if self.world > 1 and (pop % self.world or self.chunks % self.world):
-            raise ValueError(f"population {pop} and the {self.chunks} update chunks must both be divisible by the "
-                             f"number of ranks {self.world}")
-        if self.antithetic and pop % 2:
-            raise ValueError("antithetic pairs need an even population")
-        self.lo, self.hi = self.rank * pop // self.world, (self.rank + 1) * pop // self.world
-        self.n_local = self.hi - self.lo
+        self._shard_range(pop, shard, gather, chunks, antithetic, centered_rank)
         lib = L.load()
         self.stride = int(lib.coevo_dqn_slab_stride(C, n_actions))
         self.P = int(lib.coevo_dqn_param_count(C, n_actions))
-        self.base, total = slab_layout(ROLES2, (("base", 1), ("pert", self.n_local)), dict.fromkeys(ROLES2, self.stride))
+        strides = dict.fromkeys(ROLES2, self.stride)
+        self.base, total = slab_layout(ROLES2, (("base", 1), ("pert", self.n_local)), strides)
         self.slab = torch.zeros(total, dtype=torch.float32, device=device)
         self.per_gen = 2 * pop + N_EVAL
-        net_off = [self.base["first_0"]["base"], self.base["second_0"]["base"]]
-        games, ordinal0 = [], []
-        for j in range(self.n_local):
-            for ri, r in enumerate(ROLES2):
-                net_off.append(self.base[r]["pert"] + j * self.stride)
-                me = len(net_off) - 1
-                games.append((me, 1) if ri == 0 else (0, me))
-                ordinal0.append(first_ordinal + 2 * (self.lo + j) + ri)
+        net = NetTable(self.base, strides)
+        games, ordinal0, eval_games, eval_ordinal0 = co_es_games2(net, self.lo, self.hi, first_ordinal, pop)
         self.n_main = len(games)
         # two cohorts by default: one-frame tasks make this rollout fc1-bound (6.4 MB of weights per frame), and one
         # cohort's conv launch (matrix pipe) then runs under the other's fc1 stream (HBM): cfg 5 shard 9.5 vs 9.1
@@ -690,7 +672,7 @@ class DQNESEngine(_DQNSlabIO):
         if frames == "host":
             bounds = even_bounds(len(games), int(os.environ.get("COEVO_FRAME_COHORTS", "3")))
             bounds = [b - (b & 1) for b in bounds[:-1]] + [bounds[-1]]   # an individual's two games stay in one cohort
-        self.ro = cls(games, net_off, ordinal0, C, n_actions, self.slab, env_seed, self.per_gen, device, bounds=bounds)
+        self.ro = cls(games, net.net_off, ordinal0, C, n_actions, self.slab, env_seed, self.per_gen, device, bounds=bounds)
         self.ro.set_limits(np.full(self.n_main, self.T_train, dtype=np.int32))
         # the ten evaluation games of the updated base nets (one 10-frame task per agent-step) play on TILED twins of the two
         # base nets (fc1 laid out for v_mfma_f32_16x16x4: the narrow fc1 launch then has no cross-lane operand moves, 25 ->
@@ -698,9 +680,8 @@ class DQNESEngine(_DQNSlabIO):
         # COEVO_DQN_EVAL_TILED=0: evaluate on the slab itself (A/B)
         self.eval_tiled = os.environ.get("COEVO_DQN_EVAL_TILED", "1") != "0"
         self.eval_slab = torch.zeros(2 * self.stride, dtype=torch.float32, device=device) if self.eval_tiled else self.slab
-        self.eval_ro = cls([(0, 1)] * N_EVAL, [0, self.stride] if self.eval_tiled else net_off[:2],
-                           [first_ordinal + 2 * pop + j for j in range(N_EVAL)], C, n_actions, self.eval_slab, env_seed,
-                           self.per_gen, device, fc1_tiled=self.eval_tiled)
+        self.eval_ro = cls(eval_games, [0, self.stride] if self.eval_tiled else net.net_off[:2], eval_ordinal0, C, n_actions,
+                           self.eval_slab, env_seed, self.per_gen, device, fc1_tiled=self.eval_tiled)
         self.eval_ro.set_limits(np.full(N_EVAL, self.T_eval, dtype=np.int32))
         f32 = dict(dtype=torch.float32, device=device)
         self.gen_dev = torch.zeros(1, dtype=torch.int32, device=device)
@@ -713,10 +694,7 @@ class DQNESEngine(_DQNSlabIO):
         self.stats = torch.zeros(2, pop, 2, dtype=torch.float64, device=device)
         self.pblocks = int(lib.coevo_dqn_perturb_blocks(C, n_actions))
         self.dist_partial = torch.zeros(max(self.n_local, 1) * self.pblocks, dtype=torch.float64, device=device)
-        self.chunks_local = self.chunks // self.world
-        self.part_off = {r: ri * self.chunks_local * self.stride for ri, r in enumerate(ROLES2)}
-        self.part_block = 2 * self.chunks_local * self.stride
-        self.partials = torch.zeros(self.world * self.part_block, **f32)
+        self._partial_layout()
         self.game_idx = torch.stack([torch.arange(self.n_local, device=device) * 2 + ri for ri in range(2)])
         self.steps_per_generation = 2 * pop * self.T_train + N_EVAL * self.T_eval
         # the evaluation rollout as a replayed hipGraph; with several ranks (an RCCL process group alive beside the capture)
@@ -727,8 +705,8 @@ class DQNESEngine(_DQNSlabIO):
         self._eval_graph = None
 
     def generation(self, gen, sigmas, lr, fitness_sharing):
-        """perturb -> this rank's 2*n_local games -> (rewards, distances) gathered -> fitness -> chunk partial sums
-        gathered -> identical update on every rank -> 10 evaluation games -> mean evaluation rewards (host)"""
+        """perturb (with the distances to the base nets, finalized into stats) -> this rank's 2*n_local games -> the update
+        (population.CoESUpdate: identical on every rank) -> 10 evaluation games -> mean evaluation rewards (host)"""
         self.gen_dev.fill_(gen)
         self.sigma.copy_(torch.tensor([float(sigmas[0]), float(sigmas[1])], dtype=torch.float32))
         flags = 1 | (2 if self.antithetic else 0)
@@ -743,28 +721,7 @@ class DQNESEngine(_DQNSlabIO):
                        L._p(self.dist_local), 0, None)
                 self.stats[ri, lo:hi, 1] = self.dist_local[:self.n_local]
         self.ro.enqueue(self.T_train, self.gen_dev)
-        self.stats[:, lo:hi, 0] = self.ro.acc[self.game_idx, torch.arange(2, device=self.device)[:, None]]
-        if self.world > 1:
-            self.gather(self, "stats")
-        for ri, r in enumerate(ROLES2):
-            self.raw[ri].copy_(self.stats[ri, :, 0])
-            if fitness_sharing:
-                d = self.stats[ri, :, 1].to(torch.float32).contiguous()
-                L.call("coevo_sharing_score", L._p(d), self.pop, L._p(self.div[ri]))
-                self.raw[ri].div_(1.0 + self.div[ri])
-            if self.centered_rank:
-                L.call("coevo_centered_ranks", L._p(self.raw[ri]), self.pop, L._p(self.fitness[ri]))
-            else:
-                self.fitness[ri].copy_(self.raw[ri])
-            L.call("coevo_dqn_es_partial", self._ptr(r, "base"), self._ptr(r, "pert"), lo, self.C, self.n_actions,
-                   L._p(self.fitness[ri]), self.pop, self.chunks, self.rank * self.chunks_local, self.chunks_local,
-                   self.partials.data_ptr() + 4 * (self.rank * self.part_block + self.part_off[r]))
-        if self.world > 1:
-            self.gather(self, "partials")
-        for ri, r in enumerate(ROLES2):
-            L.call("coevo_dqn_es_apply", self._ptr(r, "base"), self.partials.data_ptr() + 4 * self.part_off[r],
-                   self.chunks, self.chunks_local, self.part_block, self.C, self.n_actions, self.pop,
-                   self.sigma.data_ptr() + 4 * ri, L.C.c_float(lr))
+        self.co_es_update(self.ro.acc[self.game_idx, torch.arange(2, device=self.device)[:, None]], lr, fitness_sharing)
         if self.eval_tiled:   # the updated base nets -> their tiled twins (two 6.75 MB copies)
             for ri, r in enumerate(ROLES2):
                 L.call("coevo_dqn_relayout", self._ptr(r, "base"), self.eval_slab.data_ptr() + 4 * ri * self.stride, 1, self.C,
@@ -788,16 +745,14 @@ class DQNESTrainer:
         self.env, self.args, self.collect = env, args, collect
         C, n = _env_shape(env, args)
         base = {r: dqn_init_flat(C, n) for r in ROLES2}
-        shard, gather = (0, 1), None
-        if dist_ctx is not None and dist_ctx.world > 1:
-            shard, gather = (dist_ctx.rank, dist_ctx.world), dist_ctx.gather_es
+        shard, gather = shard_and_gather(dist_ctx, "gather_es")
         self.first_ordinal = getattr(env, "n_resets", 1)
         self.eng = DQNESEngine(args.population, C, n, args.max_timesteps_per_episode, args.max_evaluation_steps,
                                env_seed=getattr(env, "seed_value", None) or SYNTH_SEED,
                                philox_seed=getattr(args, "coevo_seed", 0), shard=shard, gather=gather,
                                first_ordinal=self.first_ordinal, antithetic=getattr(args, "coevo_antithetic", False),
                                centered_rank=getattr(args, "coevo_centered_rank", False),
-                               chunks=getattr(args, "coevo_es_chunks", 8), frames=frames_mode(args))
+                               chunks=getattr(args, "coevo_es_chunks", ES_CHUNKS), frames=frames_mode(args))
         for r in ROLES2:
             self.eng.upload(r, "base", 0, base[r][None])
         self.res = DQNResult()
@@ -815,11 +770,7 @@ class DQNESTrainer:
         for s, r in enumerate(ROLES2):
             res.rewards[r].append(ev[s])
         if args.adaptive:
-            keep = getattr(args, "mutation_power_adversary", 0.0)
-            h = {"agent_0": res.rewards["first_0"], "agent_1": res.rewards["second_0"],
-                 "adversary_0": [0.0] * len(res.rewards["first_0"])}
-            adapt_mutation_power(args, self.gen, h)
-            args.mutation_power_adversary = keep
+            adapt_mutation_power2(args, self.gen, res.rewards, zero_adversary=False)
         res.sigma_after.append([args.mutation_power_agent_0, args.mutation_power_agent_1])
         res.seconds.append(time.perf_counter() - t0)
         self.gen += 1

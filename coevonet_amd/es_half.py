@@ -14,17 +14,13 @@ so the host's adaptive rule can sit on top.  ``ESTrainer`` / ``evolution_strateg
 the float16 route until the trainers are switched over."""
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
 from . import lib as L
-from .evolutionary_strategy import ES_CHUNKS
-from .genetic_algorithm import RET_SLOT
 from .mpe.simple_adversary import ENV_SEED
-from .population import N_EVAL, ROLE_D, ROLES, CoESSchedule, NetTable, SlabIO, co_es_games, slab_layout
-from .rollout import DeviceRollout, RolloutPlan, effective_steps
+from .population import ES_CHUNKS, N_EVAL, RET_SLOT, ROLE_D, ROLES, CoESSchedule, NetTable, SlabIO, co_es_games, slab_layout
+from .rollout import effective_steps
 
 
 class HalfESEngine(SlabIO, CoESSchedule):
@@ -66,13 +62,7 @@ class HalfESEngine(SlabIO, CoESSchedule):
         table = NetTable(self.base, self.stride, ROLE_D)
         games, eval_games = co_es_games(table, self.pop)   # (the evaluation games: a rollout of their own, after the update)
         self.n_main = len(games)
-        heavy_rows = int(os.environ.get("COEVO_HEAVY_ROWS", "32"))
-        es_cohorts = int(os.environ.get("COEVO_ES_COHORTS", "2"))
-        self.plan = RolloutPlan(np.array(games), table.net_off, table.net_D, device=device, heavy_rows=heavy_rows,
-                                n_cohorts=es_cohorts, row_order="class")
-        self.ro = DeviceRollout(self.plan, self.slab, env_seed=env_seed, precision="float16")
-        self.eval_plan = RolloutPlan(np.array(eval_games), table.net_off, table.net_D, device=device, split_rows=5)
-        self.eval_ro = DeviceRollout(self.eval_plan, self.slab, env_seed=env_seed, precision="float16")
+        self._rollout_pair(games, eval_games, table, env_seed, precision="float16")
         # ---- small device buffers ----------------------------------------------------------------------------------
         f32 = dict(dtype=torch.float32, device=device)
         self.fitness = {r: torch.zeros(self.pop, **f32) for r in ROLES}   # fit16: fp16 values in fp32 words

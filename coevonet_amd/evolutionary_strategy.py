@@ -33,10 +33,10 @@ import torch
 
 from . import lib as L
 from .game_logic import create_agent
-from .genetic_algorithm import N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, adapt_mutation_power
 from .mpe.simple_adversary import ENV_SEED
-from .population import CoESSchedule, NetTable, SlabIO, co_es_games, slab_layout
-from .rollout import DeviceRollout, HostEnvRollout, RolloutPlan, effective_steps
+from .population import (ES_CHUNKS, N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, CoESSchedule, CoESUpdate, NetTable, SlabIO,
+                         adapt_mutation_power, co_es_games, shard_and_gather, slab_layout)
+from .rollout import DeviceRollout, HostEnvRollout, effective_steps
 
 
 # ---- the reference's per-call helpers under their own names (evolutionary_strategy.py:11-148): sequential, on the host
@@ -88,26 +88,12 @@ def compute_weight_update(noises, rewards, args, role, individual_weights=None, 
     return update.astype(dt), diversity
 
 
-ES_CHUNKS = 8   # the canonical ES summation: this many chunk sums, added left to right (include/coevo.h, K5)
-
-
-class ESEngine(SlabIO, CoESSchedule):
+class ESEngine(SlabIO, CoESSchedule, CoESUpdate):
     def __init__(self, pop, limit_train=None, limit_eval=None, max_cycles=25, device="cuda", env_seed=ENV_SEED,
                  rng="device_philox", philox_seed=0, env="device", first_ordinal=1, shard=(0, 1), gather=None,
                  antithetic=False, centered_rank=False, chunks=ES_CHUNKS):
-        self.pop, self.rng_mode, self.philox_seed, self.env_mode, self.device = pop, rng, int(philox_seed), env, device
-        self.rank, self.world = shard
-        self.gather = gather
-        self.antithetic, self.centered_rank, self.chunks = bool(antithetic), bool(centered_rank), int(chunks)
-        if self.world > 1 and (pop % self.world or self.chunks % self.world):
-            raise ValueError(f"population {pop} and the {self.chunks} update chunks must both be divisible by the "
-                             f"number of ranks {self.world}")
-        if (self.antithetic or self.centered_rank or self.world > 1) and rng != "device_philox":
-            raise ValueError("the extension mode and the sharded run need device_philox offspring")
-        if self.antithetic and pop % 2:
-            raise ValueError("antithetic pairs need an even population")
-        self.lo, self.hi = self.rank * pop // self.world, (self.rank + 1) * pop // self.world
-        self.n_local = self.hi - self.lo
+        self.rng_mode, self.philox_seed, self.env_mode, self.device = rng, int(philox_seed), env, device
+        self._shard_range(pop, shard, gather, chunks, antithetic, centered_rank, rng)
         self.T_train = effective_steps(limit_train, max_cycles)
         self.T_eval = effective_steps(limit_eval, max_cycles)
         self.n_cycles = (max(self.T_train, self.T_eval) + 2) // 3
@@ -119,23 +105,9 @@ class ESEngine(SlabIO, CoESSchedule):
         table = NetTable(self.base, self.stride, ROLE_D)
         games, eval_games = co_es_games(table, self.n_local)   # (the evaluation games: a rollout of their own, after the update)
         self.n_main = len(games)
-        cls = DeviceRollout if env == "device" else HostEnvRollout
-        heavy_rows = int(os.environ.get("COEVO_HEAVY_ROWS", "32"))
-        # device env: 2 cohorts (114 vs 109 generations/s at cfg3); env on the host cores: COEVO_HOST_COHORTS alternating
-        # cohorts (default 4), rows numbered cohort by cohort (one contiguous observation / action range each)
-        es_cohorts = (int(os.environ.get("COEVO_ES_COHORTS", "2")) if env == "device"
-                      else int(os.environ.get("COEVO_HOST_COHORTS", "4")))
-        game_cohort = None
-        if env != "device" and es_cohorts > 1 and len(games) >= es_cohorts:
-            # contiguous game ranges (a core then owns whole cache lines of the struct-of-arrays game state)
-            game_cohort = (np.arange(len(games)) * es_cohorts // len(games)).astype(np.int32)
-        self.plan = RolloutPlan(np.array(games), table.net_off, table.net_D, device=device, heavy_rows=heavy_rows,
-                                n_cohorts=es_cohorts, game_cohort=game_cohort,
-                                row_order="class" if env == "device" else "cohort")
-        self.ro = cls(self.plan, self.slab, env_seed=env_seed)
-        # the 10 evaluation games: three nets x 10 rows, as two 5-row streaming tasks per net (1.0 -> 0.5 ms)
-        self.eval_plan = RolloutPlan(np.array(eval_games), table.net_off, table.net_D, device=device, split_rows=5)
-        self.eval_ro = cls(self.eval_plan, self.slab, env_seed=env_seed)
+        # env on the host cores: COEVO_HOST_COHORTS alternating cohorts (default 4)
+        host_cohorts = None if env == "device" else int(os.environ.get("COEVO_HOST_COHORTS", "4"))
+        self._rollout_pair(games, eval_games, table, env_seed, DeviceRollout if env == "device" else HostEnvRollout, host_cohorts)
         f32 = dict(dtype=torch.float32, device=device)
         self.fitness = {r: torch.zeros(pop, **f32) for r in ROLES}
         self.raw = {r: torch.zeros(pop, **f32) for r in ROLES}
@@ -147,14 +119,7 @@ class ESEngine(SlabIO, CoESSchedule):
         self.ret_slot = torch.tensor([RET_SLOT[r] for r in ROLES], device=device)
         # per individual (reward in the role's slot, distance to the base net), all roles: what the ranks exchange
         self.stats = torch.zeros(3, pop, 2, dtype=torch.float64, device=device)
-        # chunk partial sums of the update, rank-major: [world][role][chunks/world][stride_role]
-        self.chunks_local = self.chunks // self.world
-        self.part_off, o = {}, 0
-        for r in ROLES:
-            self.part_off[r] = o
-            o += self.chunks_local * self.stride[r]
-        self.part_block = o
-        self.partials = torch.zeros(self.world * self.part_block, **f32)
+        self._partial_layout()
         self.steps_per_generation = 3 * pop * self.T_train + N_EVAL * self.T_eval
 
     def perturb_device(self, gen, sigmas):
@@ -165,37 +130,16 @@ class ESEngine(SlabIO, CoESSchedule):
             L.call("coevo_fc_perturb_flags", self._ptr(r, "base"), L._p(self.zero_idx), self._ptr(r, "pert"), 0,
                    self.n_local, ROLE_D[r], L._p(self.sigma[r]), self.philox_seed, self.lo, gen * 4 + ri, flags)
 
+    def _local_distances(self):
+        for ri, r in enumerate(ROLES):
+            L.call("coevo_fc_distance", self._ptr(r, "base"), self._ptr(r, "pert"), self.n_local, ROLE_D[r],
+                   L._p(self.dist_local[r]))
+            self.stats[ri, self.lo:self.hi, 1] = self.dist_local[r][:self.n_local]
+
     def update_device(self, gen, lr, fitness_sharing):
-        """compute_weight_update (evolutionary_strategy.py:120-148) + base += update, on the device.  Sharded: the
-        (reward, distance) pairs and then the chunk partial sums are all-gathered; every rank applies the same update."""
+        """the update of generation `gen` from the training rollout's rewards (population.CoESUpdate)"""
         rew = self.ro.rewards if torch.is_tensor(self.ro.rewards) else torch.from_numpy(self.ro.rewards).to(self.device)
-        lo, hi = self.lo, self.hi
-        self.stats[:, lo:hi, 0] = rew[self.game_idx, self.ret_slot[:, None]]
-        if fitness_sharing:
-            for ri, r in enumerate(ROLES):
-                L.call("coevo_fc_distance", self._ptr(r, "base"), self._ptr(r, "pert"), self.n_local, ROLE_D[r],
-                       L._p(self.dist_local[r]))
-                self.stats[ri, lo:hi, 1] = self.dist_local[r][:self.n_local]
-        if self.world > 1:
-            self.gather(self, "stats")
-        for ri, r in enumerate(ROLES):
-            self.raw[r].copy_(self.stats[ri, :, 0])                  # np.array(rewards, dtype=float32)
-            if fitness_sharing:
-                d = self.stats[ri, :, 1].to(torch.float32).contiguous()
-                L.call("coevo_sharing_score", L._p(d), self.pop, L._p(self.div[r]))
-                self.raw[r].div_(1.0 + self.div[r])
-            if self.centered_rank:
-                L.call("coevo_centered_ranks", L._p(self.raw[r]), self.pop, L._p(self.fitness[r]))
-            else:
-                self.fitness[r].copy_(self.raw[r])
-            L.call("coevo_es_partial", self._ptr(r, "base"), self._ptr(r, "pert"), lo, ROLE_D[r],
-                   L._p(self.fitness[r]), self.pop, self.chunks, self.rank * self.chunks_local, self.chunks_local,
-                   self.partials.data_ptr() + 4 * (self.rank * self.part_block + self.part_off[r]))
-        if self.world > 1:
-            self.gather(self, "partials")
-        for ri, r in enumerate(ROLES):
-            L.call("coevo_es_apply", self._ptr(r, "base"), self.partials.data_ptr() + 4 * self.part_off[r], self.chunks,
-                   self.chunks_local, self.part_block, ROLE_D[r], self.pop, L._p(self.sigma[r]), L.C.c_float(lr))
+        self.co_es_update(rew[self.game_idx, self.ret_slot[:, None]], lr, fitness_sharing)
 
 
 class ESResult:
@@ -225,9 +169,7 @@ class ESTrainer:
         env_mode = env_mode or getattr(args, "coevo_env", "device")
         self.first_ordinal = getattr(env, "n_resets", 1)
         agents = {r: create_agent(env, args, role=r) for r in ROLES}  # evolutionary_strategy.py:163-165
-        shard, gather = (0, 1), None
-        if dist_ctx is not None and dist_ctx.world > 1:
-            shard, gather = (dist_ctx.rank, dist_ctx.world), dist_ctx.gather_es
+        shard, gather = shard_and_gather(dist_ctx, "gather_es")
         self.eng = ESEngine(args.population, args.max_timesteps_per_episode, args.max_evaluation_steps,
                             max_cycles=getattr(env, "max_cycles", 25), rng=self.rng,
                             philox_seed=getattr(args, "coevo_seed", 0), env=env_mode,

@@ -34,13 +34,12 @@ from . import lib as L
 from .fcnetwork import FCNetwork
 from .game_logic import create_agent
 from .mpe.simple_adversary import ENV_SEED
-from .population import (N_EVAL, RET_SLOT, ROLE_D, ROLES, CoGASchedule, CoGATail, NetTable, SlabIO, captured, co_ga_games,
-                         eval_gate_limits, mean_eval_triple, slab_layout)
+from .population import (N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, CoGASchedule, CoGATail, NetTable, SlabIO,
+                         adapt_mutation_power, captured, co_ga_games, eval_gate_limits, mean_eval_triple, shard_and_gather,
+                         slab_layout)
 from .rollout import DeviceRollout, HostEnvRollout, RolloutPlan, effective_steps
 
 ROLE_SLOT = {"agent_0": 1, "agent_1": 2, "adversary_0": 0}   # env slot the role acts in
-SIGMA_ATTR = {"agent_0": "mutation_power_agent_0", "agent_1": "mutation_power_agent_1",
-              "adversary_0": "mutation_power_adversary"}
 
 
 # ---- the reference's per-call helpers under their own names (genetic_algorithm.py:12-48): the sequential forms a caller of
@@ -67,24 +66,6 @@ def mutate_elites(env, elites, args, role):
         child.mutate(sigma)
         children.append(child)
     return children
-
-
-def adapt_mutation_power(args, gen, hist):
-    """genetic_algorithm.py:323-345 (evolutionary_strategy.py:292-316 is identical), quirk Q5 included."""
-    def worse(h):
-        return gen > 10 and np.mean(h[-10:]) < np.mean(h[-20:-10])
-    if worse(hist["agent_0"]):
-        args.mutation_power_agent_0 = min(args.mutation_power_agent_1 * 1.2, args.max_mutation_power)
-    else:
-        args.mutation_power_agent_0 = max(args.mutation_power_agent_0 * 0.95, args.min_mutation_power)
-    if worse(hist["agent_1"]):
-        args.mutation_power_agent_1 = min(args.mutation_power_agent_1 * 1.2, args.max_mutation_power)
-    else:
-        args.mutation_power_agent_1 = max(args.mutation_power_agent_1 * 0.95, args.min_mutation_power)
-    if worse(hist["adversary_0"]):
-        args.mutation_power_adversary = min(args.mutation_power_adversary * 1.2, args.max_mutation_power)
-    else:
-        args.mutation_power_adversary = max(args.mutation_power_adversary * 0.95, args.min_mutation_power)
 
 
 def small_shard_rows(n_local, hof, cus, pop):
@@ -748,10 +729,8 @@ class GATrainer:
         env_mode = env_mode or getattr(args, "coevo_env", "device")
         self.first_ordinal = getattr(env, "n_resets", 1)
         pop_flat, hof_flat = initial_population(env, args)
-        shard, gather, gather_packed = (0, 1), None, None
-        if dist_ctx is not None and dist_ctx.world > 1:
-            shard, gather = (dist_ctx.rank, dist_ctx.world), dist_ctx.gather_ga
-            gather_packed = getattr(dist_ctx, "gather_ga_packed", None)
+        shard, gather = shard_and_gather(dist_ctx, "gather_ga")
+        gather_packed = getattr(dist_ctx, "gather_ga_packed", None) if gather else None
         # the host-free generation loop needs device-built offspring, the device env and a single rank
         self.device_loop = (self.rng == "device_philox" and env_mode == "device" and shard == (0, 1)
                             and getattr(args, "coevo_device_loop", True))

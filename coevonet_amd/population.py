@@ -1,26 +1,33 @@
 """What the population engines share: the slab layout, the numbering of the weight sets a rollout reads, the game tables
-of Co-GA and Co-ES, the evaluation mean and gate, graph capture, the slab I/O calls, the per-generation rollout schedules and
-the Co-GA generation tail of the fully connected engines.
+of Co-GA and Co-ES, the evaluation mean and gate, graph capture, the slab I/O calls, the per-generation rollout schedules, the
+Co-GA generation tail of the fully connected engines, the Co-ES update of the float32 engines and the trainers' sigma rule.
 
 GAEngine / HalfGAEngine (genetic_algorithm.py, ga_half.py), ESEngine / HalfESEngine (evolutionary_strategy.py, es_half.py)
 and DQNGAEngine / HalfDQNGAEngine / DQNESEngine (dqn_population.py, dqn_ga_half.py) differ in precision, strides and kernels,
 not in who plays whom: the seat rules of the reference's generation bodies are written ONCE, here.  slab_layout, NetTable,
-co_ga_games, co_ga_games2, co_es_games, mean_eval and eval_gate_limits are plain python - they touch neither torch nor the
-library, which this module imports for captured() and the mixins only - and are pinned by tests/test_population_cpu.py; the
-mixins hold the calls the engines made identically (tests/test_ga_launch_scripts_cpu.py: recorded before they were shared).
+co_ga_games, co_ga_games2, co_es_games, co_es_games2, mean_eval, eval_gate_limits and the sigma rule are plain python - they
+touch neither torch nor the library, which this module imports for captured() and the mixins only - and are pinned by
+tests/test_population_cpu.py; the mixins hold the calls the engines made identically (tests/test_ga_launch_scripts_cpu.py,
+tests/test_es_launch_scripts_cpu.py: recorded before they were shared).
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
 
 from . import lib as L
+from .rollout import DeviceRollout, RolloutPlan
 
 ROLES = ("agent_0", "agent_1", "adversary_0")
 ROLE_D = {"agent_0": 10, "agent_1": 10, "adversary_0": 8}
 RET_SLOT = {"agent_0": 0, "agent_1": 1, "adversary_0": 2}    # position in play_game's return triple
 ROLES2 = ("first_0", "second_0")   # the two-player Atari games (DeepQN engines)
 N_EVAL = 10
+ES_CHUNKS = 8   # the canonical ES summation: this many chunk sums, added left to right (include/coevo.h, K5)
+SIGMA_ATTR = {"agent_0": "mutation_power_agent_0", "agent_1": "mutation_power_agent_1",
+              "adversary_0": "mutation_power_adversary"}
 
 
 def slab_layout(roles, regions, stride_of):
@@ -109,6 +116,22 @@ def co_es_games(net, n):
     # (evolutionary_strategy.py:272-316).  They get their own 10-game rollout after each update.
     eval_games = [(net("base", "adversary_0"), net("base", "agent_0"), net("base", "agent_1"))] * N_EVAL
     return games, eval_games
+
+
+def co_es_games2(net, lo, hi, first_ordinal, pop):
+    """The two-role Co-ES generation of the individuals [lo, hi) of a population of `pop` -> (games as (first_0, second_0)
+    net ids, the reset ordinal of each game in generation 0, the N_EVAL evaluation games of the base pair, their ordinals):
+    the two base nets are numbered first, then game 2j + role seats perturbed net j of the role (rank-local slab index
+    j - lo; ordinal first_ordinal + 2j + role, whichever shard plays it) against the other role's base net; the evaluation
+    games take the ordinals behind the population's main games."""
+    base = [net("base", r) for r in ROLES2]
+    games, ordinal0 = [], []
+    for j in range(lo, hi):
+        for ri, r in enumerate(ROLES2):
+            me = net("pert", r, j - lo)
+            games.append((me, base[1]) if ri == 0 else (base[0], me))
+            ordinal0.append(first_ordinal + 2 * j + ri)
+    return games, ordinal0, [tuple(base)] * N_EVAL, [first_ordinal + 2 * pop + j for j in range(N_EVAL)]
 
 
 def mean_eval(rewards, n_slots):
@@ -334,7 +357,23 @@ class CoGATail:
 
 class CoESSchedule:
     """The Co-ES training and evaluation rollouts of one generation (game ordinal 3j + role, then the evaluation games).
-    Needs pop, lo, n_main, first_ordinal, T_train, T_eval, env_mode, plan, ro, eval_ro."""
+    Needs pop, lo, n_main, first_ordinal, T_train, T_eval, env_mode, slab, device; _rollout_pair gives plan, ro, eval_ro."""
+
+    def _rollout_pair(self, games, eval_games, table, env_seed, cls=DeviceRollout, host_cohorts=None, **ro_kw):
+        """plan / ro and eval_plan / eval_ro over self.slab.  Device env: 2 cohorts (COEVO_ES_COHORTS; 114 vs 109 generations/s
+        at cfg3).  host_cohorts (env on the host cores): that many alternating cohorts of contiguous game ranges (a core then owns
+        whole cache lines of the struct-of-arrays game state), rows numbered cohort by cohort (one observation / action range)."""
+        cohorts = int(os.environ.get("COEVO_ES_COHORTS", "2")) if host_cohorts is None else host_cohorts
+        game_cohort = None
+        if host_cohorts is not None and cohorts > 1 and len(games) >= cohorts:
+            game_cohort = (np.arange(len(games)) * cohorts // len(games)).astype(np.int32)
+        self.plan = RolloutPlan(np.array(games), table.net_off, table.net_D, device=self.device,
+                                heavy_rows=int(os.environ.get("COEVO_HEAVY_ROWS", "32")), n_cohorts=cohorts,
+                                game_cohort=game_cohort, row_order="class" if host_cohorts is None else "cohort")
+        self.ro = cls(self.plan, self.slab, env_seed=env_seed, **ro_kw)
+        # the 10 evaluation games: three nets x 10 rows, as two 5-row streaming tasks per net (1.0 -> 0.5 ms)
+        self.eval_plan = RolloutPlan(np.array(eval_games), table.net_off, table.net_D, device=self.device, split_rows=5)
+        self.eval_ro = cls(self.eval_plan, self.slab, env_seed=env_seed, **ro_kw)
 
     def _ordinal_base(self, gen):
         return self.first_ordinal + gen * (3 * self.pop + N_EVAL)
@@ -368,3 +407,100 @@ class CoESSchedule:
 
     def rewards_host(self):
         return _host(self.ro.rewards)
+
+
+class CoESUpdate:
+    """The Co-ES update of the float32 engines after the training rollout, written once: rewards (and distances) into ``stats``,
+    gathered; per role the fitness and the chunk partial sums of the update, gathered; per role the update applied.  A class
+    names its roles, its partial-sum and apply entry points (their shape arguments: SlabIO._net_args), whether its buffers per
+    role (raw, fitness, div, sigma) are indexed by role or ``_by_number`` and, where the distances are not in ``stats`` by then,
+    ``_local_distances``.  Also written once: the shard range with its refusals and the partial-sum layout."""
+    _roles, _by_number = ROLES, False
+    _partial_entry, _apply_entry = "coevo_es_partial", "coevo_es_apply"
+
+    def _shard_range(self, pop, shard, gather, chunks, antithetic, centered_rank, rng="device_philox"):
+        """this rank's individuals [lo, hi), after refusing what a Co-ES engine cannot shard or pair"""
+        self.pop, self.gather, (self.rank, self.world) = pop, gather, shard
+        self.antithetic, self.centered_rank, self.chunks = bool(antithetic), bool(centered_rank), int(chunks)
+        if self.world > 1 and (pop % self.world or self.chunks % self.world):
+            raise ValueError(f"population {pop} and the {self.chunks} update chunks must both be divisible by the "
+                             f"number of ranks {self.world}")
+        if (self.antithetic or self.centered_rank or self.world > 1) and rng != "device_philox":
+            raise ValueError("the extension mode and the sharded run need device_philox offspring")
+        if self.antithetic and pop % 2:
+            raise ValueError("antithetic pairs need an even population")
+        self.lo, self.hi = self.rank * pop // self.world, (self.rank + 1) * pop // self.world
+        self.n_local = self.hi - self.lo
+
+    def _partial_layout(self):
+        """chunk partial sums of the update, rank-major: [world][role][chunks/world][stride_role]"""
+        self.chunks_local = self.chunks // self.world
+        self.part_off, o = {}, 0
+        for r in self._roles:
+            self.part_off[r] = o
+            o += self.chunks_local * _per_role(self.stride, r)
+        self.part_block = o
+        self.partials = torch.zeros(self.world * self.part_block, dtype=torch.float32, device=self.device)
+
+    def _local_distances(self):
+        """this rank's distances to the base nets into stats[:, lo:hi, 1], where they are not there yet"""
+
+    def co_es_update(self, rewards, lr, fitness_sharing):
+        """compute_weight_update (evolutionary_strategy.py:120-148) + base += update on the device, from rewards [role][n_local].
+        Sharded: the (reward, distance) pairs, then the chunk partial sums are all-gathered; every rank applies the same update."""
+        self.stats[:, self.lo:self.hi, 0] = rewards
+        if fitness_sharing:
+            self._local_distances()
+        if self.world > 1:
+            self.gather(self, "stats")
+        for ri, r in enumerate(self._roles):
+            k = ri if self._by_number else r
+            raw, fitness, div = self.raw[k], self.fitness[k], self.div[k]
+            raw.copy_(self.stats[ri, :, 0])                  # np.array(rewards, dtype=float32)
+            if fitness_sharing:
+                d = self.stats[ri, :, 1].to(torch.float32).contiguous()
+                L.call("coevo_sharing_score", L._p(d), self.pop, L._p(div))
+                raw.div_(1.0 + div)
+            if self.centered_rank:
+                L.call("coevo_centered_ranks", L._p(raw), self.pop, L._p(fitness))
+            else:
+                fitness.copy_(raw)
+            L.call(self._partial_entry, self._ptr(r, "base"), self._ptr(r, "pert"), self.lo, *self._net_args(r), L._p(fitness),
+                   self.pop, self.chunks, self.rank * self.chunks_local, self.chunks_local,
+                   self.partials.data_ptr() + 4 * (self.rank * self.part_block + self.part_off[r]))
+        if self.world > 1:
+            self.gather(self, "partials")
+        for ri, r in enumerate(self._roles):
+            L.call(self._apply_entry, self._ptr(r, "base"), self.partials.data_ptr() + 4 * self.part_off[r], self.chunks,
+                   self.chunks_local, self.part_block, *self._net_args(r), self.pop,
+                   L._p(self.sigma[ri if self._by_number else r]), L.C.c_float(lr))
+
+
+# ---- what the trainers share
+def adapt_mutation_power(args, gen, hist):
+    """genetic_algorithm.py:323-345 (evolutionary_strategy.py:292-316 is identical): a role whose last 10 evaluation means are
+    worse than the 10 before them grows its sigma, any other shrinks it; quirk Q5: agent_0 grows from agent_1's sigma."""
+    for role, grows_from in (("agent_0", "agent_1"), ("agent_1", "agent_1"), ("adversary_0", "adversary_0")):
+        h, attr = hist[role], SIGMA_ATTR[role]
+        if gen > 10 and np.mean(h[-10:]) < np.mean(h[-20:-10]):
+            setattr(args, attr, min(getattr(args, SIGMA_ATTR[grows_from]) * 1.2, args.max_mutation_power))
+        else:
+            setattr(args, attr, max(getattr(args, attr) * 0.95, args.min_mutation_power))
+
+
+def adapt_mutation_power2(args, gen, rewards, zero_adversary):
+    """the sigma rule over the two-player games: first_0 takes agent_0's part, second_0 agent_1's, a history of zeros the
+    adversary's, whose sigma comes back as it was.  zero_adversary: the rule sees 0.0, not the caller's value (then required)"""
+    keep = getattr(args, "mutation_power_adversary", 0.0)
+    h = {"agent_0": rewards["first_0"], "agent_1": rewards["second_0"], "adversary_0": [0.0] * len(rewards["first_0"])}
+    if zero_adversary:
+        args.mutation_power_adversary = 0.0
+    adapt_mutation_power(args, gen, h)
+    args.mutation_power_adversary = keep
+
+
+def shard_and_gather(dist_ctx, name):
+    """-> (shard, gather callback `name` of the context): one rank without a context or in a world of one"""
+    if dist_ctx is not None and dist_ctx.world > 1:
+        return (dist_ctx.rank, dist_ctx.world), getattr(dist_ctx, name)
+    return (0, 1), None

@@ -6,6 +6,7 @@ element.  The seat rules are then stated once more, independently, as a closed f
 import json
 import os
 
+import numpy as np
 import pytest
 
 from coevonet_amd import population as P
@@ -258,13 +259,216 @@ def test_the_engines_share_the_functions_instead_of_copies():
     for name in ("_rollout", "_initial_distance", "_breed_children", "_finalize_entry", "_slab_dtype", "_pack_unpack"):
         assert getattr(D16, name) is not getattr(D32, name), name
     import inspect
-    for mod in (dqn_population, dqn_ga_half):   # both take their table from co_ga_games2: neither module builds one
-        src = inspect.getsource(mod).split("class DQNESEngine")[0]
+    for mod in (dqn_population, dqn_ga_half, genetic_algorithm, ga_half, evolutionary_strategy, es_half):
+        src = inspect.getsource(mod)   # every engine takes its table from this module: no engine module builds one
         assert "ordinal0.append" not in src and "games.append" not in src
     assert dqn_population.co_ga_games2 is P.co_ga_games2 and "co_ga_games2(" in inspect.getsource(D32.__init__)
     assert "co_ga_games2" not in inspect.getsource(dqn_ga_half) and D16.__init__ is not D32.__init__
     for mod in (genetic_algorithm, ga_half, evolutionary_strategy, es_half):
         assert (mod.ROLES, mod.ROLE_D, mod.N_EVAL) == (P.ROLES, P.ROLE_D, P.N_EVAL)
+    # Co-ES: one two-role table builder, one update sequence for the two float32 engines, one rollout pair for the two fully
+    # connected ones; the float16 engine keeps its own update (other kernels, noise drawn again, one rank)
+    ES32, ES16, DES = evolutionary_strategy.ESEngine, es_half.HalfESEngine, dqn_population.DQNESEngine
+    assert dqn_population.co_es_games2 is P.co_es_games2 and "co_es_games2(" in inspect.getsource(DES.__init__)
+    assert "NetTable(" in inspect.getsource(DES.__init__)
+    for cls in (ES32, DES):
+        assert issubclass(cls, P.CoESUpdate)
+        for name in ("co_es_update", "_shard_range", "_partial_layout"):
+            assert getattr(cls, name) is getattr(P.CoESUpdate, name), name
+    assert not issubclass(ES16, P.CoESUpdate) and "coevo_es16_partial" in inspect.getsource(ES16.update)
+    assert ES32._local_distances is not P.CoESUpdate._local_distances and DES._local_distances is P.CoESUpdate._local_distances
+    assert (ES32._roles, ES32._by_number, ES32._partial_entry, ES32._apply_entry) == (P.ROLES, False, "coevo_es_partial",
+                                                                                     "coevo_es_apply")
+    assert (DES._roles, DES._by_number, DES._partial_entry, DES._apply_entry) == (P.ROLES2, True, "coevo_dqn_es_partial",
+                                                                                  "coevo_dqn_es_apply")
+    assert DES._net_args is dqn_population._DQNSlabIO._net_args and ES32._net_args is P.SlabIO._net_args
+    for fn in (ES32.update_device, DES.generation):   # neither holds the update sequence any more
+        src = inspect.getsource(fn)
+        assert "co_es_update(" in src and "gather(" not in src and "coevo_sharing_score" not in src and "_es_apply" not in src
+    for cls in (ES32, ES16):
+        assert cls._rollout_pair is P.CoESSchedule._rollout_pair and "_rollout_pair(" in inspect.getsource(cls.__init__)
+        assert "RolloutPlan(" not in inspect.getsource(cls.__init__)
+    for mod in (evolutionary_strategy, es_half, dqn_population):
+        assert mod.ES_CHUNKS is P.ES_CHUNKS and P.ES_CHUNKS == 8
+        assert "chunks=8" not in inspect.getsource(mod) and '"coevo_es_chunks", 8' not in inspect.getsource(mod)
+    # the ES modules take the shared names from this module, not through genetic_algorithm
+    assert "from .genetic_algorithm" not in inspect.getsource(es_half)
+    assert "from .genetic_algorithm import N_EVAL" not in inspect.getsource(evolutionary_strategy)
+    assert evolutionary_strategy.RET_SLOT is es_half.RET_SLOT is P.RET_SLOT
+    # the trainers: one shard prologue, one sigma rule and its two-role adapter
+    for mod in (genetic_algorithm, evolutionary_strategy, dqn_population):
+        assert mod.shard_and_gather is P.shard_and_gather and "dist_ctx.world" not in inspect.getsource(mod)
+    assert inspect.getsource(dqn_population).count("shard_and_gather(dist_ctx") == 2
+    assert genetic_algorithm.adapt_mutation_power is evolutionary_strategy.adapt_mutation_power is P.adapt_mutation_power
+    assert genetic_algorithm.SIGMA_ATTR is P.SIGMA_ATTR
+    assert dqn_population.adapt_mutation_power2 is P.adapt_mutation_power2 and not hasattr(dqn_population, "adapt_mutation_power")
+    assert "zero_adversary=True" in inspect.getsource(dqn_population.DQNGATrainer.finish)
+    assert "zero_adversary=False" in inspect.getsource(dqn_population.DQNESTrainer.step)
+
+
+@pytest.mark.parametrize("lo,hi,pop,want", [
+    (0, 3, 3, dict(net_off=[0, 4, 1, 5, 2, 6, 3, 7], games=[(2, 1), (0, 3), (4, 1), (0, 5), (6, 1), (0, 7)],
+                   ordinal0=[7, 8, 9, 10, 11, 12], eval_ordinal0=list(range(13, 23)))),
+    (2, 4, 4, dict(net_off=[0, 3, 1, 4, 2, 5], games=[(2, 1), (0, 3), (4, 1), (0, 5)],
+                   ordinal0=[11, 12, 13, 14], eval_ordinal0=list(range(15, 25))))])
+def test_co_es_two_role_table_against_the_literal_tables(lo, hi, pop, want):
+    """the two base nets are ids 0 and 1, the perturbed nets follow individual-major, role-minor (slab index rank-local); game
+    2j + role seats perturbed net j of the role in its own seat against the other role's base net, under ordinal first + 2j +
+    role of the seeded stream, whichever shard plays it; the evaluation games of the base pair come behind the population's"""
+    ones = dict.fromkeys(P.ROLES2, 1)
+    t = P.NetTable(P.slab_layout(P.ROLES2, [("base", 1), ("pert", hi - lo)], ones)[0], ones)
+    games, ordinal0, eval_games, eval_ordinal0 = P.co_es_games2(t, lo, hi, 7, pop)
+    assert t.net_off == want["net_off"] and t.net_D == []
+    assert games == want["games"] and ordinal0 == want["ordinal0"]
+    assert eval_games == [(0, 1)] * N_EVAL and eval_ordinal0 == want["eval_ordinal0"]
+    seats, _, eval_seats, _ = P.co_es_games2(Seats(), lo, hi, 7, pop)
+    for g, (f0, s0) in enumerate(seats):
+        own, opp = ("pert", P.ROLES2[g % 2], g // 2), ("base", P.ROLES2[1 - g % 2], 0)
+        assert (f0, s0) == ((own, opp) if g % 2 == 0 else (opp, own)), g
+    assert eval_seats == [(("base", "first_0", 0), ("base", "second_0", 0))] * N_EVAL
+
+
+def bare_update(**attrs):
+    e = P.CoESUpdate()
+    e.device = "cpu"
+    for k, v in attrs.items():
+        setattr(e, k, v)
+    return e
+
+
+@pytest.mark.parametrize("world,chunks_local,part_off,block", [(1, 8, [0, 24, 64], 80), (2, 4, [0, 12, 32], 40)])
+def test_co_es_partial_layout_is_rank_major_role_by_role(world, chunks_local, part_off, block):
+    """[world][role][chunks / world][stride of the role], in 32-bit words: a rank's block shrinks with the world, the whole
+    does not"""
+    e = bare_update(stride={"agent_0": 3, "agent_1": 5, "adversary_0": 2}, chunks=8, world=world)
+    e._partial_layout()
+    assert (e.chunks_local, e.part_block) == (chunks_local, block) and e.part_off == dict(zip(ROLES, part_off))
+    assert e.partials.shape == (80,) and str(e.partials.dtype) == "torch.float32" and not e.partials.any()
+    # the DeepQN engine: two roles, one stride
+    d = bare_update(stride=7, chunks=8, world=world, _roles=P.ROLES2)
+    d._partial_layout()
+    assert d.part_off == {"first_0": 0, "second_0": chunks_local * 7} and d.part_block == 2 * chunks_local * 7
+    assert d.partials.numel() == 2 * 8 * 7
+
+
+def test_co_es_shard_range_and_its_refusals():
+    e = bare_update()
+    e._shard_range(4, (1, 2), "cb", 8, False, True)
+    assert (e.pop, e.rank, e.world, e.lo, e.hi, e.n_local, e.gather, e.chunks) == (4, 1, 2, 2, 4, 2, "cb", 8)
+    assert (e.antithetic, e.centered_rank) == (False, True)
+    e._shard_range(3, (0, 1), None, 8, False, False, rng="host_reference")   # one rank, no extension: any noise source
+    assert (e.lo, e.hi, e.n_local, e.gather) == (0, 3, 3, None)
+    e._shard_range(6, (2, 3), None, 9, True, False)
+    assert (e.lo, e.hi) == (4, 6)
+    for args, message in (((9, (0, 2), None, 8, False, False), "population 9 and the 8 update chunks must both be divisible by "
+                                                               "the number of ranks 2"),
+                          ((8, (0, 2), None, 7, False, False), "population 8 and the 7 update chunks must both be divisible"),
+                          ((9, (0, 2), None, 8, True, False), "divisible"),   # before the odd population is looked at
+                          ((3, (0, 1), None, 8, True, False), "antithetic pairs need an even population"),
+                          ((4, (0, 1), None, 8, True, False, "host_reference"), "need device_philox offspring"),
+                          ((4, (0, 1), None, 8, False, True, "host_reference"), "need device_philox offspring"),
+                          ((4, (0, 2), None, 8, False, False, "host_reference"), "the extension mode and the sharded run need")):
+        with pytest.raises(ValueError, match=message):
+            bare_update()._shard_range(*args)
+
+
+class Args:
+    def __init__(self, **k):
+        self.__dict__.update(mutation_power_agent_0=0.05, mutation_power_agent_1=0.04, min_mutation_power=0.001,
+                             max_mutation_power=0.2, **k)
+
+
+FLAT, WORSE = [1.0] * 20, [1.0] * 10 + [0.0] * 10
+
+
+@pytest.mark.parametrize("gen,rewards,want", [
+    (5, dict(first_0=WORSE, second_0=WORSE), (0.05 * 0.95, 0.04 * 0.95)),       # generation <= 10: everyone shrinks
+    (12, dict(first_0=FLAT, second_0=FLAT), (0.05 * 0.95, 0.04 * 0.95)),
+    (12, dict(first_0=WORSE, second_0=FLAT), (0.04 * 1.2, 0.04 * 0.95)),        # Q5: first_0 grows from second_0's sigma
+    (12, dict(first_0=FLAT, second_0=WORSE), (0.05 * 0.95, 0.04 * 1.2)),
+    (12, dict(first_0=WORSE, second_0=WORSE), (0.04 * 1.2, 0.04 * 1.2))])
+def test_two_role_sigma_rule_at_both_call_sites_settings(gen, rewards, want):
+    """DQNGATrainer.finish: the rule sees the adversary's sigma as 0.0, the attribute need not exist and is 0.0 afterwards;
+    DQNESTrainer.step: it sees the caller's value, which comes back untouched.  The two sigmas are the same either way"""
+    ga = Args()
+    P.adapt_mutation_power2(ga, gen, rewards, zero_adversary=True)
+    assert (ga.mutation_power_agent_0, ga.mutation_power_agent_1) == want and ga.mutation_power_adversary == 0.0
+    ga = Args(mutation_power_adversary=0.03)
+    P.adapt_mutation_power2(ga, gen, rewards, zero_adversary=True)
+    assert (ga.mutation_power_agent_0, ga.mutation_power_agent_1) == want and ga.mutation_power_adversary == 0.03
+    es = Args(mutation_power_adversary=0.03)
+    P.adapt_mutation_power2(es, gen, rewards, zero_adversary=False)
+    assert (es.mutation_power_agent_0, es.mutation_power_agent_1) == want and es.mutation_power_adversary == 0.03
+    with pytest.raises(AttributeError):   # the ES site reads the caller's value: it has to be there
+        P.adapt_mutation_power2(Args(), gen, rewards, zero_adversary=False)
+
+
+def test_sigma_rule_clamps_and_treats_the_three_roles_in_order():
+    hist = {"agent_0": WORSE, "agent_1": WORSE, "adversary_0": FLAT}
+    a = Args(mutation_power_adversary=0.0005)
+    a.mutation_power_agent_1 = 0.19
+    P.adapt_mutation_power(a, 11, hist)
+    # agent_0 reads agent_1's sigma BEFORE agent_1 grows; both hit the maximum, the adversary the minimum
+    assert (a.mutation_power_agent_0, a.mutation_power_agent_1, a.mutation_power_adversary) == (0.2, 0.2, 0.001)
+    b = Args(mutation_power_adversary=0.03)
+    P.adapt_mutation_power(b, 10, hist)   # gen > 10 only
+    assert (b.mutation_power_agent_0, b.mutation_power_agent_1, b.mutation_power_adversary) == (0.05 * 0.95, 0.04 * 0.95,
+                                                                                               0.03 * 0.95)
+
+
+def sigma_rule_written_out(args, gen, hist):
+    """the rule as it stood, one statement per role, before it became a loop over the roles in population"""
+    def worse(h):
+        return gen > 10 and np.mean(h[-10:]) < np.mean(h[-20:-10])
+    if worse(hist["agent_0"]):
+        args.mutation_power_agent_0 = min(args.mutation_power_agent_1 * 1.2, args.max_mutation_power)
+    else:
+        args.mutation_power_agent_0 = max(args.mutation_power_agent_0 * 0.95, args.min_mutation_power)
+    if worse(hist["agent_1"]):
+        args.mutation_power_agent_1 = min(args.mutation_power_agent_1 * 1.2, args.max_mutation_power)
+    else:
+        args.mutation_power_agent_1 = max(args.mutation_power_agent_1 * 0.95, args.min_mutation_power)
+    if worse(hist["adversary_0"]):
+        args.mutation_power_adversary = min(args.mutation_power_adversary * 1.2, args.max_mutation_power)
+    else:
+        args.mutation_power_adversary = max(args.mutation_power_adversary * 0.95, args.min_mutation_power)
+
+
+def test_sigma_rule_as_a_loop_equals_the_rule_written_out():
+    """4 000 random histories, sigmas (from below the minimum to above the maximum) and generations (0 .. 29, short histories
+    included): the three sigmas are equal bit for bit, and every one of the 8 grow / shrink combinations occurs"""
+    rng = np.random.default_rng(16)
+    roles, seen = ("agent_0", "agent_1", "adversary_0"), set()
+    for _ in range(4000):
+        gen = int(rng.integers(0, 30))
+        hist = {r: rng.integers(-3, 4, size=gen + 1).astype(np.float64).tolist() for r in roles}
+        sig = rng.uniform(0.0005, 0.25, size=3).tolist()
+        a, b = (Args(mutation_power_adversary=sig[2]) for _ in range(2))
+        for x in (a, b):
+            x.mutation_power_agent_0, x.mutation_power_agent_1 = sig[0], sig[1]
+        P.adapt_mutation_power(a, gen, hist)
+        sigma_rule_written_out(b, gen, hist)
+        assert vars(a) == vars(b), (gen, hist, sig)
+        if gen > 10:
+            seen.add(tuple(bool(np.mean(hist[r][-10:]) < np.mean(hist[r][-20:-10])) for r in roles))
+    assert len(seen) == 8
+
+
+def test_shard_and_gather_is_one_rank_without_a_world():
+    class Ctx:
+        rank, world = 1, 2
+
+        def gather_es(self):
+            pass
+    ctx = Ctx()
+    assert P.shard_and_gather(None, "gather_es") == ((0, 1), None)
+    ctx.world = 1
+    assert P.shard_and_gather(ctx, "gather_es") == ((0, 1), None)
+    ctx.world = 2
+    shard, gather = P.shard_and_gather(ctx, "gather_es")
+    assert shard == (1, 2) and gather == ctx.gather_es
+    with pytest.raises(AttributeError):
+        P.shard_and_gather(ctx, "gather_ga")
 
 
 class ResetLog:
