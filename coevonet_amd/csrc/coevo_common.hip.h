@@ -82,16 +82,6 @@ __device__ inline float dpp_move(float v)
 }
 
 // levels 1..16: every lane ends with the tree sum of its 32-lane half
-// the first four levels only: every lane returns the sum over its 16-lane row (DPP row operations, no cross-row step)
-__device__ inline float row16_tree_sum(float v)
-{
-    v = v + dpp_move<0xB1>(v);   // quad_perm [1,0,3,2]
-    v = v + dpp_move<0x4E>(v);   // quad_perm [2,3,0,1]
-    v = v + dpp_move<0x141>(v);  // row_half_mirror
-    v = v + dpp_move<0x140>(v);  // row_mirror
-    return v;
-}
-
 __device__ inline float half_tree_sum(float v)
 {
     v = v + dpp_move<0xB1>(v);   // quad_perm [1,0,3,2]
@@ -135,12 +125,11 @@ __device__ __forceinline__ float add_xor32(float v)
     return __uint_as_float(s[0]) + __uint_as_float(s[1]);
 }
 
-// N independent 64-lane tree sums (lane xor 1, 2, 4, 8, 16, 32 - the canonical in-block tree) in one packed butterfly:
-// after level m the 2m lanes of a group hold the same value, so two values share a register from there on (a lane bit
-// selects which).  Returns a register whose lane j (j < N) holds the total of v[j].  N <= 16.  ~4 instructions per value
-// instead of 11.
+// The first four levels (lane xor 1, 2, 4, 8) of N independent tree sums in one packed butterfly: after level m the 2m
+// lanes of a group hold the same value, so two values share a register from there on (a lane bit selects which).  Returns
+// a register in which lane l of EVERY 16-lane row holds the sum of v[l % 16] over that row (v[j], j >= N: unspecified).
 template <int N>
-__device__ __forceinline__ float packed_totals(const float (&v)[N], int l)
+__device__ __forceinline__ float packed_row16_sums(const float (&v)[N], int l)
 {
     static_assert(N >= 1 && N <= 16, "four packing levels");
     constexpr int N1 = (N + 1) / 2, N2 = (N1 + 1) / 2, N3 = (N2 + 1) / 2;
@@ -182,6 +171,16 @@ __device__ __forceinline__ float packed_totals(const float (&v)[N], int l)
         const float b = s3[1] + dpp_move<0x128>(s3[1]);
         s = (l & 8) ? b : s;
     }
+    return s;
+}
+
+// N independent 64-lane tree sums (lane xor 1, 2, 4, 8, 16, 32 - the canonical in-block tree): the packed butterfly above,
+// then the two levels across the 16-lane rows.  Returns a register whose lane j (j < N) holds the total of v[j].  N <= 16.
+// ~4 instructions per value instead of 11.
+template <int N>
+__device__ __forceinline__ float packed_totals(const float (&v)[N], int l)
+{
+    float s = packed_row16_sums<N>(v, l);
     s = add_xor16(s);
     s = add_xor32(s);
     return s;

@@ -1212,10 +1212,65 @@ struct FcMfma16Smem {
     };
     float xst[12][16];  // observations transposed [k][row], zero padded to 12 inputs: A operands of fc1
     float w3s[NACT][260];
-    float red[16][8];
+    float red[16][8] __attribute__((aligned(16)));   // [row][canonical block]: a row's partials are read as 16-byte pieces
     float logit[16][COEVO_LOGIT_STRIDE];
 };
 static_assert(sizeof(FcMfma16Smem) <= 40960, "four workgroups per CU");
+
+// ---- the LayerNorm passes of the lean shared-opponent body, written like fc_policy_body_c's for FEW ISSUED INSTRUCTIONS.
+// A wave holds NT = 8 (LayerNorm 512) or 4 (LayerNorm 256) 16x16 tiles; accumulator register i of lane (lc, lg) is row
+// 4 lg + i, column lc of a tile, so per register i the wave owes NT sixteen-lane row sums in each of its four rows of lanes.
+// All 4 NT of them go through packed butterflies of 16 values (register i of tile T is value NT * i + T): afterwards lane lc
+// holds the row sum of tile lc % NT, and the canonical tile adds (T0 + T1) + (T2 + T3) are two more butterfly levels (fp32
+// addition commutes: both partners get the same bits).  -> s[j], NT / 4 registers: lane lc of s[j] holds the block sum of row
+// 4 lg + (16 j + lc) / NT, block (lc % NT) / 4 of this wave's canonical blocks.
+template <int NT, bool SQUARE>
+__device__ __forceinline__ void mfma16_block_sums(const f32x4_acc (&c)[NT], int l, float (&s)[NT / 4])
+{
+    static_assert(NT == 4 || NT == 8, "one or two canonical blocks per wave");
+#pragma unroll
+    for (int j = 0; j < NT / 4; ++j) {
+        float v[16];
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            const float x = c[(16 * j + m) % NT][(16 * j + m) / NT];
+            v[m] = SQUARE ? x * x : x;
+        }
+        float r = packed_row16_sums<16>(v, l);
+        r = r + dpp_move<0xB1>(r);   // T0 + T1 | T2 + T3 (| T4 + T5 | T6 + T7)
+        r = r + dpp_move<0x4E>(r);   // (T0 + T1) + (T2 + T3)
+        s[j] = r;
+    }
+}
+
+// the lanes with lc % 4 == 0 post the block sums: red[row][first block of the wave + block in the wave]
+template <int NT>
+__device__ __forceinline__ void mfma16_post_sums(const float (&s)[NT / 4], float (*red)[8], int w, int lc, int lg)
+{
+    if ((lc & 3) == 0) {
+#pragma unroll
+        for (int j = 0; j < NT / 4; ++j) red[4 * lg + (16 * j + lc) / NT][(NT / 4) * w + (lc % NT) / 4] = s[j];
+    }
+}
+
+// Row statistics once per row and wave: lane (lc, lg) combines the NB block partials of row 4 lg + lc % 4 left to right
+// (two or one 16-byte reads); register i of every lane then takes its row's value from lane i of its quad (DPP quad_perm).
+template <int NB>
+__device__ __forceinline__ float mfma16_row_total(const float (*red)[8], int lc, int lg)
+{
+    const float *rr = red[4 * lg + (lc & 3)];
+    const float4 a = *reinterpret_cast<const float4 *>(rr);
+    float tot = ((a.x + a.y) + a.z) + a.w;
+    if constexpr (NB == 8) {
+        const float4 b = *reinterpret_cast<const float4 *>(rr + 4);
+        tot = (((tot + b.x) + b.y) + b.z) + b.w;
+    }
+    return tot;
+}
+__device__ __forceinline__ void quad_spread(float v, float (&out)[4])
+{
+    out[0] = dpp_move<0x00>(v); out[1] = dpp_move<0x55>(v); out[2] = dpp_move<0xAA>(v); out[3] = dpp_move<0xFF>(v);
+}
 
 template <int MODE>
 __device__ __forceinline__ void fc_policy_mfma16_body(const FcArgs &a, FcMfma16Smem &sm, const coevo_fc_task &task)
@@ -1332,44 +1387,25 @@ __device__ __forceinline__ void fc_policy_mfma16_body(const FcArgs &a, FcMfma16S
     }
     // ---- LayerNorm(512): canonical blocks 2w (tiles 0..3) and 2w+1 (tiles 4..7); inside a block feature 16T' + lc:
     //      four tree levels inside the 16-lane row, then (T0 + T1) + (T2 + T3) ---------------------------------
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float s_lo = (row16_tree_sum(c1[0][i]) + row16_tree_sum(c1[1][i])) +
-                           (row16_tree_sum(c1[2][i]) + row16_tree_sum(c1[3][i]));
-        const float s_hi = (row16_tree_sum(c1[4][i]) + row16_tree_sum(c1[5][i])) +
-                           (row16_tree_sum(c1[6][i]) + row16_tree_sum(c1[7][i]));
-        if (lc == 0) { sm.red[4 * lg + i][2 * w] = s_lo; sm.red[4 * lg + i][2 * w + 1] = s_hi; }
-    }
+    float s1[2], stat[4];
+    mfma16_block_sums<8, false>(c1, l, s1);
+    mfma16_post_sums<8>(s1, sm.red, w, lc, lg);
     __syncthreads();
-    float stat[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float *rr = sm.red[4 * lg + i];
-        float tot = rr[0];
-#pragma unroll
-        for (int b = 1; b < 8; ++b) tot = tot + rr[b];
-        stat[i] = tot * (1.0f / H1);
-    }
+    quad_spread(mfma16_row_total<8>(sm.red, lc, lg) * (1.0f / H1), stat);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
         for (int T = 0; T < 8; ++T) c1[T][i] = c1[T][i] - stat[i];
-        const float s_lo = (row16_tree_sum(c1[0][i] * c1[0][i]) + row16_tree_sum(c1[1][i] * c1[1][i])) +
-                           (row16_tree_sum(c1[2][i] * c1[2][i]) + row16_tree_sum(c1[3][i] * c1[3][i]));
-        const float s_hi = (row16_tree_sum(c1[4][i] * c1[4][i]) + row16_tree_sum(c1[5][i] * c1[5][i])) +
-                           (row16_tree_sum(c1[6][i] * c1[6][i]) + row16_tree_sum(c1[7][i] * c1[7][i]));
-        if (lc == 0) { sm.red[4 * lg + i][2 * w] = s_lo; sm.red[4 * lg + i][2 * w + 1] = s_hi; }
     }
+    mfma16_block_sums<8, true>(c1, l, s1);
+    mfma16_post_sums<8>(s1, sm.red, w, lc, lg);
     __syncthreads();
+    quad_spread(1.0f / __builtin_sqrtf(mfma16_row_total<8>(sm.red, lc, lg) * (1.0f / H1) + LN_EPS), stat);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = 4 * lg + i;
-        const float *rr = sm.red[row];
-        float tot = rr[0];
-#pragma unroll
-        for (int b = 1; b < 8; ++b) tot = tot + rr[b];
-        const float rstd = 1.0f / __builtin_sqrtf(tot * (1.0f / H1) + LN_EPS);
+        const float rstd = stat[i];
 #pragma unroll
         for (int T = 0; T < 8; ++T) {
             const float y = __builtin_fmaf(c1[T][i] * rstd, p_g1[T], p_be1[T]);
@@ -1431,34 +1467,25 @@ __device__ __forceinline__ void fc_policy_mfma16_body(const FcArgs &a, FcMfma16S
     }
     COEVO_STAMP(3);
     // ---- LayerNorm(256): canonical block w = this wave's four tiles --------------------------------------------
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float s = (row16_tree_sum(c2[0][i]) + row16_tree_sum(c2[1][i])) +
-                        (row16_tree_sum(c2[2][i]) + row16_tree_sum(c2[3][i]));
-        if (lc == 0) sm.red[4 * lg + i][w] = s;
-    }
+    float s2[1];
+    mfma16_block_sums<4, false>(c2, l, s2);
+    mfma16_post_sums<4>(s2, sm.red, w, lc, lg);
     __syncthreads();  // every wave is done with h1a: h2 may overwrite it below
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float *rr = sm.red[4 * lg + i];
-        stat[i] = (((rr[0] + rr[1]) + rr[2]) + rr[3]) * (1.0f / H2);
-    }
+    quad_spread(mfma16_row_total<4>(sm.red, lc, lg) * (1.0f / H2), stat);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
         for (int T = 0; T < 4; ++T) c2[T][i] = c2[T][i] - stat[i];
-        const float s = (row16_tree_sum(c2[0][i] * c2[0][i]) + row16_tree_sum(c2[1][i] * c2[1][i])) +
-                        (row16_tree_sum(c2[2][i] * c2[2][i]) + row16_tree_sum(c2[3][i] * c2[3][i]));
-        if (lc == 0) sm.red[4 * lg + i][w] = s;
     }
+    mfma16_block_sums<4, true>(c2, l, s2);
+    mfma16_post_sums<4>(s2, sm.red, w, lc, lg);
     __syncthreads();
+    quad_spread(1.0f / __builtin_sqrtf(mfma16_row_total<4>(sm.red, lc, lg) * (1.0f / H2) + LN_EPS), stat);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = 4 * lg + i;
-        const float *rr = sm.red[row];
-        const float tot = ((rr[0] + rr[1]) + rr[2]) + rr[3];
-        const float rstd = 1.0f / __builtin_sqrtf(tot * (1.0f / H2) + LN_EPS);
+        const float rstd = stat[i];
 #pragma unroll
         for (int T = 0; T < 4; ++T) {
             const float y = __builtin_fmaf(c2[T][i] * rstd, p_g2[T], p_be2[T]);
