@@ -25,7 +25,7 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 # So: export it yourself for a process that runs the host-cores mode after a graph-replaying mode and is short-lived, or do
 # what bench.py does - run the host-cores mode in a process of its own.
 
-__all__ = ["HalfGAEngine", "HalfESEngine", "DeepQNHalf", "HalfDQNGAEngine", "HalfSynthRollout"]
+__all__ = ["HalfGAEngine", "HalfESEngine", "DeepQNHalf", "HalfDQNGAEngine", "HalfSynthRollout", "HalfDQNESEngine"]
 
 
 def __getattr__(name):
@@ -42,4 +42,7 @@ def __getattr__(name):
     if name in ("HalfDQNGAEngine", "HalfSynthRollout"):
         from . import dqn_ga_half
         return getattr(dqn_ga_half, name)
+    if name == "HalfDQNESEngine":
+        from .dqn_es_half import HalfDQNESEngine
+        return HalfDQNESEngine
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

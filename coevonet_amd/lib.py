@@ -27,6 +27,7 @@ ST_NAMES = {1: "input contains inf or NaN", 2: "output contains inf or NaN after
 
 DQN_LOGIT_STRIDE = 32
 DQN_FC1_TILED = 0x100   # COEVO_DQN_FC1_TILED: or-ed into the channel argument of the layout-dependent DeepQN entry points
+DQP_SKIP_BN = 1         # COEVO_DQP_SKIP_BN: the BatchNorm affine keeps its words (Co-ES)
 DQN_MAX_ROWS = 16
 DQN_TASK_DTYPE = np.dtype([("net_off", "<i8"), ("row_begin", "<i4"), ("n_rows", "<i4")])
 
@@ -255,6 +256,11 @@ _SIGS = {
                                            C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
     "coevo_dqn16_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "coevo_dqn_es16_partial_floats": (C.c_int64, [C.c_int, C.c_int]),
+    "coevo_dqn_es16_partial": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32,
+                                         C.c_uint32, C.c_void_p, C.c_void_p]),
+    "coevo_dqn_es16_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                       C.c_void_p]),
     "coevo_timing_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "coevo_timing_end": (C.c_int, [C.c_void_p, C.c_void_p]),
     "coevo_dqn_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

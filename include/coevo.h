@@ -801,6 +801,30 @@ int coevo_dqn16_perturb_dist(const void *parent_slab, const int32_t *parent_idx,
                              const void *dist_ref, double *dist_partial, void *stream);
 int coevo_dqn16_distance(const void *ref_net, const void *pop_slab, int n, int C, int n_actions, double *dist_partial,
                          void *stream);
+/* Float16 Co-ES update on the fp16 DeepQN slab (coevo_dqn16_pack's layout; DESIGN.md 6a "Float16 DeepQN Co-ES"): what
+ * compute_weight_update (evolutionary_strategy.py:120-148) and base_weights += update (:259-265) execute on half arrays for the
+ * layers DeepQN.get_perturbable_layers names (Atari/deepqn.py:158-172: every conv and Linear weight and bias move; the three
+ * BatchNorm gamma / beta and the stride's padding keep their words).  As for coevo_es16_partial, the noise is drawn again - the
+ * numbers coevo_dqn16_perturb_dist (flags COEVO_DQP_SKIP_BN) added for the same (seed, stream_lo_first + j, stream_hi) - and
+ * rounded to fp16; no perturbed net is read.  The rounding points are coevo_es16_*'s:
+ *   noise16[j][p] = f16(sigma * eps(seed, stream_lo_first + j, stream_hi, p)), the product rounded to fp32 first, p the canonical
+ *                   parameters() index (coevo_dqn_param_count's order); round to nearest even, fp16 subnormals kept
+ *   fit16[j]      = coevo_es16_fitness as it is (rewards = SynthRollout's [games][3] fp64 table)
+ *   sum           = chunk c = individuals [c*n/C, (c+1)*n/C), j ascending from 0 with acc = fmaf(f32(fit16[j]),
+ *                   f32(noise16[j][p]), acc) in fp32, chunk sums added left to right in fp32; dot16 = f16(sum), past 65504 inf
+ *   apply         scale16 = f16(lr / (n * sigma)) (fp64 quotient of the double lr and the device fp32 sigma, one rounding),
+ *                   upd16 = f16(f32(scale16) * f32(dot16)), theta' = f16(f32(theta) + f32(upd16))
+ * A chunk partial holds coevo_dqn_es16_partial_floats(C, n_actions) floats = coevo_dqn16_slab_stride + 512 * 3136 / 2: the net's
+ * entries in fp16-slab order with every half entry widened to one float - the words in front of fc1 as they are, 8 floats per
+ * 16-byte piece of fc1, then one float per 32-bit word up to the stride; 0 at BatchNorm and padding words.
+ * COEVO_ERR_ARG, with nothing launched and nothing written: a NULL pointer, C outside 1 .. 6 (any bit or-ed into it included)
+ * or n_actions outside 1 .. 32, n_total < 1, chunks_total outside 1 .. 64, a partial or net pointer that is not 16-byte
+ * aligned.  A chunk without an individual (n_total < chunks_total) gives a zero partial.  One launch each on `stream`. */
+int64_t coevo_dqn_es16_partial_floats(int C, int n_actions);
+int coevo_dqn_es16_partial(int C, int n_actions, const float *fitness, int n_total, int chunks_total, const float *sigma_dev,
+                           uint64_t seed, uint32_t stream_lo_first, uint32_t stream_hi, float *partial, void *stream);
+int coevo_dqn_es16_apply(void *theta16_net, const float *partial, int chunks_total, int C, int n_actions, int n_total,
+                         const float *sigma_dev, double lr, void *stream);
 /* K5 for the DeepQN layout (see coevo_es_partial / coevo_es_apply): BatchNorm affine is never updated */
 int coevo_dqn_es_partial(const float *theta_net, const float *pert_slab_local, int ind_first, int C, int n_actions,
                          const float *fitness_all, int n_total, int chunks_total, int chunk_first, int n_chunks,
