@@ -854,7 +854,11 @@ int coevo_synth_step(int32_t *game_state, double *acc, int n_games, const int64_
 /* coevo_synth_step for t >= 1 with the output layer of step t-1 fused in: game g's workgroup turns the hidden row of its
  * actor (row_prev[g] of the workspace coevo_dqn_forward_hidden_timed filled for tasks_prev / n_rows_total) into logits and
  * the first-max action (Atari/deepqn.py:48 + the argmax rule of MPE/fcnetwork.py:78-85), stores it in actions_prev, books
- * it and writes the next frame.  Same results as coevo_dqn_forward_argmax + coevo_synth_step. */
+ * it and writes the next frame.  Same results as coevo_dqn_forward_argmax + coevo_synth_step: booked actions, game state,
+ * returns and next frames of every game.  The status words can differ in ONE case: a game whose limit is already reached
+ * (t - 1 >= limit, or a disabled game) gets no output layer here - its actions_prev row keeps what it held and raises
+ * nothing - while coevo_dqn_forward_argmax computes every row and raises COEVO_ST_NO_ACTION for a finished game's stale row
+ * too.  A net that acts in a live game raises the bit in both (tests/test_dqn_forward_edges_gpu.py pins both cases). */
 int coevo_dqn_out_synth_step(int32_t *game_state, double *acc, int n_games, const int64_t *game_ordinal0,
                              const int32_t *gen_dev, int64_t ordinals_per_gen, int t, const int32_t *limit,
                              const int32_t *row_prev, int32_t *actions_prev, const int32_t *row_cur, uint8_t *frames, int C,
