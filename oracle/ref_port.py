@@ -617,6 +617,11 @@ def dqn_bn_segments(C, n_actions):
     return [(P - 320, 320)]
 
 
+def synth_target(seed, ordinal, t, n_actions):
+    """the action that scores at agent-step t of the game with reset ordinal `ordinal`"""
+    return int(lib().oracle_synth_target(int(seed), int(ordinal), int(t), int(n_actions)))
+
+
 def synth_frame(seed, ordinal, t, last_action, C):
     out = np.zeros((84, 84, C), dtype=np.uint8)
     lib().oracle_synth_frame(int(seed), int(ordinal), int(t), int(last_action), int(C), out.ctypes.data)
