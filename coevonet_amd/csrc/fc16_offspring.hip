@@ -55,18 +55,15 @@ __device__ __forceinline__ double f16_piece_d2(const uint4 &a, const uint4 &b, i
     return d2;
 }
 
-// grid (f16_perturb_blocks(D), n_children): workgroup (bx, c) writes pieces 256 bx .. 256 bx + 255 of child c
-__global__ __launch_bounds__(256) void fc16_perturb_dist_kernel(const uint32_t *parent_slab, const int32_t *parent_idx,
-                                                                 uint32_t *child_slab, int child_first, int D,
-                                                                 const float *sigma_dev, uint64_t seed,
-                                                                 uint32_t stream_lo_first, uint32_t stream_hi, int flags,
-                                                                 const int32_t *gen_dev, const uint32_t *dist_ref,
-                                                                 double *dist_partial)
+// one workgroup's 256 pieces of child c (block bx of nblocks); shared by the single- and the multi-role launch
+__device__ __forceinline__ void fc16_perturb_block(const uint32_t *parent_slab, const int32_t *parent_idx, uint32_t *child_slab,
+                                                   int child_first, int D, const float *sigma_dev, uint64_t seed,
+                                                   uint32_t stream_lo_first, uint32_t stream_hi, int flags,
+                                                   const int32_t *gen_dev, const uint32_t *dist_ref, double *dist_partial,
+                                                   int c, int bx, int nblocks, double *scratch)
 {
-    __shared__ double scratch[4];
     if (gen_dev) stream_hi += 4u * (uint32_t)(*gen_dev);   // generation-indexed noise stream without a host argument
     const bool skip_layernorm = (flags & COEVO_PERTURB_SKIP_LAYERNORM) != 0;
-    const int c = blockIdx.y, bx = blockIdx.x;
     const uint32_t slo = stream_lo_first + (uint32_t)c;
     const int64_t stride = f16_stride(D);
     const int u = bx * 256 + (int)threadIdx.x;
@@ -101,10 +98,39 @@ __global__ __launch_bounds__(256) void fc16_perturb_dist_kernel(const uint32_t *
         reinterpret_cast<uint4 *>(child_slab + (int64_t)(child_first + c) * stride)[u] = ov;
         if (dist_partial) d2 = f16_piece_d2(ov, reinterpret_cast<const uint4 *>(dist_ref)[u], u, D);
     }
-    if (dist_partial) {   // uniform over the launch
+    if (dist_partial) {   // uniform over the workgroup
         const double tot = block_sum_f64(d2, scratch);
-        if (threadIdx.x == 0) dist_partial[(size_t)c * gridDim.x + bx] = tot;
+        if (threadIdx.x == 0) dist_partial[(size_t)c * nblocks + bx] = tot;
     }
+}
+
+// grid (f16_perturb_blocks(D), n_children): workgroup (bx, c) writes pieces 256 bx .. 256 bx + 255 of child c
+__global__ __launch_bounds__(256) void fc16_perturb_dist_kernel(const uint32_t *parent_slab, const int32_t *parent_idx,
+                                                                 uint32_t *child_slab, int child_first, int D,
+                                                                 const float *sigma_dev, uint64_t seed,
+                                                                 uint32_t stream_lo_first, uint32_t stream_hi, int flags,
+                                                                 const int32_t *gen_dev, const uint32_t *dist_ref,
+                                                                 double *dist_partial)
+{
+    __shared__ double scratch[4];
+    fc16_perturb_block(parent_slab, parent_idx, child_slab, child_first, D, sigma_dev, seed, stream_lo_first, stream_hi, flags,
+                       gen_dev, dist_ref, dist_partial, blockIdx.y, blockIdx.x, gridDim.x, scratch);
+}
+
+static_assert(sizeof(coevo_fc16_perturb_job) == 72, "layout mirrored by coevonet_amd/lib.py Perturb16Job");
+struct Perturb16Jobs { coevo_fc16_perturb_job j[COEVO_MAX_JOBS]; };
+// blockIdx.z = job (role); the grid covers the largest job, the surplus workgroups of the others leave at once.  A job's
+// partials keep its OWN block count as their stride (f16_perturb_blocks(D): 70 or 69), not the grid's.
+__global__ __launch_bounds__(256) void fc16_perturb_multi_kernel(Perturb16Jobs jobs, uint64_t seed, int flags,
+                                                                  const int32_t *gen_dev)
+{
+    __shared__ double scratch[4];
+    const coevo_fc16_perturb_job &jb = jobs.j[blockIdx.z];
+    const int nblocks = f16_perturb_blocks(jb.D);
+    if ((int)blockIdx.x >= nblocks || (int)blockIdx.y >= jb.n_children) return;   // workgroup-uniform, before any barrier
+    fc16_perturb_block(static_cast<const uint32_t *>(jb.parent_slab), jb.parent_idx, static_cast<uint32_t *>(jb.child_slab),
+                       jb.child_first, jb.D, jb.sigma_dev, seed, jb.stream_lo_first, jb.stream_hi, flags, gen_dev,
+                       static_cast<const uint32_t *>(jb.dist_ref), jb.dist_partial, blockIdx.y, blockIdx.x, nblocks, scratch);
 }
 
 // the same partials for nets that are already in a slab (generation 0, uploaded populations): grid (blocks, n)
@@ -131,6 +157,20 @@ __global__ __launch_bounds__(64) void fc16_dist_finalize_kernel(const double *pa
     if (threadIdx.x == 0) {
         dist[first + c] = f16_of_f64(sqrt(v));
         if (c == 0 && head) dist[first - 1] = *head;
+    }
+}
+
+// blockIdx.y = job: fc16_dist_finalize_kernel of each job in one launch (dist_finalize_multi_kernel with the fp16 rounding)
+struct Finalize16Jobs { coevo_fc_finalize_job j[COEVO_MAX_JOBS]; };
+__global__ __launch_bounds__(64) void fc16_dist_finalize_multi_kernel(Finalize16Jobs jobs)
+{
+    const coevo_fc_finalize_job &jb = jobs.j[blockIdx.y];
+    const int c = blockIdx.x;
+    if (c >= jb.n) return;
+    const double v = wave_sum_partials(jb.dist_partial + (size_t)c * jb.n_blocks, jb.n_blocks);
+    if (threadIdx.x == 0) {
+        jb.dist[jb.first + c] = f16_of_f64(sqrt(v));
+        if (c == 0 && jb.head) jb.dist[jb.first - 1] = *jb.head;
     }
 }
 
@@ -188,21 +228,51 @@ using namespace coevo;
 
 extern "C" int64_t coevo_fc16_perturb_blocks(int D) { return fc_dim_ok(D) ? f16_perturb_blocks(D) : COEVO_ERR_ARG; }
 
+// what one fp16 breeding job (the arguments of one coevo_fc16_perturb_dist call) must satisfy
+static bool perturb16_job_ok(const coevo_fc16_perturb_job &j)
+{
+    if ((j.dist_ref == nullptr) != (j.dist_partial == nullptr)) return false;
+    if (!j.parent_slab || !j.parent_idx || !j.child_slab || !j.sigma_dev || !fc_dim_ok(j.D)) return false;
+    if (!aligned16(j.parent_slab) || !aligned16(j.child_slab) || !aligned16(j.dist_ref)) return false;
+    return j.n_children >= 0 && j.child_first >= 0 && j.n_children <= 65535;
+}
+
 extern "C" int coevo_fc16_perturb_dist(const void *parent_slab, const int32_t *parent_idx, void *child_slab, int child_first,
                                        int n_children, int D, const float *sigma_dev, uint64_t seed,
                                        uint32_t stream_lo_first, uint32_t stream_hi, int flags, const int32_t *gen_dev,
                                        const void *dist_ref, double *dist_partial, void *stream)
 {
-    if ((dist_ref == nullptr) != (dist_partial == nullptr)) return COEVO_ERR_ARG;
-    if (!parent_slab || !parent_idx || !child_slab || !sigma_dev || !fc_dim_ok(D)) return COEVO_ERR_ARG;
-    if (!aligned16(parent_slab) || !aligned16(child_slab) || !aligned16(dist_ref)) return COEVO_ERR_ARG;
-    if (n_children < 0 || child_first < 0 || n_children > 65535 || (flags & ~COEVO_PERTURB_SKIP_LAYERNORM)) return COEVO_ERR_ARG;
+    const coevo_fc16_perturb_job j{parent_slab, parent_idx, child_slab, sigma_dev, dist_ref, dist_partial,
+                                   child_first, n_children, D, stream_lo_first, stream_hi, 0};
+    if (!perturb16_job_ok(j) || (flags & ~COEVO_PERTURB_SKIP_LAYERNORM)) return COEVO_ERR_ARG;
     if (n_children == 0) return COEVO_OK;
     const dim3 grid((unsigned)f16_perturb_blocks(D), (unsigned)n_children);
     hipLaunchKernelGGL(fc16_perturb_dist_kernel, grid, dim3(256), 0, (hipStream_t)stream,
                        static_cast<const uint32_t *>(parent_slab), parent_idx, static_cast<uint32_t *>(child_slab),
                        child_first, D, sigma_dev, seed, stream_lo_first, stream_hi, flags, gen_dev,
                        static_cast<const uint32_t *>(dist_ref), dist_partial);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_fc16_perturb_dist_multi(const coevo_fc16_perturb_job *jobs, int n_jobs, uint64_t seed, int flags,
+                                             const int32_t *gen_dev, void *stream)
+{
+    if (!jobs || n_jobs < 1 || n_jobs > COEVO_MAX_JOBS || (flags & ~COEVO_PERTURB_SKIP_LAYERNORM)) return COEVO_ERR_ARG;
+    Perturb16Jobs pj{};
+    unsigned gx = 0, gy = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const coevo_fc16_perturb_job &j = jobs[i];
+        if (!perturb16_job_ok(j)) return COEVO_ERR_ARG;
+        pj.j[i] = j;
+        if (j.n_children == 0) continue;   // (an empty job does not widen the grid)
+        const unsigned nb = (unsigned)f16_perturb_blocks(j.D);
+        gx = nb > gx ? nb : gx;
+        gy = (unsigned)j.n_children > gy ? (unsigned)j.n_children : gy;
+    }
+    if (gy == 0) return COEVO_OK;
+    hipLaunchKernelGGL(fc16_perturb_multi_kernel, dim3(gx, gy, (unsigned)n_jobs), dim3(256), 0, (hipStream_t)stream, pj, seed,
+                       flags, gen_dev);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }
@@ -225,6 +295,24 @@ extern "C" int coevo_fc16_distance_finalize(const double *dist_partial, int n_bl
     if (!dist_partial || !dist || n_blocks <= 0 || n <= 0 || first < 0 || (head && first < 1)) return COEVO_ERR_ARG;
     hipLaunchKernelGGL(fc16_dist_finalize_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, dist_partial, n_blocks, dist,
                        first, head);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_fc16_distance_finalize_multi(const coevo_fc_finalize_job *jobs, int n_jobs, void *stream)
+{
+    if (!jobs || n_jobs < 1 || n_jobs > COEVO_MAX_JOBS) return COEVO_ERR_ARG;
+    Finalize16Jobs fj{};
+    int nmax = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const coevo_fc_finalize_job &j = jobs[i];
+        if (!j.dist_partial || !j.dist || j.n_blocks <= 0 || j.n < 0 || j.first < 0 || (j.head && j.first < 1)) return COEVO_ERR_ARG;
+        fj.j[i] = j;
+        nmax = j.n > nmax ? j.n : nmax;
+    }
+    if (nmax == 0) return COEVO_OK;
+    hipLaunchKernelGGL(fc16_dist_finalize_multi_kernel, dim3((unsigned)nmax, (unsigned)n_jobs), dim3(64), 0, (hipStream_t)stream,
+                       fj);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }

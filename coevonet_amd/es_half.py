@@ -10,9 +10,12 @@ and rounds it to fp16, where the float32 engine subtracts the base net from the 
 N_EVAL evaluation games of the updated trio.  The rounding points are the contract of DESIGN.md 6a "Float16 Co-ES".
 
 One rank, device env, ``device_philox`` noise, no antithetic pairs, no centered ranks; the caller passes sigma per generation,
-so the host's adaptive rule can sit on top.  ``ESTrainer`` / ``evolution_strategy_train`` still refuse float16: this object is
-the float16 route until the trainers are switched over."""
+so the host's adaptive rule sits on top.  ``ESTrainer`` / ``evolution_strategy_train`` build this engine under
+``args.precision == "float16"`` with ``multi_breed=True``: the three roles' perturbed nets in one launch
+(coevo_fc16_perturb_dist_multi) and, with fitness sharing, their distances in one (coevo_fc16_distance_finalize_multi)."""
 from __future__ import annotations
+
+import ctypes as ct
 
 import numpy as np
 import torch
@@ -33,7 +36,7 @@ class HalfESEngine(SlabIO, CoESSchedule):
 
     def __init__(self, pop, limit_train=None, limit_eval=None, max_cycles=25, device="cuda", env_seed=ENV_SEED,
                  philox_seed=0, first_ordinal=1, chunks=ES_CHUNKS, *, rng="device_philox", env="device", shard=(0, 1),
-                 antithetic=False, centered_rank=False):
+                 antithetic=False, centered_rank=False, multi_breed=False):
         # what float16 does not cover is refused before the library is loaded
         if rng != "device_philox":
             raise ValueError(f'HalfESEngine: precision float16 perturbs with rng="device_philox" only, not "{rng}"')
@@ -76,6 +79,7 @@ class HalfESEngine(SlabIO, CoESSchedule):
         self.dist_partial = {r: torch.zeros(self.pop * self.pblocks[r], dtype=torch.float64, device=device) for r in ROLES}
         self.partial = {r: torch.zeros(self.chunks * L.es16_partial_floats(ROLE_D[r]), **f32) for r in ROLES}
         self._dist_gen = None   # the generation whose perturb() left the distance partials behind
+        self.multi_breed = bool(multi_breed)   # one launch for the three roles' perturbed nets, one for their distances
         self.steps_per_generation = 3 * self.pop * self.T_train + N_EVAL * self.T_eval
 
     # ------------------------------------------------------------------ loading weights (population.SlabIO)
@@ -87,6 +91,17 @@ class HalfESEngine(SlabIO, CoESSchedule):
         """perturbed net j of role ri = f16(f32(base) + sigma eps) on the Linear entries, noise stream (j, 4 gen + ri):
         ESEngine.perturb_device's numbering.  fitness_sharing: the distances to the base net are accumulated while the nets
         are written (update() computes them itself when they are missing)"""
+        if self.multi_breed:
+            pj = (L.Perturb16Job * 3)()
+            for ri, r in enumerate(ROLES):
+                self.sigma[r].fill_(float(sigmas[r]))
+                pj[ri] = L.Perturb16Job(self._ptr(r, "base"), L._p(self.zero_idx), self._ptr(r, "pert"), L._p(self.sigma[r]),
+                                        self._ptr(r, "base") if fitness_sharing else None,
+                                        L._p(self.dist_partial[r]) if fitness_sharing else None, 0, self.pop, ROLE_D[r], 0,
+                                        gen * 4 + ri, 0)
+            L.call("coevo_fc16_perturb_dist_multi", ct.cast(pj, ct.c_void_p), 3, self.philox_seed, 1, None)
+            self._dist_gen = gen if fitness_sharing else None
+            return
         for ri, r in enumerate(ROLES):
             self.sigma[r].fill_(float(sigmas[r]))
             L.call("coevo_fc16_perturb_dist", self._ptr(r, "base"), L._p(self.zero_idx), self._ptr(r, "pert"), 0, self.pop,
@@ -99,6 +114,12 @@ class HalfESEngine(SlabIO, CoESSchedule):
         """compute_weight_update (evolutionary_strategy.py:120-148) on half arrays + base += update, on the device; sigma is
         the one perturb() stored"""
         self.ro.check_status()
+        finalized = fitness_sharing and self.multi_breed and self._dist_gen == gen
+        if finalized:   # the fused partials are current: the three roles' distances in one launch
+            fj = (L.FinalizeJob * 3)()
+            for ri, r in enumerate(ROLES):
+                fj[ri] = L.FinalizeJob(L._p(self.dist_partial[r]), L._p(self.dist[r]), None, self.pblocks[r], self.pop, 0, 0)
+            L.call("coevo_fc16_distance_finalize_multi", ct.cast(fj, ct.c_void_p), 3)
         for ri, r in enumerate(ROLES):
             D = ROLE_D[r]
             score = None
@@ -106,8 +127,9 @@ class HalfESEngine(SlabIO, CoESSchedule):
                 if self._dist_gen != gen:   # perturb() ran without the fused distances, or the nets were uploaded
                     L.call("coevo_fc16_distance", self._ptr(r, "base"), self._ptr(r, "pert"), self.pop, D,
                            L._p(self.dist_partial[r]))
-                L.call("coevo_fc16_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop,
-                       L._p(self.dist[r]), 0, None)
+                if not finalized:
+                    L.call("coevo_fc16_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop,
+                           L._p(self.dist[r]), 0, None)
                 L.call("coevo_sharing_score", L._p(self.dist[r]), self.pop, L._p(self.div[r]))
                 score = L._p(self.div[r])
             L.call("coevo_es16_fitness", L._p(self.ro.rewards), L._p(self.game_idx[r]), RET_SLOT[r], self.pop, score,

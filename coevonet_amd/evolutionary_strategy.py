@@ -32,10 +32,11 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .es_half import HalfESEngine
 from .game_logic import create_agent
 from .mpe.simple_adversary import ENV_SEED
 from .population import (ES_CHUNKS, N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, CoESSchedule, CoESUpdate, NetTable, SlabIO,
-                         adapt_mutation_power, co_es_games, shard_and_gather, slab_layout)
+                         adapt_mutation_power, co_es_games, half_route, shard_and_gather, slab_layout)
 from .rollout import DeviceRollout, HostEnvRollout, effective_steps
 
 
@@ -147,6 +148,7 @@ class ESResult:
         self.rewards = {r: [] for r in ROLES}
         self.diversity, self.sigma_after, self.game_rewards, self.seconds = [], [], [], []
         self.stopped_at = None
+        self.fitness = []   # float16 route: per generation the fit16 of the three roles (fp16 values)
 
 
 def _linear_mask(D):
@@ -160,24 +162,26 @@ def _linear_mask(D):
 
 class ESTrainer:
     def __init__(self, env, args, rng=None, env_mode=None, collect=True, dist_ctx=None):
-        if getattr(args, "precision", "float32") != "float32":
-            # the reference runs Co-ES in float16 too (evolutionary_strategy.py:11-20); its fp16 ES kernels are not built
-            raise ValueError(f"Co-ES with precision {args.precision} is not supported (float16 covers Co-GA nets and "
-                             "play_game only)")
+        # float16: rng "device_philox" + the device env on one rank, no extension mode, or a ValueError before anything else
+        self.half = half_route(args, "Co-ES with precision", rng, env_mode, dist_ctx, "gather_es",
+                               extensions=("coevo_antithetic", "coevo_centered_rank"))
         self.env, self.args, self.collect = env, args, collect
         self.rng = rng or getattr(args, "coevo_rng", "host_reference")
         env_mode = env_mode or getattr(args, "coevo_env", "device")
         self.first_ordinal = getattr(env, "n_resets", 1)
         agents = {r: create_agent(env, args, role=r) for r in ROLES}  # evolutionary_strategy.py:163-165
         shard, gather = shard_and_gather(dist_ctx, "gather_es")
-        self.eng = ESEngine(args.population, args.max_timesteps_per_episode, args.max_evaluation_steps,
-                            max_cycles=getattr(env, "max_cycles", 25), rng=self.rng,
-                            philox_seed=getattr(args, "coevo_seed", 0), env=env_mode,
-                            first_ordinal=self.first_ordinal,
-                            env_seed=getattr(env, "seed_value", ENV_SEED) or ENV_SEED, shard=shard, gather=gather,
-                            antithetic=getattr(args, "coevo_antithetic", False),
-                            centered_rank=getattr(args, "coevo_centered_rank", False),
-                            chunks=getattr(args, "coevo_es_chunks", ES_CHUNKS))
+        common = dict(max_cycles=getattr(env, "max_cycles", 25), philox_seed=getattr(args, "coevo_seed", 0),
+                      first_ordinal=self.first_ordinal, env_seed=getattr(env, "seed_value", ENV_SEED) or ENV_SEED,
+                      chunks=getattr(args, "coevo_es_chunks", ES_CHUNKS))
+        if self.half:   # (create_agent built FCNetworkHalf nets; flat() carries fp16 values)
+            self.eng = HalfESEngine(args.population, args.max_timesteps_per_episode, args.max_evaluation_steps,
+                                    multi_breed=True, **common)
+        else:
+            self.eng = ESEngine(args.population, args.max_timesteps_per_episode, args.max_evaluation_steps,
+                                rng=self.rng, env=env_mode, shard=shard, gather=gather,
+                                antithetic=getattr(args, "coevo_antithetic", False),
+                                centered_rank=getattr(args, "coevo_centered_rank", False), **common)
         keep = [self.eng.upload(r, "base", 0, agents[r].model.flat()[None]) for r in ROLES]
         torch.cuda.current_stream().synchronize()
         self.base_flat = {r: agents[r].model.flat().copy() for r in ROLES}  # host copy (host_reference mode)
@@ -232,6 +236,8 @@ class ESTrainer:
         sigmas = {r: getattr(args, SIGMA_ATTR[r]) for r in ROLES}
         if self.rng == "host_reference":
             self._perturb_host()
+        elif self.half:
+            eng.perturb(gen, sigmas, args.fitness_sharing)
         else:
             eng.perturb_device(gen, sigmas)
         eng.rollout(gen)
@@ -239,11 +245,16 @@ class ESTrainer:
             eng.ro.check_status()
             divs = self._update_host()
         else:
-            eng.update_device(gen, args.learning_rate, args.fitness_sharing)
+            if self.half:
+                eng.update(gen, args.learning_rate, args.fitness_sharing)
+            else:
+                eng.update_device(gen, args.learning_rate, args.fitness_sharing)
             divs = [float(eng.div[r].item()) if args.fitness_sharing else None for r in ROLES] if self.collect else None
         if self.collect:
             res.game_rewards.append(eng.rewards_host()[:eng.n_main].copy())
             res.diversity.append(divs)
+            if self.half:
+                res.fitness.append([eng.fitness[r].cpu().numpy().copy() for r in ROLES])
         stop = self._finish_generation(gen, eng.evaluate(gen))
         res.seconds.append(time.perf_counter() - t0)
         self.gen += 1
@@ -290,7 +301,9 @@ class ESTrainer:
 def evolution_strategy_train(env, args, output_dir, rng=None, env_mode=None, collect=True, return_result=False,
                              dist_ctx=None):
     """Drop-in for evolutionary_strategy.py:151: returns (agent_0, agent_1, adversary) like the reference; with
-    return_result=True also the ESResult history (what the reference only plots)."""
+    return_result=True also the ESResult history (what the reference only plots).  args.precision "float16" trains half nets
+    through HalfESEngine: rng "device_philox" (the argument or args.coevo_rng), device env, one rank, no extension mode;
+    anything else raises ValueError before the GPU is touched (DESIGN 6a "Float16 trainers")."""
     import os
     if getattr(args, "game", "simple_adversary_v3") != "simple_adversary_v3":   # the two-player Atari games
         from .dqn_population import dqn_evolution_strategy_train

@@ -8,9 +8,13 @@ fp16-valued distances), the promotion (coevo_ga16_promote) and the offspring wit
 (coevo_fc16_perturb_dist, coevo_fc16_distance_finalize) - the order and the noise streams of ``GAEngine.breed_device`` on
 one GPU.  The rounding points are the float16 contract of DESIGN.md "float16 nets".
 
-One cohort, device env, ``device_philox`` offspring, fixed mutation powers.  ``GATrainer`` / ``genetic_algorithm_train``
-still refuse float16: this object is the float16 route until the trainers are switched over."""
+One cohort, device env, ``device_philox`` offspring; the caller passes the mutation powers per generation, so the host's
+adaptive rule sits on top.  ``GATrainer`` / ``genetic_algorithm_train`` build this engine under ``args.precision == "float16"``
+with ``multi_breed=True``: the three roles' children and distances in one launch each (coevo_fc16_perturb_dist_multi,
+coevo_fc16_distance_finalize_multi) in place of six."""
 from __future__ import annotations
+
+import ctypes as ct
 
 import numpy as np
 import torch
@@ -34,7 +38,7 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
 
     def __init__(self, pop, hof, elites, limit_train=None, limit_eval=None, max_cycles=25, device="cuda",
                  env_seed=ENV_SEED, philox_seed=0, first_ordinal=1, *, adaptive=False, shard=(0, 1), env="device",
-                 rng="device_philox"):
+                 rng="device_philox", multi_breed=False):
         # what float16 does not cover is refused before the library is loaded
         if adaptive:
             raise ValueError("HalfGAEngine: adaptive mutation power is not built for precision float16")
@@ -77,6 +81,7 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
         self.dist_partial = {r: torch.zeros(pop * self.pblocks[r], dtype=torch.float64, device=device) for r in ROLES}
         self.parent_idx = torch.tensor([c % elites for c in range(pop - 1)], dtype=torch.int32, device=device)
         self._dist_current = False
+        self.multi_breed = bool(multi_breed)   # breed(): one launch each for the three roles' children and distances
         self.steps_per_generation = 3 * pop * hof * self.T_train + N_EVAL * self.T_eval
 
     # ------------------------------------------------------------------ loading weights (population.SlabIO)
@@ -108,9 +113,24 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
         for r in ROLES:
             self.sigma[r].fill_(float(sigmas[r]))
         self._promote_roles(elites_from_pop=True, best_to_pop0=True)
-        for ri, r in enumerate(ROLES):
-            self._breed_role_children(ri, r, 0, self.pop - 1, gen * 4 + ri, None, L._p(self.sigma[r]))
+        if self.multi_breed:
+            self._breed_children_multi(gen)
+        else:
+            for ri, r in enumerate(ROLES):
+                self._breed_role_children(ri, r, 0, self.pop - 1, gen * 4 + ri, None, L._p(self.sigma[r]))
         self._dist_current = True
+
+    def _breed_children_multi(self, gen):
+        """_breed_role_children of the three roles as one job each of the two multi launches"""
+        n = self.pop - 1
+        pj, fj = (L.Perturb16Job * 3)(), (L.FinalizeJob * 3)()
+        for ri, r in enumerate(ROLES):
+            pj[ri] = L.Perturb16Job(self._ptr(r, "elite"), self.parent_idx.data_ptr(), self._ptr(r, "pop"), L._p(self.sigma[r]),
+                                    self._ptr(r, "stale"), L._p(self.dist_partial[r]), 1, n, ROLE_D[r], 0, gen * 4 + ri, 0)
+            fj[ri] = L.FinalizeJob(L._p(self.dist_partial[r]), L._p(self.dist[r]), L._p(self.best_dist[r]), self.pblocks[r], n,
+                                   1, 0)
+        L.call("coevo_fc16_perturb_dist_multi", ct.cast(pj, ct.c_void_p), 3, self.philox_seed, 0, None)
+        L.call("coevo_fc16_distance_finalize_multi", ct.cast(fj, ct.c_void_p), 3)
 
     def diversity(self):
         """the sharing score of each role in the last select() (float32)"""

@@ -32,11 +32,12 @@ import torch
 
 from . import lib as L
 from .fcnetwork import FCNetwork
+from .ga_half import HalfGAEngine
 from .game_logic import create_agent
 from .mpe.simple_adversary import ENV_SEED
 from .population import (N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, CoGASchedule, CoGATail, NetTable, SlabIO,
-                         adapt_mutation_power, captured, co_ga_games, eval_gate_limits, mean_eval_triple, shard_and_gather,
-                         slab_layout)
+                         adapt_mutation_power, captured, co_ga_games, eval_gate_limits, half_route, mean_eval_triple,
+                         shard_and_gather, slab_layout)
 from .rollout import DeviceRollout, HostEnvRollout, RolloutPlan, effective_steps
 
 ROLE_SLOT = {"agent_0": 1, "agent_1": 2, "adversary_0": 0}   # env slot the role acts in
@@ -719,16 +720,27 @@ class GATrainer:
     exactly these steps)."""
 
     def __init__(self, env, args, rng=None, env_mode=None, collect=True, dist_ctx=None):
-        if getattr(args, "precision", "float32") != "float32":
-            # float16 nets have their forward (coevo_fc16_forward_argmax) and play_game; the population engine's fp16
-            # rollout, breeding and selection kernels are not built, so the trainer refuses before touching the GPU
-            raise ValueError(f"Co-GA training with precision {args.precision} is not supported (float16 covers the nets, "
-                             "create_agent / mutate / clone, checkpoints and play_game)")
+        # float16: rng "device_philox" + the device env on one rank, or a ValueError before anything else happens
+        self.half = half_route(args, "Co-GA training with precision", rng, env_mode, dist_ctx, "gather_ga")
         self.env, self.args, self.collect = env, args, collect
         self.rng = rng or getattr(args, "coevo_rng", "host_reference")
         env_mode = env_mode or getattr(args, "coevo_env", "device")
         self.first_ordinal = getattr(env, "n_resets", 1)
-        pop_flat, hof_flat = initial_population(env, args)
+        pop_flat, hof_flat = initial_population(env, args)   # (create_agent builds FCNetworkHalf under float16)
+        self.res = GAResult()
+        self.gen = 0
+        self.stamp_every = 1
+        if self.half:
+            # the host-driven loop of step() over the float16 engine; the adaptive rule stays on the host (_finish_generation)
+            self.device_loop = self.sharded_loop = False
+            self.eng = HalfGAEngine(args.population, args.hof_size, args.elites_number, args.max_timesteps_per_episode,
+                                    args.max_evaluation_steps, max_cycles=getattr(env, "max_cycles", 25),
+                                    env_seed=getattr(env, "seed_value", ENV_SEED) or ENV_SEED,
+                                    philox_seed=getattr(args, "coevo_seed", 0), first_ordinal=self.first_ordinal,
+                                    multi_breed=True)
+            self.eng.load_initial(pop_flat, hof_flat)
+            self.res.engine = self.eng
+            return
         shard, gather = shard_and_gather(dist_ctx, "gather_ga")
         gather_packed = getattr(dist_ctx, "gather_ga_packed", None) if gather else None
         # the host-free generation loop needs device-built offspring, the device env and a single rank
@@ -756,10 +768,7 @@ class GATrainer:
                             env_seed=getattr(env, "seed_value", ENV_SEED) or ENV_SEED, shard=shard, gather=gather,
                             cohorts=int(cohorts), gather_packed=gather_packed)
         self.eng.load_initial(pop_flat, hof_flat)
-        self.res = GAResult()
         self.res.engine = self.eng
-        self.gen = 0
-        self.stamp_every = 1
         if self.device_loop or self.sharded_loop:
             self.eng.setup_device_loop(args, capacity=max(getattr(args, "generations", 0), 1) + 64)
 
@@ -788,12 +797,17 @@ class GATrainer:
             res.seconds.append(time.perf_counter() - t0)
             self.gen += 1
             return
-        eng.rollout(gen, with_prev_eval=gen > 0)
+        if self.half:
+            eng.rollout(gen)   # (generation gen - 1's evaluation games ride along from generation 1 on)
+        else:
+            eng.rollout(gen, with_prev_eval=gen > 0)
         if gen > 0:
             _finish_generation(args, gen - 1, eng.eval_rewards(), res)
         eng.select()
         sigmas = {r: getattr(args, SIGMA_ATTR[r]) for r in ROLES}
-        if self.rng == "host_reference":
+        if self.half:
+            eng.breed(gen, sigmas)
+        elif self.rng == "host_reference":
             eng.breed_host_reference(self.env, args, sigmas)
         else:
             eng.breed_device(gen, sigmas)
@@ -877,7 +891,9 @@ def genetic_algorithm_train(env, agent, args, output_dir, rng=None, env_mode=Non
     None and plots instead).
 
     rng: "host_reference" (default) reproduces the reference's torch RNG stream bit for bit;
-         "device_philox" builds offspring on the device (args.coevo_rng may select it as well)."""
+         "device_philox" builds offspring on the device (args.coevo_rng may select it as well).
+    args.precision "float16" trains half nets through HalfGAEngine: device_philox, device env and one rank only; anything
+    else raises ValueError before the GPU is touched (DESIGN 6a "Float16 trainers")."""
     if getattr(args, "game", "simple_adversary_v3") != "simple_adversary_v3":   # the two-player Atari games
         from .dqn_population import dqn_genetic_algorithm_train
         return dqn_genetic_algorithm_train(env, agent, args, output_dir, collect=collect, dist_ctx=dist_ctx)

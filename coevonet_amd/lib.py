@@ -54,6 +54,10 @@ class PerturbJob(C.Structure):   # coevo_fc_perturb_job
                 ("stream_lo_first", C.c_uint32), ("stream_hi", C.c_uint32), ("pad", C.c_int32)]
 
 
+class Perturb16Job(C.Structure):   # coevo_fc16_perturb_job: PerturbJob's fields over fp16 slabs
+    _fields_ = list(PerturbJob._fields_)
+
+
 class FinalizeJob(C.Structure):  # coevo_fc_finalize_job
     _fields_ = [("dist_partial", C.c_void_p), ("dist", C.c_void_p), ("head", C.c_void_p), ("n_blocks", C.c_int32),
                 ("n", C.c_int32), ("first", C.c_int32), ("pad", C.c_int32)]
@@ -158,6 +162,8 @@ _SIGS = {
     "coevo_fc16_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "coevo_fc16_distance_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                C.c_void_p]),
+    "coevo_fc16_perturb_dist_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    "coevo_fc16_distance_finalize_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "coevo_fc16_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "coevo_ga16_promote": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "coevo_es16_partial_floats": (C.c_int64, [C.c_int]),

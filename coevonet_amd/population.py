@@ -504,3 +504,30 @@ def shard_and_gather(dist_ctx, name):
     if dist_ctx is not None and dist_ctx.world > 1:
         return (dist_ctx.rank, dist_ctx.world), getattr(dist_ctx, name)
     return (0, 1), None
+
+
+def half_route(args, what, rng, env_mode, dist_ctx, gather_name, extensions=()):
+    """Which engines a trainer of the fully connected nets builds: False = the float32 ones, True = the float16 ones
+    (HalfGAEngine / HalfESEngine).  What float16 does not cover is refused here with "`what` float16 ...", the first thing a
+    trainer does: no other attribute of `args` has been read and the library is not loaded.  A bit-exact host_reference mode
+    cannot exist in float16 (the fp16 forward rounds in the canonical order, not in torch's half BLAS order), so the route
+    is rng "device_philox" + the device env on one rank, without the extension modes named in `extensions`."""
+    precision = getattr(args, "precision", "float32")
+    if precision == "float32":
+        return False
+    if precision != "float16":
+        raise ValueError(f"Unsupported precision: {precision}")
+    rng = rng or getattr(args, "coevo_rng", "host_reference")
+    env_mode = env_mode or getattr(args, "coevo_env", "device")
+    if rng != "device_philox":
+        raise ValueError(f'{what} float16 needs rng="device_philox" (the argument, or args.coevo_rng), not "{rng}": there is '
+                         "no bit-exact reference mode in float16")
+    if env_mode != "device":
+        raise ValueError(f'{what} float16 has the device env only, not env "{env_mode}"')
+    shard, gather = shard_and_gather(dist_ctx, gather_name)
+    if shard != (0, 1) or gather is not None:
+        raise ValueError(f"{what} float16 runs on one rank only, not shard {shard}")
+    for attr in extensions:
+        if getattr(args, attr, False):
+            raise ValueError(f"{what} float16 is not built with args.{attr}")
+    return True

@@ -567,6 +567,21 @@ int coevo_fc16_distance(const void *ref_net, const void *pop_slab, int n, int D,
  * coevo_fc_distance_finalize has it */
 int coevo_fc16_distance_finalize(const double *dist_partial, int n_blocks, int n, float *dist, int first, const float *head,
                                  void *stream);
+/* The fp16 breeding of several roles in ONE launch each (coevo_fc_perturb_dist_multi / coevo_fc_distance_finalize_multi for
+ * fp16 slabs).  Job j = the arguments of one coevo_fc16_perturb_dist / coevo_fc16_distance_finalize call; every word written -
+ * children, dist_partial, dist, the head word - equals the per-job call's, bit for bit.  A job's partials keep its own stride
+ * coevo_fc16_perturb_blocks(D) (70 for D = 10, 69 for D = 8) whatever the other jobs are; jobs with and without a distance
+ * may be mixed; a job with n_children == 0 (n == 0) is skipped.  `jobs` is host memory.  COEVO_ERR_ARG, nothing launched
+ * and nothing written: jobs == NULL, n_jobs outside 1 .. COEVO_MAX_JOBS, flags other than 0 / COEVO_PERTURB_SKIP_LAYERNORM,
+ * any job its per-job call would refuse.  All jobs empty: COEVO_OK, no launch. */
+typedef struct {   /* the field order of coevo_fc_perturb_job, untyped slabs; 72 bytes */
+    const void *parent_slab; const int32_t *parent_idx; void *child_slab; const float *sigma_dev;
+    const void *dist_ref; double *dist_partial;
+    int32_t child_first, n_children, D; uint32_t stream_lo_first, stream_hi; int32_t pad;
+} coevo_fc16_perturb_job;
+int coevo_fc16_perturb_dist_multi(const coevo_fc16_perturb_job *jobs /* host */, int n_jobs, uint64_t seed, int flags,
+                                  const int32_t *gen_dev, void *stream);
+int coevo_fc16_distance_finalize_multi(const coevo_fc_finalize_job *jobs /* host */, int n_jobs, void *stream);
 /* coevo_fc_gather for fp16 slabs: dst[dst_first + i] = src[src_idx[i]], whole 16-byte words of the stride */
 int coevo_fc16_gather(const void *src_slab, const int32_t *src_idx, void *dst_slab, int dst_first, int n, int D, void *stream);
 /* coevo_ga_promote for fp16 slabs (genetic_algorithm.py:262-275): elite[k] = pop[order[k]] (k < E <= 8; skipped when
