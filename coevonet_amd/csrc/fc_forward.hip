@@ -1278,7 +1278,7 @@ __device__ __forceinline__ void fc_policy_mfma16_body(const FcArgs &a, FcMfma16S
     typedef unsigned u32x2_s __attribute__((ext_vector_type(2)));
     COEVO_STAMP(0);
     const int t = threadIdx.x, w = t >> 6, l = t & 63, lc = l & 15, lg = l >> 4;
-    const int D = task.D, nrows = task.n_rows, row0 = task.row_begin;
+    const int D = task.D, nrows = task.n_rows, row0 = task.row_begin, flags = task.reserved;
     const float *net = a.slab + task.net_off;
     int st = 0;
 
@@ -1421,14 +1421,17 @@ __device__ __forceinline__ void fc_policy_mfma16_body(const FcArgs &a, FcMfma16S
     COEVO_STAMP(2);
 
     // ---- fc2: 4 column tiles per wave, 128 k-steps; B operands of the four tiles from the lane's own 16-byte piece by
-    //      a 4x4 (register x 16-lane row) transpose -------------------------------------------------------------
+    //      a 4x4 (register x 16-lane row) transpose - or, TILED (COEVO_TASK_TILED: the net has a tile-major twin of W2,
+    //      transposed once where the net was written), the piece's four registers as they were loaded --------------
     f32x4_acc c2[4];
-    {
 #pragma unroll
-        for (int T = 0; T < 4; ++T)
+    for (int T = 0; T < 4; ++T)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) c2[T][i] = p_b2[T];
-        const float4 *wp = reinterpret_cast<const float4 *>(net + fc_off_w2(D)) + (size_t)w * 128 * 64 + l;
+        for (int i = 0; i < 4; ++i) c2[T][i] = p_b2[T];
+    auto fc2 = [&](auto tiled) {
+        constexpr bool TILED = decltype(tiled)::value;
+        const float *w2 = TILED ? a.slab + (int64_t)(flags >> COEVO_TASK_TWIN_SHIFT) * COEVO_TASK_TWIN_UNIT : net + fc_off_w2(D);
+        const float4 *wp = reinterpret_cast<const float4 *>(w2) + (size_t)w * 128 * 64 + l;
         constexpr int U = COEVO_HEAVY16_U;
         float4 bufA[U], bufB[U];
         auto issue = [&](float4 (&buf)[U], int kq) {
@@ -1440,14 +1443,21 @@ __device__ __forceinline__ void fc_policy_mfma16_body(const FcArgs &a, FcMfma16S
             for (int u = 0; u < U; ++u) {
                 const int q = kq + u;
                 const float av = sm.h1a[4 * q + lg][lc ^ (q & 3)];  // A[row lc][k = 4q + lg]
-                const u32x2_s s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(buf[u].x), __float_as_uint(buf[u].z), false, false);
-                const u32x2_s s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(buf[u].y), __float_as_uint(buf[u].w), false, false);
-                const u32x2_s y01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
-                const u32x2_s y23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
-                c2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(y01[0]), c2[0], 0, 0, 0);
-                c2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(y01[1]), c2[1], 0, 0, 0);
-                c2[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(y23[0]), c2[2], 0, 0, 0);
-                c2[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(y23[1]), c2[3], 0, 0, 0);
+                if constexpr (TILED) {
+                    c2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, buf[u].x, c2[0], 0, 0, 0);
+                    c2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, buf[u].y, c2[1], 0, 0, 0);
+                    c2[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, buf[u].z, c2[2], 0, 0, 0);
+                    c2[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, buf[u].w, c2[3], 0, 0, 0);
+                } else {
+                    const u32x2_s s02 = __builtin_amdgcn_permlane32_swap(__float_as_uint(buf[u].x), __float_as_uint(buf[u].z), false, false);
+                    const u32x2_s s13 = __builtin_amdgcn_permlane32_swap(__float_as_uint(buf[u].y), __float_as_uint(buf[u].w), false, false);
+                    const u32x2_s y01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
+                    const u32x2_s y23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
+                    c2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(y01[0]), c2[0], 0, 0, 0);
+                    c2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(y01[1]), c2[1], 0, 0, 0);
+                    c2[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(y23[0]), c2[2], 0, 0, 0);
+                    c2[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, __uint_as_float(y23[1]), c2[3], 0, 0, 0);
+                }
             }
         };
         issue(bufA, 0);
@@ -1464,7 +1474,11 @@ __device__ __forceinline__ void fc_policy_mfma16_body(const FcArgs &a, FcMfma16S
         __builtin_amdgcn_sched_barrier(0);
         consume(bufA, kq);
         consume(bufB, kq + U);
-    }
+    };
+    if (!(flags & COEVO_TASK_TILED))   // workgroup-uniform
+        fc2(std::false_type{});
+    else
+        fc2(std::true_type{});
     COEVO_STAMP(3);
     // ---- LayerNorm(256): canonical block w = this wave's four tiles --------------------------------------------
     float s2[1];

@@ -282,6 +282,65 @@ __global__ __launch_bounds__(256) void ga_promote_kernel(GaPromoteArgs a)
     if (a.tick && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.tick += 1;
 }
 
+// ---- tile-major twins of W2 (COEVO_TASK_TILED: what the lean shared-opponent body feeds its matrix instructions as loaded).
+// Inside every group of 64 pieces (output block w, k-quad q) twin piece l = 16 lg + lc, element T is the net's piece
+// 16 T + lc, element lg.  t0: the first float of the thread's OWN twin piece inside the W2 block; w2: the net's W2 block.
+constexpr int64_t W2_FLOATS = (int64_t)H1 * H2;
+__device__ __forceinline__ float4 w2_twin_piece(const float *w2, int64_t t0)
+{
+    const int64_t group = t0 & ~(int64_t)255;
+    const int l = (int)(t0 >> 2) & 63, lc = l & 15, lg = l >> 4;
+    const float *p = w2 + group + 4 * lc + lg;
+    return make_float4(p[0], p[64], p[128], p[192]);
+}
+
+__global__ __launch_bounds__(256) void fc_w2_tile_major_kernel(const float *src, float *dst, int64_t stride, int64_t o_w2)
+{
+    const int64_t t0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;   // (the grid covers the W2 block exactly)
+    *reinterpret_cast<float4 *>(dst + (int64_t)blockIdx.y * W2_FLOATS + t0) = w2_twin_piece(src + (int64_t)blockIdx.y * stride + o_w2, t0);
+}
+
+// twin slot I -> I - 1 for I < n, every load before the first store as in promote_hof_shift - but no surplus store: the last
+// slot belongs to the caller alone
+template <int I>
+__device__ __forceinline__ void promote_twin_shift(float *twin, int64_t t0, int n)
+{
+    if constexpr (I < PROMOTE_MAX_HOF) {
+        const float4 v = *reinterpret_cast<const float4 *>(twin + (int64_t)(I < n ? I : n - 1) * W2_FLOATS + t0);
+        promote_twin_shift<I + 1>(twin, t0, n);
+        if (I < n) *reinterpret_cast<float4 *>(twin + (int64_t)(I - 1) * W2_FLOATS + t0) = v;
+    }
+}
+
+// ga_promote_kernel without the rebuild mode + the twins of role y's Hall of Fame, a.twins [role][hof][W2_FLOATS]: a thread whose
+// piece lies in W2 owns the same piece of every twin slot - it shifts them with the FIFO and gathers the new member's from the
+// best's net.  (That net is pop[order[0]] or elite[0]; the only store of this launch that can alias it is pop[0] = itself.)
+__global__ __launch_bounds__(256) void ga_promote_tiled_kernel(GaPromoteArgs a, float *twins)
+{
+    const unsigned y = blockIdx.y;
+    const PromoteRole R = PROMOTE_ROLE(a, y);
+    float *pop = static_cast<float *>(R.pop), *hof = static_cast<float *>(R.hof), *elite = static_cast<float *>(R.elite);
+    const int64_t stride = fc_stride(R.D);
+    const int64_t s0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (s0 >= stride) return;
+    const int64_t t0 = s0 - fc_off_w2(R.D);
+    const bool in_w2 = t0 >= 0 && t0 < W2_FLOATS;
+    float *twin = twins + (int64_t)y * a.hof * W2_FLOATS;
+    float4 tw = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (in_w2) {
+        const float *best = R.from_pop ? pop + (int64_t)R.order[0] * stride : elite;
+        tw = w2_twin_piece(best + fc_off_w2(R.D), t0);
+        promote_twin_shift<1>(twin, t0, a.hof);
+    }
+    const float4 e0 = R.from_pop ? promote_elites<0>(pop, R.order, elite, stride, s0, a.E)
+                                 : *reinterpret_cast<const float4 *>(elite + s0);
+    promote_hof_shift<1>(hof, stride, s0, a.hof);
+    *reinterpret_cast<float4 *>(hof + (int64_t)(a.hof - 1) * stride + s0) = e0;
+    if (R.to_pop0) *reinterpret_cast<float4 *>(pop + s0) = e0;
+    if (in_w2) *reinterpret_cast<float4 *>(twin + (int64_t)(a.hof - 1) * W2_FLOATS + t0) = tw;
+    if (a.tick && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *a.tick += 1;
+}
+
 // sum over the individuals i = lo .. hi - 1, ascending, of fitness[i] * (pert_i - theta) at the thread's four slab positions,
 // one fmaf per term starting from 0; pp = the thread's quad of individual 0, the nets `stride` floats apart.
 // The perturbed nets are read exactly once: non-temporal, and 16 rows in flight per lane (only stride/1024 = 137
@@ -570,6 +629,31 @@ extern "C" int coevo_ga_promote_tick(const coevo_ga_promote_role *roles, int n_r
 {
     if (!counter) return COEVO_ERR_ARG;
     return ga_promote_launch(roles, n_roles, E, hof, nullptr, 0, 0, nullptr, counter, stream);
+}
+
+// ... and the Hall of Fame's tile-major W2 twins kept in the same launch (the pipelined one-GPU loop, COEVO_TASK_TILED)
+extern "C" int coevo_ga_promote_tick_tiled(const coevo_ga_promote_role *roles, int n_roles, int E, int hof, int32_t *counter,
+                                           float *w2_twins, void *stream)
+{
+    if (!counter || !w2_twins || !aligned16(w2_twins)) return COEVO_ERR_ARG;
+    GaPromoteArgs a{};
+    if (!promote_roles(a, roles, n_roles, E, hof, true)) return COEVO_ERR_ARG;
+    a.tick = counter;
+    unsigned max_blocks = 0;
+    for (int r = 0; r < n_roles; ++r) max_blocks = std::max(max_blocks, quad_blocks(fc_stride(roles[r].D)));
+    hipLaunchKernelGGL(ga_promote_tiled_kernel, dim3(max_blocks, (unsigned)n_roles), dim3(256), 0, (hipStream_t)stream, a, w2_twins);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_fc_w2_tile_major(const float *src, float *dst, int n_nets, int D, void *stream)
+{
+    if (!src || !dst || !aligned16(src) || !aligned16(dst) || !fc_dim_ok(D) || n_nets < 0 || n_nets > 65535) return COEVO_ERR_ARG;
+    if (n_nets == 0) return COEVO_OK;
+    hipLaunchKernelGGL(fc_w2_tile_major_kernel, dim3((unsigned)(W2_FLOATS / 1024), (unsigned)n_nets), dim3(256), 0,
+                       (hipStream_t)stream, src, dst, fc_stride(D), fc_off_w2(D));
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
 }
 
 // Promotion with the elites REBUILT in the same launch (a population-sharded run: a rank holds only its own individuals, so

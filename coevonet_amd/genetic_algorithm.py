@@ -99,6 +99,10 @@ def cohort_partition(n_local, K):
 # (profiles/r06_mall_residency.md: the budget sweep).  The Hall of Fame, elite and stale nets count against the budget.
 RESIDENT_MB_DEFAULT = 224
 
+# The pipelined one-GPU loop plays the Hall of Fame from tile-major twins of W2, transposed once per generation in the promotion
+# launch instead of in every 16-row task of every env-cycle (COEVO_HOF_TILED=0: the canonical nets, A/B; same results either way)
+HOF_TILED_DEFAULT = "1"
+
 
 def resident_budget_bytes():
     v = os.environ.get("COEVO_RESIDENT_MB", "").strip().lower()
@@ -163,7 +167,20 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         self.P = {r: L.fc_param_count(ROLE_D[r]) for r in ROLES}
         self.base, total = slab_layout(ROLES, (("pop", pop), ("hof", hof), ("elite", elites), ("stale", 1), ("hof_tmp", hof),
                                                ("elite_prev", elites)), self.stride)
-        self.slab = torch.zeros(total, dtype=torch.float32, device=device)
+        # Tile-major W2 twins of the Hall of Fame [role][slot][W2_FLOATS] (COEVO_TASK_TILED; COEVO_HOF_TILED=0: none) behind the
+        # slab in the same allocation: a shared-opponent task names its twin by its offset into the slab.  Read only once the
+        # pipelined one-GPU loop has turned the mode on (_enable_hof_tiled); from then on every writer of the "hof" region keeps
+        # them: the promotion launch of that loop's tail (coevo_ga_promote_tick_tiled), every other promotion and the
+        # launch-per-step FIFO push (_refresh_hof_twins behind them) and uploads (_uploaded).
+        self._hof_tiled, self.hof_twin = False, None
+        if env == "device" and self.world == 1 and hof <= 16 and os.environ.get("COEVO_HOF_TILED", HOF_TILED_DEFAULT) != "0":
+            twin0 = -(-total // L.TASK_TWIN_UNIT) * L.TASK_TWIN_UNIT
+            store = torch.zeros(twin0 + 3 * hof * L.W2_FLOATS, dtype=torch.float32, device=device)
+            self.slab, self.hof_twin = store[:total], store[twin0:]
+            self._twin_off = {self.base[r]["hof"] + j * self.stride[r]: twin0 + (ri * hof + j) * L.W2_FLOATS
+                              for ri, r in enumerate(ROLES) for j in range(hof)}
+        else:
+            self.slab = torch.zeros(total, dtype=torch.float32, device=device)
         # ---- game table of one generation launch (population.co_ga_games) ----------------------------------
         table = NetTable(self.base, self.stride, ROLE_D)
         games, self.n_main = co_ga_games(table, self.lo, self.hi, hof)
@@ -196,7 +213,12 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
             if not resident:
                 return ()
             ind_bytes = sum(4 * self.stride[r] for r in ROLES)
-            n = resident_prefix(resident_budget_bytes(), (hof + elites + 1) * ind_bytes, ind_bytes, self.cohort_bounds)
+            fixed = (hof + elites + 1) * ind_bytes
+            if self.hof_twin is not None:
+                # the rollout reads the Hall of Fame's twins (+7.9 MB at hof 5) and no longer their canonical W2 (-7.9 MB)
+                twin_bytes = 4 * self.hof_twin.numel()
+                fixed += twin_bytes - 3 * hof * 4 * L.W2_FLOATS
+            n = resident_prefix(resident_budget_bytes(), fixed, ind_bytes, self.cohort_bounds)
             return [table.ids[("pop", r, self.lo + i)] for r in ROLES for k in range(self.K)
                     for i in range(int(self.cohort_bounds[k]), int(self.cohort_bounds[k]) + int(n[k]))]
 
@@ -237,6 +259,30 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
     def _uploaded(self, region):
         if region in ("pop", "stale"):
             self._dist_current = False   # (the stale-agent distances breed_device() left behind no longer describe the slab)
+        if region == "hof" and self._hof_tiled:
+            self._refresh_hof_twins()
+
+    # ------------------------------------------------------------------ tile-major W2 twins of the Hall of Fame
+    def _refresh_hof_twins(self):
+        """every twin from its canonical net (current stream, behind whatever wrote the "hof" region)"""
+        for ri, r in enumerate(ROLES):
+            L.call("coevo_fc_w2_tile_major", self._ptr(r, "hof"),
+                   self.hof_twin.data_ptr() + 4 * ri * self.hof * L.W2_FLOATS, self.hof, ROLE_D[r])
+
+    def _enable_hof_tiled(self):
+        """build the twins and point the Hall of Fame's shared-opponent tasks at them (COEVO_TASK_TILED): from here on the lean
+        cycle launch feeds its fc2 matrix instructions the loaded registers as they are"""
+        plan = self.plan
+        torch.cuda.synchronize()   # (no launch in flight reads the task table while it is rewritten)
+        self._refresh_hof_twins()
+        tasks = plan.heavy_np.copy()
+        for i, off in enumerate(tasks["net_off"].tolist()):
+            if off in self._twin_off:
+                tasks["reserved"][i] |= L.task_tiled_flags(self._twin_off[off])
+        plan.heavy_np = tasks
+        plan.heavy.copy_(L.tasks_to_device(tasks, self.device))
+        torch.cuda.synchronize()
+        self._hof_tiled = True
 
     def download(self, role, region, first, n):
         if region == "pop":
@@ -506,6 +552,8 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         while cohort k's chain already streams weights, and the chains start a breeding time apart, which is the stagger
         they want anyway.  The host knows `gen`; sigma, ranks and distances stay on the device."""
         assert self.world == 1 and self.env_mode == "device" and self.fused_tail and self.K > 1
+        if self.hof_twin is not None and not self._hof_tiled and self.plan.heavy is not None:
+            self._enable_hof_tiled()
         self._enqueue_cohort_chains(gen)
         if self._tail_graph is None:
             self._tail_graph = captured(lambda: self._enqueue_selection_and_breeding(breed=False))

@@ -35,6 +35,15 @@ DQN_TASK_DTYPE = np.dtype([("net_off", "<i8"), ("row_begin", "<i4"), ("n_rows", 
 TASK_DTYPE = np.dtype([("net_off", "<i8"), ("row_begin", "<i4"), ("n_rows", "<i4"), ("D", "<i4"),
                        ("reserved", "<i4")])
 TASK_RESIDENT = 1   # coevo_fc_task.reserved bit COEVO_TASK_RESIDENT (include/coevo.h)
+# COEVO_TASK_TILED: a shared-opponent task reads W2 from the net's tile-major twin, W2_FLOATS floats that start
+# (reserved >> TASK_TWIN_SHIFT) * TASK_TWIN_UNIT floats into the slab
+TASK_TILED, TASK_TWIN_SHIFT, TASK_TWIN_UNIT, W2_FLOATS = 2, 8, 1024, 512 * 256
+
+
+def task_tiled_flags(twin_off):
+    """coevo_fc_task.reserved of a task whose net's W2 twin starts twin_off floats into the slab"""
+    assert twin_off % TASK_TWIN_UNIT == 0 and 0 <= twin_off // TASK_TWIN_UNIT < 1 << (31 - TASK_TWIN_SHIFT)
+    return TASK_TILED | (twin_off // TASK_TWIN_UNIT) << TASK_TWIN_SHIFT
 
 
 class PCG64State(C.Structure):
@@ -182,6 +191,8 @@ _SIGS = {
     "coevo_ga_select_adapt": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                         C.c_void_p]),
     "coevo_ga_promote_tick": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "coevo_ga_promote_tick_tiled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "coevo_fc_w2_tile_major": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "coevo_fc_perturb_dist_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
     "coevo_fc_distance_finalize_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "coevo_mpe_reset_gen": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, PCG64State, C.c_int64, C.c_void_p,

@@ -304,12 +304,18 @@ class CoGATail:
             roles[ri] = L.GaPromoteRole(self._ptr(r, "pop"), self._ptr(r, "hof"), self._ptr(r, "elite"),
                                         L._p(self.order[r]), ROLE_D[r], 1 if elites_from_pop else 0,
                                         1 if best_to_pop0 else 0, 0)
+        tiled = getattr(self, "_hof_tiled", False)   # (GAEngine: the Hall of Fame has tile-major W2 twins that the rollout reads)
+        if tick and rebuild is None and tiled:
+            L.call("coevo_ga_promote_tick_tiled", roles, 3, self.E, self.hof, L._p(self.gen_dev), L._p(self.hof_twin))
+            return
         if rebuild is not None:
             L.call("coevo_ga_promote_rebuild", roles, 3, self.E, self.hof, L._p(self.sigma32_prev), self.philox_seed, *rebuild)
         elif tick:
             L.call("coevo_ga_promote_tick", roles, 3, self.E, self.hof, L._p(self.gen_dev))
         else:
             L.call(self._promote_entry, roles, 3, self.E, self.hof)
+        if tiled:
+            self._refresh_hof_twins()
 
     def _elites_unfused(self, r, rebuild=None):
         """the elites of role r out of the population slab or - rebuild = (sigma pointer, noise stream, device generation or
@@ -332,6 +338,8 @@ class CoGATail:
             L.call("coevo_fc_gather", self._ptr(r, "hof_tmp"), L._p(self.iota), self._ptr(r, "hof"), 0,
                    self.hof - 1, D)
         L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "hof"), self.hof - 1, 1, D)
+        if getattr(self, "_hof_tiled", False):
+            self._refresh_hof_twins()
 
     def _best_to_pop0(self, r):
         L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "pop"), 0, 1, ROLE_D[r])

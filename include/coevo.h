@@ -91,6 +91,21 @@ typedef struct {
  * device-env cycle launch streams it with plain loads instead of non-temporal ones, so that it stays in the Infinity Cache
  * from one env-cycle to the next.  Cache policy only: results do not depend on it.  Every other launch ignores it. */
 #define COEVO_TASK_RESIDENT 1
+/* coevo_fc_task.reserved bit: a shared-opponent task (<= 16 rows) of the lean cycle launch reads the second layer's weights
+ * from the net's TILE-MAJOR TWIN instead of the net: COEVO_FC_W2_FLOATS floats that start
+ * (reserved >> COEVO_TASK_TWIN_SHIFT) * COEVO_TASK_TWIN_UNIT floats into the slab (coevo_fc_w2_tile_major writes them).
+ * The matrix instructions then take the loaded registers as they are.  Results do not depend on it while the twin matches
+ * the net; whoever writes the net keeps the twin (coevo_fc_w2_tile_major, coevo_ga_promote_tick_tiled).  Every other
+ * launch and every per-individual task ignores it. */
+#define COEVO_TASK_TILED 2
+#define COEVO_TASK_TWIN_SHIFT 8
+#define COEVO_TASK_TWIN_UNIT 1024
+#define COEVO_FC_W2_FLOATS (COEVO_FC_H1 * COEVO_FC_H2)
+/* Tile-major twins of the second layer of n_nets nets (`src`: the first net, the others fc_slab_stride(D) floats apart) ->
+ * dst [n_nets][COEVO_FC_W2_FLOATS].  A permutation inside every group of 256 floats (output block w = 0..3, k-quad q = 0..127):
+ * twin piece l = 16 lg + lc, element T = the net's piece 16 T + lc, element lg = fc2.weight[64 w + 16 T + lc][4 q + lg] - the B
+ * operand of column tile T that lane l of wave w feeds v_mfma_f32_16x16x4_f32 at k-step q. */
+int coevo_fc_w2_tile_major(const float *src, float *dst, int n_nets, int D, void *stream);
 
 /* FCNetwork.forward + determine_action (MPE/fcnetwork.py:37-90) for every row of every task, one launch.
  *   obs      [rows][COEVO_OBS_STRIDE] fp32          actions [rows] int32 (first index of the maximum logit)
@@ -532,6 +547,10 @@ typedef struct coevo_ga_promote_role {
 int coevo_ga_promote(const coevo_ga_promote_role *roles, int n_roles, int E, int hof, void *stream);
 /* ... with coevo_counter_add(counter, 1) in the same launch: the last launch of a device-resident generation's tail */
 int coevo_ga_promote_tick(const coevo_ga_promote_role *roles, int n_roles, int E, int hof, int32_t *counter, void *stream);
+/* ... and with the tile-major twins of the Hall of Fame (COEVO_TASK_TILED) kept in the same launch: w2_twins
+ * [n_roles][hof][COEVO_FC_W2_FLOATS]; role r's slots shift with its FIFO and the last one is written from the best's net */
+int coevo_ga_promote_tick_tiled(const coevo_ga_promote_role *roles, int n_roles, int E, int hof, int32_t *counter,
+                                float *w2_twins, void *stream);
 /* ... with the elites REBUILT in the same launch (roles with elites_from_pop == 0; `order` required): elite[k] = individual
  * order[k] of the generation just evaluated = the unchanged best (id 0: old elite 0) or child c = id - 1 = old elite[c % E] +
  * sigma[role] * noise(stream (c, stream_hi_prev + role [+ 4 (g - 1) with gen_dev])), regenerated in place from the OLD elites
