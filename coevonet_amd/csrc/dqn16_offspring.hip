@@ -14,59 +14,21 @@
 //   distance   per entry d = f16(f32(a) - f32(b)); d * d accumulated in fp64: the eight (or four) entries of a thread's 16-byte
 //              piece in slab order, then block_sum_f64; one partial per block of 256 pieces; the stride's padding is not
 //              counted.  dist = f16(sqrt(sum of the partials)) in one rounding (coevo_fc16_distance_finalize).
-// A thread owns ONE 16-byte piece of the net.  In the fc1 block ([8][392][64][8] halves, 91 % of the words) that is eight
-// consecutive canonical indices from a multiple of eight = two aligned Philox quads; everywhere else it is four fp32 words that
-// hold fp16 values and map through dqn16_word_to_flat - the conv weights sit in conv16_mfma's lane order, so such a piece can
-// need four Philox blocks (the last one is kept, as in the generic branch of dqn_perturb_kernel).
+// A thread owns ONE 16-byte piece of the net (dqn16_pieces.hip.h, which also holds the noise of a piece: the float16 DeepQN
+// Co-ES update of dqn16_es.hip regenerates it from there).  The roundings are f16_child / f16_diff of fc16_layout.hip.h, the
+// distance loops those of f16_steps.hip.h.
 #include <hip/hip_runtime.h>
 
-#include "dqn16_layout.hip.h"
-#include "fc16_layout.hip.h"
-#include "philox.hip.h"
+#include "dqn16_pieces.hip.h"
+#include "f16_steps.hip.h"
 
 namespace coevo {
-
-// Left alone, hipcc folds f16(a + sigma * z) and f16(sigma * z) into v_fma_mix* forms, which round the exact sum once to fp16
-// and skip the fp32 rounding of the contract.  The empty statement makes the fp32 value a value of its own (f16r_after_fma of
-// dqn_conv.hip.h, es16_noise16 of fc16_es.hip).
-__device__ __forceinline__ float dq16_pin(float v)
-{
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-// child entry = f16(f32(parent) + noise): the sum in fp32, rounded once to half
-__device__ __forceinline__ float dq16_child(float parent, float noise) { return f16r(dq16_pin(parent + dq16_pin(noise))); }
-
-__device__ __forceinline__ int dq16_pieces(const DqnLayout &L) { return (int)(L.stride >> 2); }
-__device__ __forceinline__ bool dq16_fc1_piece(int u, const DqnLayout &L) { return 4 * (int64_t)u >= L.wf && 4 * (int64_t)u < L.bf; }
 
 // squared distance of piece u of net a to the same piece of net b: the piece's entries in slab order, padding left out
 __device__ __forceinline__ double dq16_piece_d2(const uint4 &a, const uint4 &b, int u, const DqnLayout &L)
 {
-    double d2 = 0.0;
-    if (dq16_fc1_piece(u, L)) {
-        _Float16 ha[8], hb[8];
-        __builtin_memcpy(ha, &a, sizeof(ha));
-        __builtin_memcpy(hb, &b, sizeof(hb));
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float d = f16r(dq16_pin(dq16_pin((float)ha[i]) - dq16_pin((float)hb[i])));
-            d2 += (double)d * (double)d;
-        }
-    } else {
-        float fa[4], fb[4];
-        __builtin_memcpy(fa, &a, sizeof(fa));
-        __builtin_memcpy(fb, &b, sizeof(fb));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (4 * (int64_t)u + i < L.total) {   // dqn16_word_to_flat >= 0
-                const float d = f16r(dq16_pin(fa[i] - fb[i]));
-                d2 += (double)d * (double)d;
-            }
-        }
-    }
-    return d2;
+    if (dq16_fc1_piece(u, L)) return f16_d2_halves(a, b);
+    return f16_d2_words(a, b, [&](int i) { return 4 * (int64_t)u + i < L.total; });   // dqn16_word_to_flat >= 0
 }
 
 // grid (coevo_dqn16_perturb_blocks, n_children): workgroup (bx, c) writes pieces 256 bx .. 256 bx + 255 of child c
@@ -90,34 +52,24 @@ __global__ __launch_bounds__(256) void dqn16_perturb_dist_kernel(const uint32_t 
         if (!(flags & COEVO_DQP_COPY)) {
             const float sigma = *sigma_dev;
             if (dq16_fc1_piece(u, L)) {
-                // piece (ob, o, l) = fc1.w[64 ob + l][8 o .. 8 o + 7]: never BatchNorm, never padding
-                const int t = u - (int)(L.wf >> 2), l = t & 63, o = (t >> 6) % DQ16_OCTETS, ob = (t >> 6) / DQ16_OCTETS;
-                const int F_wf = 2048 * C + 69792;   // conv1.w conv1.b conv2.w conv2.b conv3.w conv3.b come first
-                const uint32_t q0 = (uint32_t)((F_wf + (ob * 64 + l) * DQ_FC1_IN + 8 * o) >> 2);
-                float z[8];
-                philox_normal4(seed, slo, stream_hi, q0, z);
-                philox_normal4(seed, slo, stream_hi, q0 + 1u, z + 4);
+                float noise[8];
+                dq16_fc1_piece_noise(u, L, C, sigma, seed, slo, stream_hi, noise);
                 _Float16 hin[8], hout[8];
                 __builtin_memcpy(hin, &pv, sizeof(hin));
 #pragma unroll
-                for (int i = 0; i < 8; ++i) hout[i] = (_Float16)dq16_child(dq16_pin((float)hin[i]), sigma * z[i]);
+                for (int i = 0; i < 8; ++i) hout[i] = (_Float16)f16_child((float)hin[i], noise[i]);
                 __builtin_memcpy(&ov, hout, sizeof(hout));
             } else {
-                float in[4], out[4], zz[4];
-                __builtin_memcpy(in, &pv, sizeof(in));
-                int64_t have = -1;
+                int64_t p[4];
+                bool want[4];
+                dq16_word_piece_flat(u, C, n_actions, p);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int64_t s = 4 * (int64_t)u + i;
-                    const int64_t p = dqn16_word_to_flat(s, C, n_actions);
-                    out[i] = in[i];
-                    if (p < 0 || ((flags & COEVO_DQP_SKIP_BN) && dqn_slab_is_batchnorm(s, L))) continue;
-                    const int64_t q = p >> 2;
-                    if (q != have) { philox_normal4(seed, slo, stream_hi, (uint32_t)q, zz); have = q; }
-                    const int e = (int)(p & 3);
-                    const float zi = e == 0 ? zz[0] : (e == 1 ? zz[1] : (e == 2 ? zz[2] : zz[3]));   // (no runtime-indexed array)
-                    out[i] = dq16_child(in[i], sigma * zi);
-                }
+                for (int i = 0; i < 4; ++i) want[i] = dq16_word_moves(4 * (int64_t)u + i, L, (flags & COEVO_DQP_SKIP_BN) != 0);
+                float in[4], out[4], noise[4];
+                dq16_word_piece_noise(p, want, sigma, seed, slo, stream_hi, noise);
+                __builtin_memcpy(in, &pv, sizeof(in));
+#pragma unroll
+                for (int i = 0; i < 4; ++i) out[i] = want[i] ? f16_child(in[i], noise[i]) : in[i];
                 __builtin_memcpy(&ov, out, sizeof(out));
             }
         }
@@ -150,8 +102,6 @@ __global__ __launch_bounds__(256) void dqn16_distance_kernel(const uint32_t *ref
 }  // namespace coevo
 
 using namespace coevo;
-
-static unsigned dqn16_blocks(int C, int n) { return quad_blocks(dqn16_layout(C, n).stride); }
 
 extern "C" int64_t coevo_dqn16_perturb_blocks(int C, int n_actions)
 {

@@ -41,6 +41,9 @@ __host__ __device__ inline int64_t dqn_param_count(int C, int n)
     return 32LL * C * 64 + 32 + 64LL * 512 + 64 + 64LL * 576 + 64 + 512LL * DQ_FC1_IN + 512 + 512LL * n + n + 320;
 }
 
+// canonical flat index of fc1.w[0][0]: conv1.w conv1.b conv2.w conv2.b conv3.w conv3.b come first
+__host__ __device__ constexpr int64_t dqn_flat_wf(int C) { return 2048LL * C + 69792; }
+
 // Conv weights are stored in the order the implicit-GEMM kernel's lanes consume them (deepqn.hip conv16_mfma): position
 // i = ((qp * NP + np) * 64 + lane) * 4 + e holds W[co = 32 np + 16 (e & 1) + lane % 16][tap = 4 (2 qp + e / 2) + lane / 16]
 // (NP = COUT / 32, taps in the canonical (ci, ky, kx) order), so one 16-byte load per lane brings the B operands of two

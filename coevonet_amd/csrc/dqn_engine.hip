@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void dqn_perturb_kernel(const float *parent_sl
             const int64_t i = s0 - L.wf;
             const int lane = (int)((i >> 2) & 63), cc = lane & 15, kk = lane >> 4;
             const int64_t T = (i >> 8) & 3, Q = (i >> 10) % 196, ob = (i >> 10) / 196;
-            const int64_t F_wf = 2048LL * C + 69792;
+            const int64_t F_wf = dqn_flat_wf(C);
             const int64_t p0 = F_wf + (ob * 64 + 16 * T + cc) * DQ_FC1_IN + 16 * Q + 4 * kk;
             float zl[4], z[4];
             philox_normal4(seed, slo, stream_hi, (uint32_t)(p0 >> 2), zl);
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void dqn_perturb_kernel(const float *parent_sl
             // canonical indices = one Philox block; never BatchNorm, never padding
             const int64_t i = s0 - L.wf;
             const int64_t l = (i >> 2) & 63, kk = i >> 8, kq = kk % 784, ob = kk / 784;
-            const int64_t F_wf = 2048LL * C + 69792;  // conv1.w conv1.b conv2.w conv2.b conv3.w conv3.b come first
+            const int64_t F_wf = dqn_flat_wf(C);
             const int64_t p0 = F_wf + (ob * 64 + l) * DQ_FC1_IN + kq * 4;
             float z[4];
             philox_normal4(seed, slo, stream_hi, (uint32_t)(p0 >> 2), z);

@@ -16,43 +16,23 @@
 //                          of a thread's 16-byte piece in slab order, then block_sum_f64; one partial per 256-piece block.
 //                          dist = f16(sqrt(sum of the partials)), stored as an fp32 word.
 // A thread owns ONE 16-byte piece of the net (fc16_pieces.hip.h, which also holds the noise of a piece: the float16 Co-ES
-// update of fc16_es.hip regenerates it from there).
+// update of fc16_es.hip regenerates it from there).  The distance loops are those of f16_steps.hip.h (f16_diff of
+// fc16_layout.hip.h).  The child sum of fc16_perturb_block is written out, not f16_child: its pin costs this kernel 2 - 3 % (it
+// keeps the sums out of v_pk_add_f32; profiles/r21_fp16_steps_once.md), and the compiler does not fold this sum - the unit's
+// disassembly holds no v_fma_mix* -, which tests/test_fp16_breeding_gpu.py decides word for word.
 #include <hip/hip_runtime.h>
 
-#include "coevo_common.hip.h"
-#include "fc16_layout.hip.h"
+#include "f16_steps.hip.h"
 #include "fc16_pieces.hip.h"
 #include "promote_roles.hip.h"
-#include "philox.hip.h"
 
 namespace coevo {
 
 // squared distance of piece u of net a to the same piece of net b: the piece's Linear entries in slab order
 __device__ __forceinline__ double f16_piece_d2(const uint4 &a, const uint4 &b, int u, int D)
 {
-    double d2 = 0.0;
-    if (u < f16_half_pieces(D)) {
-        _Float16 ha[8], hb[8];
-        __builtin_memcpy(ha, &a, sizeof(ha));
-        __builtin_memcpy(hb, &b, sizeof(hb));
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float d = f16r((float)ha[i] - (float)hb[i]);
-            d2 += (double)d * (double)d;
-        }
-    } else {
-        float fa[4], fb[4];
-        __builtin_memcpy(fa, &a, sizeof(fa));
-        __builtin_memcpy(fb, &b, sizeof(fb));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (f16_tail_kind(4 * u + i, D) == 0) {
-                const float d = f16r(fa[i] - fb[i]);
-                d2 += (double)d * (double)d;
-            }
-        }
-    }
-    return d2;
+    if (u < f16_half_pieces(D)) return f16_d2_halves(a, b);
+    return f16_d2_words(a, b, [=](int i) { return f16_tail_kind(4 * u + i, D) == 0; });
 }
 
 // one workgroup's 256 pieces of child c (block bx of nblocks); shared by the single- and the multi-role launch

@@ -83,17 +83,4 @@ __device__ __forceinline__ void f16_tail_piece_noise(int u, int D, float sigma, 
     for (int i = 0; i < 4; ++i) noise[i] = sigma * z[i];
 }
 
-// fp64 -> fp16 in ONE rounding (to nearest even): to fp32 with round-to-odd first, which the fp32 -> fp16 conversion then
-// rounds as if it saw the fp64 value (fp32 carries more than two bits beyond fp16's eleven)
-__device__ inline float f16_of_f64(double s)
-{
-    float f = (float)s;
-    if ((double)f != s && !__builtin_isinf(f) && !__builtin_isnan(f)) {
-        uint32_t b = __float_as_uint(f);
-        if (__builtin_fabs((double)f) > __builtin_fabs(s)) b -= 1u;   // back to the truncated value
-        f = __uint_as_float(b | 1u);                                    // sticky bit
-    }
-    return f16r(f);
-}
-
 }  // namespace coevo
