@@ -12,7 +12,9 @@
 //   dqn16_conv_kernel  one workgroup per frame: conv16_mfma / bn_relu_rows of dqn_conv.hip.h with H16 = true (LDS keeps fp32
 //                      words that hold fp16 values: the fp32 kernel's footprint, three workgroups per CU)
 //   dqn16_fc1_kernel   one wave per (task, 64-output block) streams the block's 2-byte weights once per task
-//   dqn16_out_kernel   512 -> n logits, rounded to fp16, first-max action
+//   dqn16_out_kernel   512 -> n logits, rounded to fp16, first-max action (dqn_out_row<true>, dqn_common.hip.h)
+// coevo_dqn16_forward_hidden stops after the second: a rollout runs the output row inside its env-step launch
+// (coevo_dqn16_out_synth_step, dqn_engine.hip), as the float32 rollout does.
 // Weights are converted with the exact v_cvt_f32_f16 and feed fp32 chains (v_mfma_f32_4x4x1 / 16x16x4 with fp32 operands are
 // bit-identical to the sequential fmaf chain: tools/mfma4_chain_probe.hip, tools/mfma16_chain_probe.hip); no f16 MFMA, no
 // v_dot2, no mixed-precision FMA - their internal sums are not the sequential order.
@@ -219,8 +221,8 @@ __global__ __launch_bounds__(64, 1) void dqn16_fc1_kernel(const uint32_t *slab, 
     else dqn16_fc1_body<4, DQ16_FC1_NB>(net, L, task, act, hid, xs, ob, l);
 }
 
-// output layer + first-max action: one 64-thread workgroup per row, the structure of dqn_out_row (dqn_common.hip.h) with the
-// logit rounded to fp16 before it is stored and scanned
+// output layer + first-max action: one 64-thread workgroup per row runs dqn_out_row<true> (dqn_common.hip.h), the one body of
+// the float16 output row - the fused env step of dqn_engine.hip (coevo_dqn16_out_synth_step) runs the same
 __global__ __launch_bounds__(64) void dqn16_out_kernel(const uint32_t *slab, const coevo_dqn_task *tasks, int n_tasks, int C,
                                                         int n_actions, const float *hid, int32_t *actions, float *logits,
                                                         int32_t *status)
@@ -231,41 +233,9 @@ __global__ __launch_bounds__(64) void dqn16_out_kernel(const uint32_t *slab, con
     const coevo_dqn_task task = tasks[task_of_row(tasks, n_tasks, row)];
     if (dqn16_bad_task(task)) return;   // workgroup-uniform, before every barrier: the row is left untouched
     const float *net = reinterpret_cast<const float *>(slab + task.net_off);
-    const DqnLayout L = dqn16_layout(C, n_actions);
-    const float4 *x4 = reinterpret_cast<const float4 *>(hid + (size_t)row * DQ_FC1_OUT);
-    reinterpret_cast<float4 *>(xs)[tid] = x4[tid];
-    reinterpret_cast<float4 *>(xs)[tid + 64] = x4[tid + 64];
-    __syncthreads();
-    if (tid < n_actions) {
-        float y = net[L.bo + tid];
-        const float4 *w4 = reinterpret_cast<const float4 *>(net + L.wo + (size_t)tid * DQ_FC1_OUT);
-        constexpr int B = 16;
-        for (int k0 = 0; k0 < DQ_FC1_OUT / 4; k0 += B) {
-            float4 wv[B];
-#pragma unroll
-            for (int i = 0; i < B; ++i) wv[i] = w4[k0 + i];
-#pragma unroll
-            for (int i = 0; i < B; ++i) {
-                const float4 xv = reinterpret_cast<const float4 *>(xs)[k0 + i];
-                y = __builtin_fmaf(wv[i].x, xv.x, y);
-                y = __builtin_fmaf(wv[i].y, xv.y, y);
-                y = __builtin_fmaf(wv[i].z, xv.z, y);
-                y = __builtin_fmaf(wv[i].w, xv.w, y);
-            }
-        }
-        y = f16r_after_fma(y);   // (not v_fma_mixlo_f16: dqn_conv.hip.h)
-        lg[tid] = y;
-        if (logits) logits[(size_t)row * COEVO_DQN_LOGIT_STRIDE + tid] = y;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int best = -1;
-        float cur = -__builtin_inff();
-        for (int i = 0; i < n_actions; ++i)
-            if (lg[i] > cur) { cur = lg[i]; best = i; }
-        if (best < 0) { atomicOr(status, COEVO_ST_NO_ACTION); best = 0; }
-        actions[row] = best;
-    }
+    const int a = dqn_out_row<true>(net, dqn16_layout(C, n_actions), n_actions, hid + (size_t)row * DQ_FC1_OUT,
+                                    logits ? logits + (size_t)row * COEVO_DQN_LOGIT_STRIDE : nullptr, status, xs, lg, tid);
+    if (tid == 0) actions[row] = a;
 }
 
 }  // namespace coevo
@@ -302,18 +272,18 @@ extern "C" int coevo_dqn16_unpack(const void *slab, float *flat, int n, int C, i
     return dqn16_pack_launch(flat, const_cast<uint32_t *>(static_cast<const uint32_t *>(slab)), n, C, n_actions, false, stream);
 }
 
-extern "C" int coevo_dqn16_forward_argmax(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
-                                          int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *actions,
-                                          float *logits, int32_t *status, void *workspace, void *stream)
+// conv stack + fc1 of every row (hid: post-ReLU fc1 outputs, fp16 values, behind the conv3 activations in the workspace), after
+// the argument checks the two float16 forward entry points share
+static int dqn16_hidden_launch(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task, int n_rows_total,
+                               int C, int n_actions, const uint8_t *frames, int32_t *status, void *workspace, hipStream_t s)
 {
-    if (!slab || !tasks || !frames || !actions || !status || !workspace) return COEVO_ERR_ARG;
+    if (!slab || !tasks || !frames || !status || !workspace) return COEVO_ERR_ARG;
     if (n_tasks <= 0 || n_rows_total <= 0 || !dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;   // (any bit or-ed into C fails here)
     if (max_rows_per_task < 1 || max_rows_per_task > DQ16_RMAX) return COEVO_ERR_ARG;
     if (reinterpret_cast<uintptr_t>(slab) & 15) return COEVO_ERR_ARG;
     const uint32_t *sl = static_cast<const uint32_t *>(slab);
     float *act = static_cast<float *>(workspace);
     float *hid = act + (size_t)n_rows_total * DQ_FC1_IN;
-    hipStream_t s = (hipStream_t)stream;
     const dim3 cg(8 * ((n_rows_total + 7) / 8)), cb(512);   // a multiple of 8: the kernel's XCD-aware row mapping
     if (C == 4) hipLaunchKernelGGL((dqn16_conv_kernel<4, 4>), cg, cb, 0, s, sl, tasks, n_tasks, n_rows_total, C, n_actions, frames, act);
     else if (C < 4) hipLaunchKernelGGL((dqn16_conv_kernel<4, 0>), cg, cb, 0, s, sl, tasks, n_tasks, n_rows_total, C, n_actions, frames, act);
@@ -321,8 +291,32 @@ extern "C" int coevo_dqn16_forward_argmax(const void *slab, const coevo_dqn_task
     else hipLaunchKernelGGL((dqn16_conv_kernel<6, 0>), cg, cb, 0, s, sl, tasks, n_tasks, n_rows_total, C, n_actions, frames, act);
     const dim3 fg(8 * ((n_tasks + 7) / 8), 8);
     hipLaunchKernelGGL(dqn16_fc1_kernel, fg, dim3(64), 0, s, sl, tasks, n_tasks, C, n_actions, act, hid, status);
-    hipLaunchKernelGGL(dqn16_out_kernel, dim3(n_rows_total), dim3(64), 0, s, sl, tasks, n_tasks, C, n_actions, hid, actions,
-                       logits, status);
+    return COEVO_OK;
+}
+
+extern "C" int coevo_dqn16_forward_argmax(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
+                                          int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *actions,
+                                          float *logits, int32_t *status, void *workspace, void *stream)
+{
+    if (!actions) return COEVO_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = dqn16_hidden_launch(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, status,
+                                       workspace, s);
+    if (rc != COEVO_OK) return rc;
+    const float *hid = static_cast<const float *>(workspace) + (size_t)n_rows_total * DQ_FC1_IN;
+    hipLaunchKernelGGL(dqn16_out_kernel, dim3(n_rows_total), dim3(64), 0, s, static_cast<const uint32_t *>(slab), tasks, n_tasks, C,
+                       n_actions, hid, actions, logits, status);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_dqn16_forward_hidden(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
+                                          int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *status,
+                                          void *workspace, void *stream)
+{
+    const int rc = dqn16_hidden_launch(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, status,
+                                       workspace, (hipStream_t)stream);
+    if (rc != COEVO_OK) return rc;
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }

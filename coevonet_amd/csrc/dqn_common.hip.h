@@ -1,6 +1,7 @@
 // DeepQN slab layout shared by the forward kernels (deepqn.hip) and the population engine (dqn_engine.hip).
 #pragma once
 #include "coevo_common.hip.h"
+#include "fc16_layout.hip.h"
 
 namespace coevo {
 
@@ -130,6 +131,10 @@ __device__ __forceinline__ int task_of_row(const coevo_dqn_task *tasks, int n_ta
 // chain of its logit; the hidden row is staged in LDS once (every lane reads the same element: a broadcast) and the
 // lane's weight row comes in 16-byte pieces, 16 of them in flight (as a dword-at-a-time loop this took as long as a
 // tenth of the conv stack).  Returns the action to every thread.  xs: 512 floats, 16-byte aligned; lg: 64 floats.
+// H16: the row of the float16 forward (DESIGN.md 6a "Float16 DeepQN") - `net` is a net of the fp16 slab, whose bo / wo sections
+// are fp32 words that hold fp16 values (L = dqn16_layout), and the chain's fp32 result is rounded once to fp16 before it is
+// stored and scanned.  dqn16_out_kernel (dqn16.hip) and the fused env step (dqn_engine.hip) both call this.
+template <bool H16 = false>
 __device__ __forceinline__ int dqn_out_row(const float *net, const DqnLayout L, int n_actions, const float *hid_row,
                                            float *logits_row, int32_t *status, float *xs, float *lg, int tid)
 {
@@ -156,6 +161,7 @@ __device__ __forceinline__ int dqn_out_row(const float *net, const DqnLayout L, 
                 y = __builtin_fmaf(wv[i].w, xv.w, y);
             }
         }
+        if constexpr (H16) y = f16r_after_fma(y);   // (not v_fma_mixlo_f16: fc16_layout.hip.h)
         lg[tid] = y;
         if (logits_row) logits_row[tid] = y;
     }

@@ -39,15 +39,6 @@ namespace coevo {
 // The raw sums go to LDS as out[channel][position] (odd pitch); BatchNorm + ReLU then runs over them channel by channel.
 typedef float f32x4_acc __attribute__((ext_vector_type(4)));
 
-// f16r of a value an fmaf has just produced, the fp32 result pinned in a register first: left to itself the compiler fuses the
-// pair into v_fma_mixlo_f16, a mixed-precision FMA that rounds the exact sum ONCE to fp16 - the contract (and the reference's
-// half modules, which compute in fp32 and store half) rounds to fp32, then to fp16
-__device__ __forceinline__ float f16r_after_fma(float v)
-{
-    asm("" : "+v"(v));
-    return f16r(v);
-}
-
 // x / 255.0f for x = 0 .. 255, correctly rounded, without the divide: 1/255 split into a float head and tail,
 // fma(x, head, x * tail) equals the IEEE quotient for all 256 inputs (tests/test_host_logic_cpu.py checks the identity
 // in numpy; an LDS table of the quotients cost a dependent, bank-conflicted read per gathered tap)

@@ -10,6 +10,7 @@
 // Noise: eps(seed, stream, p), p = canonical flat index in torch parameters() order (include/coevo.h), the same
 // Philox / Box-Muller as the FCNetwork offspring - the oracle's generic flat perturb is the checker.
 #include "dqn_common.hip.h"
+#include "dqn16_layout.hip.h"
 #include "philox.hip.h"
 
 namespace coevo {
@@ -178,7 +179,12 @@ __device__ inline uint32_t synth_target(uint64_t seed, int64_t ordinal, int t, i
 // FUSED = the output layer of step t-1 rides in this launch (coevo_dqn_out_synth_step): the workgroup of game g first
 // turns the hidden row of its actor (hid[row_prev[g]], left by conv stack + fc1) into logits and the first-max action, then
 // books that action and writes the next frame - one launch per agent-step less than output-layer launch + env launch.
-template <bool FUSED>
+// OUT names the output row that rides along: SYNTH_NO_OUT (coevo_synth_step), SYNTH_OUT_F32 (coevo_dqn_out_synth_step) or
+// SYNTH_OUT_F16 (coevo_dqn16_out_synth_step: `slab` is the fp16 slab as 32-bit words, the row is dqn_out_row<true>, and a task
+// the float16 forward cannot serve (dqn16_bad_task: fc1 has reported it and left its hidden rows alone) gets no output row -
+// the action booked is the word actions_prev already holds, as the unfused pair books it).
+constexpr int SYNTH_NO_OUT = 0, SYNTH_OUT_F32 = 1, SYNTH_OUT_F16 = 2;
+template <int OUT>
 __global__ __launch_bounds__(256) void synth_step_kernel(int32_t *gstate, double *acc, int n_games,
                                                           const int64_t *game_ordinal0, const int32_t *gen_dev,
                                                           int64_t ordinals_per_gen, int t, const int32_t *limit,
@@ -193,16 +199,21 @@ __global__ __launch_bounds__(256) void synth_step_kernel(int32_t *gstate, double
     int64_t ordinal = game_ordinal0[g] + (gen_dev ? (int64_t)(*gen_dev) * ordinals_per_gen : 0);
     const int lim = (ordinal < 0) ? 0 : limit[g];   // a negative ordinal disables the game
     __shared__ int s_last;
+    constexpr bool FUSED = OUT != SYNTH_NO_OUT, H16 = OUT == SYNTH_OUT_F16;
     __shared__ __attribute__((aligned(16))) float xs[FUSED ? DQ_FC1_OUT : 4];
     __shared__ float lg[FUSED ? 64 : 1];
     int action = 0;
+    bool stale = false;   // the fp16 row of a bad task: nothing is computed, the stored word is booked
     if constexpr (FUSED) {
         if (t - 1 < lim) {   // workgroup-uniform; (a finished game's row holds a stale frame: its action is never booked)
             const int row = row_prev[g];
             const coevo_dqn_task task = tasks_prev[task_of_row(tasks_prev, n_tasks_prev, row)];
-            action = dqn_out_row(slab + task.net_off, dqn_layout(C, n_actions), n_actions, hid + (size_t)row * DQ_FC1_OUT,
-                                 nullptr, status, xs, lg, threadIdx.x);
-            if (threadIdx.x == 0) actions_prev[row] = action;
+            if constexpr (H16) stale = dqn16_bad_task(task);   // workgroup-uniform, before any load through net_off and every barrier
+            if (!stale) {
+                action = dqn_out_row<H16>(slab + task.net_off, H16 ? dqn16_layout(C, n_actions) : dqn_layout(C, n_actions),
+                                          n_actions, hid + (size_t)row * DQ_FC1_OUT, nullptr, status, xs, lg, threadIdx.x);
+                if (threadIdx.x == 0) actions_prev[row] = action;
+            }
         }
     }
     if (threadIdx.x == 0) {
@@ -211,7 +222,7 @@ __global__ __launch_bounds__(256) void synth_step_kernel(int32_t *gstate, double
             last = 0xFF; prev_hit = 0;
             acc[3 * (size_t)g] = 0.0; acc[3 * (size_t)g + 1] = 0.0; acc[3 * (size_t)g + 2] = 0.0;
         } else if (t - 1 < lim) {   // book the action of step t-1 (actor = (t-1) & 1)
-            const int a = FUSED ? action : actions_prev[row_prev[g]];
+            const int a = (FUSED && !stale) ? action : actions_prev[row_prev[g]];
             const int hit = ((uint32_t)a == synth_target(seed, ordinal, t - 1, n_actions)) ? 1 : 0;
             const size_t slot = 3 * (size_t)g + ((t - 1) & 1);
             acc[slot] = acc[slot] + (double)(prev_hit - hit);
@@ -308,7 +319,7 @@ extern "C" int coevo_synth_step(int32_t *game_state, double *acc, int n_games, c
     if (!dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;
     if (t > 0 && (!row_prev || !actions_prev)) return COEVO_ERR_ARG;
     if (frames && !row_cur) return COEVO_ERR_ARG;
-    hipLaunchKernelGGL(synth_step_kernel<false>, dim3(n_games), dim3(256), 0, (hipStream_t)stream, game_state, acc, n_games,
+    hipLaunchKernelGGL(synth_step_kernel<SYNTH_NO_OUT>, dim3(n_games), dim3(256), 0, (hipStream_t)stream, game_state, acc, n_games,
                        game_ordinal0, gen_dev, ordinals_per_gen, t, limit, row_prev, const_cast<int32_t *>(actions_prev),
                        row_cur, frames, C, n_actions, seed, nullptr, nullptr, 0, nullptr, nullptr);
     COEVO_HIP_CHECK(hipGetLastError());
@@ -326,9 +337,30 @@ extern "C" int coevo_dqn_out_synth_step(int32_t *game_state, double *acc, int n_
     if (!dqn_shape_ok(C, n_actions) || !row_prev || !actions_prev || (frames && !row_cur)) return COEVO_ERR_ARG;
     if (!slab || !tasks_prev || n_tasks_prev <= 0 || n_rows_total <= 0 || !workspace || !status) return COEVO_ERR_ARG;
     const float *hid = static_cast<const float *>(workspace) + (size_t)n_rows_total * DQ_FC1_IN;   // (deepqn.hip's layout)
-    hipLaunchKernelGGL(synth_step_kernel<true>, dim3(n_games), dim3(256), 0, (hipStream_t)stream, game_state, acc, n_games,
+    hipLaunchKernelGGL(synth_step_kernel<SYNTH_OUT_F32>, dim3(n_games), dim3(256), 0, (hipStream_t)stream, game_state, acc, n_games,
                        game_ordinal0, gen_dev, ordinals_per_gen, t, limit, row_prev, actions_prev, row_cur, frames, C,
                        n_actions, seed, slab, tasks_prev, n_tasks_prev, hid, status);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+// the float16 sibling: `slab` is the fp16 slab (coevo_dqn16_pack's layout, 16-byte aligned), the workspace the one
+// coevo_dqn16_forward_hidden filled
+extern "C" int coevo_dqn16_out_synth_step(int32_t *game_state, double *acc, int n_games, const int64_t *game_ordinal0,
+                                          const int32_t *gen_dev, int64_t ordinals_per_gen, int t, const int32_t *limit,
+                                          const int32_t *row_prev, int32_t *actions_prev, const int32_t *row_cur,
+                                          uint8_t *frames, int C, int n_actions, uint64_t seed, const void *slab,
+                                          const coevo_dqn_task *tasks_prev, int n_tasks_prev, int n_rows_total,
+                                          const void *workspace, int32_t *status, void *stream)
+{
+    if (!game_state || !acc || !game_ordinal0 || !limit || n_games <= 0 || t < 1 || t > 65535) return COEVO_ERR_ARG;
+    if (!dqn_shape_ok(C, n_actions) || !row_prev || !actions_prev || (frames && !row_cur)) return COEVO_ERR_ARG;
+    if (!slab || !tasks_prev || n_tasks_prev <= 0 || n_rows_total <= 0 || !workspace || !status) return COEVO_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(slab) & 15) return COEVO_ERR_ARG;
+    const float *hid = static_cast<const float *>(workspace) + (size_t)n_rows_total * DQ_FC1_IN;   // (dqn16.hip's layout)
+    hipLaunchKernelGGL(synth_step_kernel<SYNTH_OUT_F16>, dim3(n_games), dim3(256), 0, (hipStream_t)stream, game_state, acc,
+                       n_games, game_ordinal0, gen_dev, ordinals_per_gen, t, limit, row_prev, actions_prev, row_cur, frames, C,
+                       n_actions, seed, static_cast<const float *>(slab), tasks_prev, n_tasks_prev, hid, status);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }

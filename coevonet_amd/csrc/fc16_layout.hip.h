@@ -33,6 +33,16 @@ __device__ __forceinline__ float f32_pin(float v)
     return v;
 }
 
+// f16r of a value an fmaf has just produced, the fp32 result pinned in a register first: left to itself the compiler fuses the
+// pair into v_fma_mixlo_f16, a mixed-precision FMA that rounds the exact sum ONCE to fp16 - the contract (and the reference's
+// half modules, which compute in fp32 and store half) rounds to fp32, then to fp16.  (The conv stack of dqn_conv.hip.h and the
+// output row of dqn_common.hip.h round with it.)
+__device__ __forceinline__ float f16r_after_fma(float v)
+{
+    asm("" : "+v"(v));
+    return f16r(v);
+}
+
 // child entry = f16(f32(parent) + noise): the sum in fp32, rounded once to half
 __device__ __forceinline__ float f16_child(float parent, float noise) { return f16r(f32_pin(parent + noise)); }
 // noise16 = f16(noise32), noise32 = sigma * eps the fp32 number the perturb launch added

@@ -5,14 +5,15 @@
 The base net and the ``pop`` perturbed nets of the two roles live in ONE fp16 slab (coevo_dqn16_pack's layout).  A generation is:
 the perturbed nets (coevo_dqn16_perturb_dist from the role's base net, BatchNorm untouched, noise stream (j, 4 gen + role index),
 the distance to the base net fused in when fitness sharing is on), the float16 rollout of the 2 * pop games
-(``HalfSynthRollout``: coevo_synth_step + coevo_dqn16_forward_argmax per agent-step), the update (coevo_es16_fitness,
+(``HalfSynthRollout``: coevo_dqn16_out_synth_step + coevo_dqn16_forward_hidden per agent-step), the update (coevo_es16_fitness,
 coevo_dqn_es16_partial - which draws the noise again and rounds it to fp16, where the float32 engine subtracts the base net from
 the perturbed nets -, coevo_dqn_es16_apply) and the N_EVAL evaluation games of the updated pair.  The rounding points are the
 contract of DESIGN.md 6a "Float16 DeepQN Co-ES".
 
 One rank, one cohort, frames synthesised on the device, ``device_philox`` noise, no antithetic pairs, no centered ranks; the
-caller passes sigma per generation, so the host's adaptive rule can sit on top.  ``DQNESTrainer`` /
-``dqn_evolution_strategy_train`` still refuse float16: this object is the float16 route until the trainers are switched over."""
+caller passes sigma per generation, so the host's adaptive rule sits on top: ``DQNESTrainer`` /
+``dqn_evolution_strategy_train`` build this engine for ``args.precision == "float16"`` and drive ``generation`` with
+``DQNESEngine.generation``'s arguments (dqn_population.dqn_half_route says what they refuse)."""
 from __future__ import annotations
 
 import numpy as np

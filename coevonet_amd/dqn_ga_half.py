@@ -4,15 +4,17 @@
 
 The population, the Hall of Fame, the elites and the stale agent of the two roles live in ONE fp16 slab (coevo_dqn16_pack's
 layout, ``DQNGAEngine``'s regions per role).  A generation is ``DQNGAEngine``'s own code on one rank with float16 calls: the rollout
-of all 2 * pop * hof games plus the evaluation games of the previous generation's best pair (coevo_synth_step +
-coevo_dqn16_forward_argmax per agent-step), then the tail - coevo_ga_select on fp16-valued distances, coevo_ga_adapt_sigma,
+of all 2 * pop * hof games plus the evaluation games of the previous generation's best pair (coevo_dqn16_out_synth_step +
+coevo_dqn16_forward_hidden per agent-step: three launches, as in float32), then the tail - coevo_ga_select on fp16-valued distances, coevo_ga_adapt_sigma,
 the gathers (coevo_net_gather with the stride in words), the offspring with their stale-agent distances fused in
 (coevo_dqn16_perturb_dist, coevo_fc16_distance_finalize) and the counter tick - captured once into a hipGraph and replayed.
 The rounding points are DESIGN.md 6a "Float16 DeepQN" and "Float16 DeepQN breeding".
 
-One rank, one cohort, frames synthesised on the device.  ``DQNGATrainer`` / ``dqn_genetic_algorithm_train`` still refuse
-float16: this object is the float16 route until the trainers are switched over."""
+One rank, one cohort, frames synthesised on the device.  ``DQNGATrainer`` / ``dqn_genetic_algorithm_train`` build this engine
+for ``args.precision == "float16"`` (dqn_population.dqn_half_route says what they refuse)."""
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -23,32 +25,46 @@ from .dqn_population import DQNGAEngine, SynthRollout
 
 class HalfSynthRollout(SynthRollout):
     """``SynthRollout``'s game and task tables (one cohort) over an fp16 slab: ``net_off`` counts 32-bit words of
-    coevo_dqn16_pack's layout.  Per agent-step it enqueues coevo_synth_step (books the previous action, writes the next frames)
-    and coevo_dqn16_forward_argmax; it synchronises with nothing, so a generation can be captured into a graph."""
+    coevo_dqn16_pack's layout.  Three launches per agent-step, the float32 rollout's structure: coevo_dqn16_out_synth_step (the
+    output row of the previous step, its booking, the next frames; coevo_synth_step at t = 0) and the conv-stack and fc1 launches
+    of coevo_dqn16_forward_hidden.  ``COEVO_DQN16_FUSED_OUT=0``, read at construction, keeps the four-launch route
+    (coevo_synth_step + coevo_dqn16_forward_argmax) for A/B runs: the same words in every buffer the engines read.  It
+    synchronises with nothing, so a generation can be captured into a graph."""
 
     def __init__(self, game_nets, net_off, ordinal0, C, n_actions, slab, env_seed, ordinals_per_gen, device="cuda"):
         super().__init__(game_nets, net_off, ordinal0, C, n_actions, slab, env_seed, ordinals_per_gen, device)
         ln = self.lanes[0]
         ln["ws"] = torch.zeros(int(L.load().coevo_dqn16_workspace_bytes(ln["n"])) // 4, dtype=torch.float32, device=device)
+        self.fused_out = os.environ.get("COEVO_DQN16_FUSED_OUT", "1") != "0"
 
     def start_timing(self, pairs=512, every=7):
         raise NotImplementedError("HalfSynthRollout: the float16 forward has no timed form")
 
     def _enqueue_lane(self, ln, T, g, stream, timed):
-        m = ln["n"]
-        lib = L.load()
         for t in range(T + 1):
-            p, q = t & 1, (t - 1) & 1
-            L._check(lib.coevo_synth_step(L._p(self.gstate), L._p(self.acc), m, L._p(self.ordinal0), g, self.ordinals_per_gen,
-                                          t, L._p(self.limit), L._p(ln["rows"][q]) if t else None,
-                                          ln["actions"][q].data_ptr() if t else None,
-                                          L._p(ln["rows"][p]) if t < T else None, L._p(ln["frames"]) if t < T else None,
-                                          self.C, self.n_actions, self.env_seed, stream), "coevo_synth_step")
-            if t < T:
-                L._check(lib.coevo_dqn16_forward_argmax(L._p(self.slab), L._p(ln["tasks"][p]), ln["n_tasks"][p],
-                                                        ln["max_rows"][p], m, self.C, self.n_actions, L._p(ln["frames"]),
-                                                        ln["actions"][p].data_ptr(), None, L._p(self.status), L._p(ln["ws"]),
-                                                        stream), "coevo_dqn16_forward_argmax")
+            self.enqueue_step(ln, t, T, g, stream)
+
+    def enqueue_step(self, ln, t, T, g, stream):
+        """the launches of agent-step t of a T-step rollout (t = T: the closing bookkeeping call alone)"""
+        m, lib = ln["n"], L.load()
+        p, q = t & 1, (t - 1) & 1
+        env = (L._p(self.gstate), L._p(self.acc), m, L._p(self.ordinal0), g, self.ordinals_per_gen, t, L._p(self.limit),
+               L._p(ln["rows"][q]) if t else None, ln["actions"][q].data_ptr() if t else None,
+               L._p(ln["rows"][p]) if t < T else None, L._p(ln["frames"]) if t < T else None, self.C, self.n_actions,
+               self.env_seed)
+        fwd = (L._p(self.slab), L._p(ln["tasks"][p]), ln["n_tasks"][p], ln["max_rows"][p], m, self.C, self.n_actions,
+               L._p(ln["frames"]))
+        if t and self.fused_out:   # the output layer of step t-1 rides in the env-step launch
+            L._check(lib.coevo_dqn16_out_synth_step(*env, L._p(self.slab), L._p(ln["tasks"][q]), ln["n_tasks"][q], m,
+                                                    L._p(ln["ws"]), L._p(self.status), stream), "coevo_dqn16_out_synth_step")
+        else:
+            L._check(lib.coevo_synth_step(*env, stream), "coevo_synth_step")
+        if t < T and self.fused_out:
+            L._check(lib.coevo_dqn16_forward_hidden(*fwd, L._p(self.status), L._p(ln["ws"]), stream),
+                     "coevo_dqn16_forward_hidden")
+        elif t < T:
+            L._check(lib.coevo_dqn16_forward_argmax(*fwd, ln["actions"][p].data_ptr(), None, L._p(self.status),
+                                                    L._p(ln["ws"]), stream), "coevo_dqn16_forward_argmax")
 
     def weight_bytes_per_round(self):
         """algorithmic bytes of one round (two agent-steps): every distinct acting fp16 weight set once per agent-step + the

@@ -17,6 +17,10 @@ device from counter-based noise (``coevo_dqn_perturb``), selection / sigma rule 
 a whole generation as one hipGraph.  Sharded over GPUs by population index with one all-gather of (last-game reward,
 distance) per individual (Co-GA: elites rebuilt from noise, no weight crosses xGMI) or of rewards + chunk partial sums
 (Co-ES), as for the MPE engines.
+
+``args.precision == "float16"`` (DESIGN.md 6a "Float16 DeepQN trainers"): ``DQNGATrainer`` / ``DQNESTrainer`` build
+``dqn_ga_half.HalfDQNGAEngine`` / ``dqn_es_half.HalfDQNESEngine`` from the same initial nets rounded to half - one rank, frames
+synthesised on the device, no Co-ES extension mode; ``population.dqn_half_route`` refuses the rest before anything is loaded.
 """
 from __future__ import annotations
 
@@ -30,7 +34,7 @@ from . import lib as L
 from .atari_synthetic import SYNTH_SEED
 from .deepqn import DeepQN
 from .population import (ES_CHUNKS, N_EVAL, ROLES2, CoESUpdate, NetTable, SlabIO, adapt_mutation_power2, captured, co_es_games2,
-                         co_ga_games2, eval_gate_limits, mean_eval, shard_and_gather, slab_layout)
+                         co_ga_games2, dqn_half_route, eval_gate_limits, mean_eval, shard_and_gather, slab_layout)
 
 SIGMA2 = ("mutation_power_agent_0", "mutation_power_agent_1")
 TASK_ROWS = L.DQN_MAX_ROWS
@@ -550,6 +554,12 @@ def dqn_initial_population(pop, hof, C, n_actions):
     return {r: np.stack(popu[r]) for r in ROLES2}, hof_flat
 
 
+def half_values(flat):
+    """flat float32 parameters rounded to half as ``DeepQN(...).to(torch.float16)`` rounds them (nearest even), kept in float32:
+    what ``DeepQNHalf`` holds and coevo_dqn16_pack stores"""
+    return torch.from_numpy(np.ascontiguousarray(flat, dtype=np.float32)).to(torch.float16).to(torch.float32).numpy()
+
+
 def _env_shape(env, args):
     C = int(getattr(env, "C", None) or env.observation_space(env.agents[0]).shape[-1])
     n = int(getattr(env, "n_actions", None) or env.action_space(env.agents[0]).n)
@@ -557,20 +567,30 @@ def _env_shape(env, args):
 
 
 class DQNGATrainer:
+    """Co-GA over DeepQN through the reference's trainer surface.  args.precision "float16" trains half nets through
+    HalfDQNGAEngine (one rank, frames synthesised on the device; anything else is a ValueError before anything is read or
+    loaded); ``step`` / ``finish`` / ``close`` and ``collect=False`` are the same code over either engine."""
+
     def __init__(self, env, args, collect=True, dist_ctx=None):
+        self.half = dqn_half_route(args, "DeepQN Co-GA training with precision", frames_mode, dist_ctx, "gather_ga2")
         self.env, self.args, self.collect = env, args, collect
         C, n = _env_shape(env, args)
         pop_flat, hof_flat = dqn_initial_population(args.population, args.hof_size, C, n)
         shard, gather = shard_and_gather(dist_ctx, "gather_ga2")
         self.first_ordinal = getattr(env, "n_resets", 1)
-        self.eng = DQNGAEngine(args.population, args.hof_size, args.elites_number, C, n,
-                               args.max_timesteps_per_episode, args.max_evaluation_steps,
-                               env_seed=getattr(env, "seed_value", None) or SYNTH_SEED,
-                               philox_seed=getattr(args, "coevo_seed", 0), shard=shard, gather=gather,
-                               first_ordinal=self.first_ordinal, capacity=max(getattr(args, "generations", 0), 1) + 64,
-                               sigmas=(args.mutation_power_agent_0, args.mutation_power_agent_1),
-                               sig_min=args.min_mutation_power, sig_max=args.max_mutation_power, adaptive=args.adaptive,
-                               frames=frames_mode(args))
+        common = dict(env_seed=getattr(env, "seed_value", None) or SYNTH_SEED, philox_seed=getattr(args, "coevo_seed", 0),
+                      first_ordinal=self.first_ordinal, capacity=max(getattr(args, "generations", 0), 1) + 64,
+                      sigmas=(args.mutation_power_agent_0, args.mutation_power_agent_1),
+                      sig_min=args.min_mutation_power, sig_max=args.max_mutation_power, adaptive=args.adaptive)
+        if self.half:   # the creation order and generator consumption of float32; the nets rounded as .to(float16) rounds
+            from .dqn_ga_half import HalfDQNGAEngine   # (imports this module)
+            pop_flat, hof_flat = ({r: half_values(f[r]) for r in ROLES2} for f in (pop_flat, hof_flat))
+            self.eng = HalfDQNGAEngine(args.population, args.hof_size, args.elites_number, C, n,
+                                       args.max_timesteps_per_episode, args.max_evaluation_steps, **common)
+        else:
+            self.eng = DQNGAEngine(args.population, args.hof_size, args.elites_number, C, n,
+                                   args.max_timesteps_per_episode, args.max_evaluation_steps, shard=shard, gather=gather,
+                                   frames=frames_mode(args), **common)
         self.eng.load_initial(pop_flat, hof_flat)
         self.res = DQNResult()
         self.res.engine = self.eng
@@ -618,7 +638,8 @@ class DQNGATrainer:
 
 
 def dqn_genetic_algorithm_train(env, agent, args, output_dir, collect=True, dist_ctx=None):
-    """genetic_algorithm_train for the two-player Atari games (main.py:181 with --game pong_v3 / boxing_v2)"""
+    """genetic_algorithm_train for the two-player Atari games (main.py:181 with --game pong_v3 / boxing_v2); args.precision
+    "float16" trains half nets (DQNGATrainer)"""
     from .io_utils import MetricsWriter
     tr = DQNGATrainer(env, args, collect=collect, dist_ctx=dist_ctx)
     for _ in range(args.generations):
@@ -741,18 +762,30 @@ class DQNESEngine(_DQNSlabIO, CoESUpdate):
 
 
 class DQNESTrainer:
+    """Co-ES over DeepQN through the reference's trainer surface.  args.precision "float16" trains half base nets through
+    HalfDQNESEngine (one rank, frames synthesised on the device, no antithetic pairs, no centered ranks; anything else is a
+    ValueError before anything is read or loaded); the host's sigma rule sits on top of either engine's ``generation``."""
+
     def __init__(self, env, args, collect=True, dist_ctx=None):
+        self.half = dqn_half_route(args, "DeepQN Co-ES with precision", frames_mode, dist_ctx, "gather_es",
+                                   extensions=("coevo_antithetic", "coevo_centered_rank"))
         self.env, self.args, self.collect = env, args, collect
         C, n = _env_shape(env, args)
         base = {r: dqn_init_flat(C, n) for r in ROLES2}
         shard, gather = shard_and_gather(dist_ctx, "gather_es")
         self.first_ordinal = getattr(env, "n_resets", 1)
-        self.eng = DQNESEngine(args.population, C, n, args.max_timesteps_per_episode, args.max_evaluation_steps,
-                               env_seed=getattr(env, "seed_value", None) or SYNTH_SEED,
-                               philox_seed=getattr(args, "coevo_seed", 0), shard=shard, gather=gather,
-                               first_ordinal=self.first_ordinal, antithetic=getattr(args, "coevo_antithetic", False),
-                               centered_rank=getattr(args, "coevo_centered_rank", False),
-                               chunks=getattr(args, "coevo_es_chunks", ES_CHUNKS), frames=frames_mode(args))
+        common = dict(env_seed=getattr(env, "seed_value", None) or SYNTH_SEED, philox_seed=getattr(args, "coevo_seed", 0),
+                      first_ordinal=self.first_ordinal, chunks=getattr(args, "coevo_es_chunks", ES_CHUNKS))
+        if self.half:   # the two float32 initialisations, rounded as .to(float16) rounds
+            from .dqn_es_half import HalfDQNESEngine   # (imports this module)
+            base = {r: half_values(base[r]) for r in ROLES2}
+            self.eng = HalfDQNESEngine(args.population, C, n, args.max_timesteps_per_episode, args.max_evaluation_steps,
+                                       **common)
+        else:
+            self.eng = DQNESEngine(args.population, C, n, args.max_timesteps_per_episode, args.max_evaluation_steps,
+                                   shard=shard, gather=gather, antithetic=getattr(args, "coevo_antithetic", False),
+                                   centered_rank=getattr(args, "coevo_centered_rank", False), frames=frames_mode(args),
+                                   **common)
         for r in ROLES2:
             self.eng.upload(r, "base", 0, base[r][None])
         self.res = DQNResult()
@@ -767,6 +800,8 @@ class DQNESTrainer:
         if self.collect:
             res.game_rewards.append(eng.ro.acc[:eng.n_main, :2].cpu().numpy().copy())
             res.diversity.append([float(eng.div[ri].item()) if args.fitness_sharing else None for ri in range(2)])
+            if self.half:   # the generation's fit16 of the two roles (fp16 values)
+                res.fitness.append([eng.fitness[ri].cpu().numpy().copy() for ri in range(2)])
         for s, r in enumerate(ROLES2):
             res.rewards[r].append(ev[s])
         if args.adaptive:
@@ -787,7 +822,8 @@ class DQNESTrainer:
 
 def dqn_evolution_strategy_train(env, args, output_dir, collect=True, dist_ctx=None):
     """evolution_strategy_train for the two-player Atari games; returns (base nets [first_0, second_0] as flat parameter
-    vectors, DQNResult)"""
+    vectors, DQNResult).  args.precision "float16" trains half nets (DQNESTrainer); the vectors are then float32 arrays of fp16
+    values, ``DeepQNHalf.flat()``'s convention"""
     from .io_utils import MetricsWriter
     tr = DQNESTrainer(env, args, collect=collect, dist_ctx=dist_ctx)
     for _ in range(args.generations):

@@ -303,7 +303,10 @@ def evolution_strategy_train(env, args, output_dir, rng=None, env_mode=None, col
     """Drop-in for evolutionary_strategy.py:151: returns (agent_0, agent_1, adversary) like the reference; with
     return_result=True also the ESResult history (what the reference only plots).  args.precision "float16" trains half nets
     through HalfESEngine: rng "device_philox" (the argument or args.coevo_rng), device env, one rank, no extension mode;
-    anything else raises ValueError before the GPU is touched (DESIGN 6a "Float16 trainers")."""
+    anything else raises ValueError before the GPU is touched (DESIGN 6a "Float16 trainers").  With args.game pong_v3 /
+    boxing_v2 the DeepQN trainer takes over (dqn_population.dqn_evolution_strategy_train: it returns (base nets, DQNResult));
+    there "float16" trains half DeepQN nets through HalfDQNESEngine on one rank, frames synthesised on the device, no
+    antithetic pairs, no centered ranks (DESIGN 6a "Float16 DeepQN trainers")."""
     import os
     if getattr(args, "game", "simple_adversary_v3") != "simple_adversary_v3":   # the two-player Atari games
         from .dqn_population import dqn_evolution_strategy_train

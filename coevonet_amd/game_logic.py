@@ -160,25 +160,43 @@ def _play_atari_aec(env, player1, player2, args, eval):
     return rewards["first_0"], rewards["second_0"]
 
 
-def _play_atari_device(env, player1, player2, args, eval):
-    """one whole synthetic-env episode on the device (coevo_synth_step + coevo_dqn_forward_argmax per agent-step)"""
+def _play_atari_device(env, player1, player2, args, eval, half=False):
+    """one whole synthetic-env episode on the device: a two-net slab and a one-game rollout (per agent-step the env-step launch
+    with the previous step's output layer in it + conv stack and fc1).  half: two DeepQNHalf players on an fp16 slab
+    (coevo_dqn16_pack, HalfSynthRollout)"""
+    from .dqn_ga_half import HalfSynthRollout
     from .dqn_population import SynthRollout
     dev = "cuda"
     C, n = env.C, env.n_actions
-    stride = int(L.load().coevo_dqn_slab_stride(C, n))
-    slab = torch.zeros(2 * stride, dtype=torch.float32, device=dev)
-    flat = torch.from_numpy(np.stack([player1.flat(), player2.flat()])).to(dev)
-    L.call("coevo_dqn_pack", L._p(flat), L._p(slab), 2, C, n)
+    sym = "coevo_dqn16" if half else "coevo_dqn"
+    stride = int(getattr(L.load(), sym + "_slab_stride")(C, n))
+    slab = torch.zeros(2 * stride, dtype=torch.int32 if half else torch.float32, device=dev)
+    flat = torch.from_numpy(np.ascontiguousarray(np.stack([player1.flat(), player2.flat()]), dtype=np.float32)).to(dev)
+    L.call(sym + "_pack", L._p(flat), L._p(slab), 2, C, n)
     limit = args.max_evaluation_steps if eval else args.max_timesteps_per_episode
     if limit is None:
         raise ValueError("the synthetic Atari env never terminates: a step limit is required")
-    ro = SynthRollout([(0, 1)], [0, stride], [env.ordinal], C, n, slab, env.seed_value, 0, dev)
+    ro = (HalfSynthRollout if half else SynthRollout)([(0, 1)], [0, stride], [env.ordinal], C, n, slab, env.seed_value, 0, dev)
     ro.set_limits([int(limit)])
     ro.enqueue(int(limit), None)
     torch.cuda.synchronize()
     L.raise_on_status(ro.status)
     r = ro.acc.cpu().numpy()[0]
+    if half:
+        _leave_env_stepped(env, int(limit), ro.lanes[0]["actions"].cpu().numpy()[:, 0])
     return float(r[0]), float(r[1])
+
+
+def _leave_env_stepped(env, T, actions):
+    """Two half players walked the AEC loop before their device route existed, and their callers saw the env object stepped:
+    leave it where T calls of env.step leave it.  actions[p]: the last action of the player of parity p"""
+    from .atari_synthetic import synth_target
+    for t in range(max(T - 2, 0), T):   # what the last two steps left in the books holds all of it
+        actor, other = env.possible_agents[t & 1], env.possible_agents[1 - (t & 1)]
+        hit = 1.0 if int(actions[t & 1]) == synth_target(env.seed_value, env.ordinal, t, env.n_actions) else 0.0
+        env._cumulative_rewards[actor] = hit
+        env._cumulative_rewards[other] += -hit
+        env.last_action, env.t, env.agent_selection = int(actions[t & 1]), t + 1, other
 
 
 def play_MPE(env, player1, player2, adversary, args, eval):
@@ -197,12 +215,14 @@ def play_MPE(env, player1, player2, adversary, args, eval):
 
 def play_atari(env, player1, player2, args, eval=False):
     """utils/game_logic_functions.py:84-119 (its own signature has no eval flag - quirk Q10; the call site at :227 passes
-    one, so it is accepted here and selects the step limit as for MPE).  Two float16 players (DeepQNHalf, not a DeepQN)
-    walk the AEC loop, one coevo_dqn16_forward_argmax per agent-step: the device episode route is float32-only"""
-    from .deepqn import DeepQN
-    if isinstance(env, SyntheticAtariAEC) and isinstance(player1, DeepQN) and isinstance(player2, DeepQN) \
-            and not getattr(args, "coevo_host_aec", False):
-        return _play_atari_device(env, player1, player2, args, eval)
+    one, so it is accepted here and selects the step limit as for MPE).  On this package's synthetic env two DeepQN players, or
+    two DeepQNHalf players, play the whole episode on the device (float16: an fp16 slab and a HalfSynthRollout); a mixed pair,
+    another env or args.coevo_host_aec walk the AEC loop, one forward per agent-step"""
+    from .deepqn import DeepQN, DeepQNHalf
+    if isinstance(env, SyntheticAtariAEC) and not getattr(args, "coevo_host_aec", False):
+        for net in (DeepQN, DeepQNHalf):   # (DeepQNHalf is DeepQN's sibling, not a subclass)
+            if isinstance(player1, net) and isinstance(player2, net):
+                return _play_atari_device(env, player1, player2, args, eval, half=net is DeepQNHalf)
     return _play_atari_aec(env, player1, player2, args, eval)
 
 

@@ -941,7 +941,9 @@ def genetic_algorithm_train(env, agent, args, output_dir, rng=None, env_mode=Non
     rng: "host_reference" (default) reproduces the reference's torch RNG stream bit for bit;
          "device_philox" builds offspring on the device (args.coevo_rng may select it as well).
     args.precision "float16" trains half nets through HalfGAEngine: device_philox, device env and one rank only; anything
-    else raises ValueError before the GPU is touched (DESIGN 6a "Float16 trainers")."""
+    else raises ValueError before the GPU is touched (DESIGN 6a "Float16 trainers").  With args.game pong_v3 / boxing_v2 the
+    DeepQN trainer takes over (dqn_population.dqn_genetic_algorithm_train); there "float16" trains half DeepQN nets through
+    HalfDQNGAEngine on one rank with the frames synthesised on the device (DESIGN 6a "Float16 DeepQN trainers")."""
     if getattr(args, "game", "simple_adversary_v3") != "simple_adversary_v3":   # the two-player Atari games
         from .dqn_population import dqn_genetic_algorithm_train
         return dqn_genetic_algorithm_train(env, agent, args, output_dir, collect=collect, dist_ctx=dist_ctx)

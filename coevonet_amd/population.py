@@ -514,17 +514,34 @@ def shard_and_gather(dist_ctx, name):
     return (0, 1), None
 
 
+def _wants_half(args):
+    """False for float32 (or no precision attribute), True for float16, ValueError for anything else"""
+    precision = getattr(args, "precision", "float32")
+    if precision == "float32":
+        return False
+    if precision != "float16":
+        raise ValueError(f"Unsupported precision: {precision}")
+    return True
+
+
+def _half_one_rank_plain(args, what, dist_ctx, gather_name, extensions):
+    """the refusals every float16 trainer shares: more than one rank, an extension mode"""
+    shard, gather = shard_and_gather(dist_ctx, gather_name)
+    if shard != (0, 1) or gather is not None:
+        raise ValueError(f"{what} float16 runs on one rank only, not shard {shard}")
+    for attr in extensions:
+        if getattr(args, attr, False):
+            raise ValueError(f"{what} float16 is not built with args.{attr}")
+
+
 def half_route(args, what, rng, env_mode, dist_ctx, gather_name, extensions=()):
     """Which engines a trainer of the fully connected nets builds: False = the float32 ones, True = the float16 ones
     (HalfGAEngine / HalfESEngine).  What float16 does not cover is refused here with "`what` float16 ...", the first thing a
     trainer does: no other attribute of `args` has been read and the library is not loaded.  A bit-exact host_reference mode
     cannot exist in float16 (the fp16 forward rounds in the canonical order, not in torch's half BLAS order), so the route
     is rng "device_philox" + the device env on one rank, without the extension modes named in `extensions`."""
-    precision = getattr(args, "precision", "float32")
-    if precision == "float32":
+    if not _wants_half(args):
         return False
-    if precision != "float16":
-        raise ValueError(f"Unsupported precision: {precision}")
     rng = rng or getattr(args, "coevo_rng", "host_reference")
     env_mode = env_mode or getattr(args, "coevo_env", "device")
     if rng != "device_philox":
@@ -532,10 +549,18 @@ def half_route(args, what, rng, env_mode, dist_ctx, gather_name, extensions=()):
                          "no bit-exact reference mode in float16")
     if env_mode != "device":
         raise ValueError(f'{what} float16 has the device env only, not env "{env_mode}"')
-    shard, gather = shard_and_gather(dist_ctx, gather_name)
-    if shard != (0, 1) or gather is not None:
-        raise ValueError(f"{what} float16 runs on one rank only, not shard {shard}")
-    for attr in extensions:
-        if getattr(args, attr, False):
-            raise ValueError(f"{what} float16 is not built with args.{attr}")
+    _half_one_rank_plain(args, what, dist_ctx, gather_name, extensions)
+    return True
+
+
+def dqn_half_route(args, what, frames_mode, dist_ctx, gather_name, extensions=()):
+    """half_route for the DeepQN trainers, whose noise is always counter-based and whose env is always the synthetic one on the
+    device: False = DQNGAEngine / DQNESEngine, True = HalfDQNGAEngine / HalfDQNESEngine.  Refused with "`what` float16 ...":
+    frames rendered on the host (``frames_mode(args)``: args.coevo_frames / COEVO_DQN_FRAMES), more than one rank, the
+    extension modes named in `extensions`.  The first thing a trainer does, as above."""
+    if not _wants_half(args):
+        return False
+    if frames_mode(args) != "device":
+        raise ValueError(f'{what} float16 synthesises frames on the device only, not frames "{frames_mode(args)}"')
+    _half_one_rank_plain(args, what, dist_ctx, gather_name, extensions)
     return True

@@ -782,6 +782,12 @@ int64_t coevo_dqn16_workspace_bytes(int n_rows_total);   /* conv3 activations + 
 int coevo_dqn16_forward_argmax(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
                                int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *actions,
                                float *logits, int32_t *status, void *workspace, void *stream);
+/* coevo_dqn16_forward_argmax without its output-layer launch: conv stack + fc1, two launches.  Leaves the hidden rows (post-ReLU
+ * fc1 outputs, fp16 values) in the workspace where coevo_dqn16_forward_argmax puts them, for coevo_dqn16_out_synth_step.  The same
+ * argument checks (the 16-byte alignment of `slab` included) and the same COEVO_ST_BAD_TASK rule. */
+int coevo_dqn16_forward_hidden(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
+                               int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *status,
+                               void *workspace, void *stream);
 
 /* ---------------------------------------------------------------- DeepQN population engine (cfg 4 / cfg 5) ---------- */
 /* Offspring of the DeepQN layout on the device: child = parent +- sigma * eps(seed, stream, p), p = canonical flat index
@@ -898,6 +904,19 @@ int coevo_dqn_out_synth_step(int32_t *game_state, double *acc, int n_games, cons
                              const int32_t *row_prev, int32_t *actions_prev, const int32_t *row_cur, uint8_t *frames, int C,
                              int n_actions, uint64_t seed, const float *slab, const coevo_dqn_task *tasks_prev,
                              int n_tasks_prev, int n_rows_total, const void *workspace, int32_t *status, void *stream);
+/* coevo_dqn_out_synth_step over an fp16 slab (coevo_dqn16_pack's layout, 16-byte aligned; the workspace is the one
+ * coevo_dqn16_forward_hidden filled): the float16 output row - the sequential-k fp32 chain from the bias, rounded once to fp16,
+ * first maximum of a strict '>' scan - then the same booking and the same next frame.  Same effects as
+ * coevo_dqn16_forward_argmax + coevo_synth_step with the same ONE exception (a finished or disabled game's row is not
+ * evaluated: its actions_prev word is left alone and raises nothing).  A task the float16 forward cannot serve (n_rows outside
+ * 1 .. COEVO_DQN_MAX_ROWS, net_off not a multiple of 4 words: fc1 has raised COEVO_ST_BAD_TASK) gets no output row, nothing is
+ * loaded through its net_off, and the action booked is the word actions_prev already holds - what the unfused pair books.
+ * COEVO_ERR_ARG (nothing written): a NULL pointer, t < 1, a bad shape, a slab that is not 16-byte aligned. */
+int coevo_dqn16_out_synth_step(int32_t *game_state, double *acc, int n_games, const int64_t *game_ordinal0,
+                               const int32_t *gen_dev, int64_t ordinals_per_gen, int t, const int32_t *limit,
+                               const int32_t *row_prev, int32_t *actions_prev, const int32_t *row_cur, uint8_t *frames, int C,
+                               int n_actions, uint64_t seed, const void *slab, const coevo_dqn_task *tasks_prev,
+                               int n_tasks_prev, int n_rows_total, const void *workspace, int32_t *status, void *stream);
 
 /* The DeepQN games with the env on the HOST (PCIe-inclusive form of cfg 4 / cfg 5): what play_atari drives through env.observe
  * / env.step / env.last (utils/game_logic_functions.py:84-120) when the env lives in host memory (:47-53), for all of a rank's
