@@ -2,52 +2,106 @@
 
 PyTorch-ROCm is only plumbing here: tensors give device memory (``data_ptr()``) and streams.  There is NO CPU or
 eager fallback: if the HIP library is missing or a call fails, this raises.
+
+The header is the one statement of the ABI: ``parse_header`` turns its text into the constants, the ``ctypes.Structure``
+mirrors and the signature table ``_SIGS`` at import.  An entry point, struct or ``COEVO_*`` value declared there is bound here.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
+import re
 
 import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COEVO_LIB") or os.path.join(HERE, "libcoevo.so")  # COEVO_LIB: A/B builds
-
-OBS_STRIDE = 12
-LOGIT_STRIDE = 8
-FC_MAX_ROWS = 32
-MPE_STATE_DOUBLES = 24
-STAMP_SLOTS = 32
-ST_NAMES = {1: "input contains inf or NaN", 2: "output contains inf or NaN after fc1",
-            4: "output contains inf or NaN after fc2", 8: "output contains inf or NaN",
-            16: "no action selected (current_best_position = -1)",
-            32: "persistent rollout: a workgroup timed out waiting for the other rows of its games (COEVO_ST_SYNC_TIMEOUT)",
-            64: "fp16 forward: a task with a bad width, row count or unaligned net offset was skipped (COEVO_ST_BAD_TASK)"}
-
-DQN_LOGIT_STRIDE = 32
-DQN_FC1_TILED = 0x100   # COEVO_DQN_FC1_TILED: or-ed into the channel argument of the layout-dependent DeepQN entry points
-DQP_SKIP_BN = 1         # COEVO_DQP_SKIP_BN: the BatchNorm affine keeps its words (Co-ES)
-DQN_MAX_ROWS = 16
-DQN_TASK_DTYPE = np.dtype([("net_off", "<i8"), ("row_begin", "<i4"), ("n_rows", "<i4")])
-
-# numpy view of coevo_fc_task
-TASK_DTYPE = np.dtype([("net_off", "<i8"), ("row_begin", "<i4"), ("n_rows", "<i4"), ("D", "<i4"),
-                       ("reserved", "<i4")])
-TASK_RESIDENT = 1   # coevo_fc_task.reserved bit COEVO_TASK_RESIDENT (include/coevo.h)
-# COEVO_TASK_TILED: a shared-opponent task reads W2 from the net's tile-major twin, W2_FLOATS floats that start
-# (reserved >> TASK_TWIN_SHIFT) * TASK_TWIN_UNIT floats into the slab
-TASK_TILED, TASK_TWIN_SHIFT, TASK_TWIN_UNIT, W2_FLOATS = 2, 8, 1024, 512 * 256
+HEADER_PATH = os.path.join(HERE, "..", "include", "coevo.h")
 
 
-def task_tiled_flags(twin_off):
-    """coevo_fc_task.reserved of a task whose net's W2 twin starts twin_off floats into the slab"""
-    assert twin_off % TASK_TWIN_UNIT == 0 and 0 <= twin_off // TASK_TWIN_UNIT < 1 << (31 - TASK_TWIN_SHIFT)
-    return TASK_TILED | (twin_off // TASK_TWIN_UNIT) << TASK_TWIN_SHIFT
+class CoevoError(RuntimeError):
+    pass
+
+
+# ---------------------------------------------------------------------------------------------------- the header reader
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+_POINTED_TO = ("void", "char", "uint8_t")   # what the header names behind a '*' only
+
+
+def _declare(text, structs, decl, spec=None):
+    """one C declarator, 'const float *obs' or 'tasks[2]' -> (name, ctypes type or None for void, type word); `spec` is the
+    type word of the list's first declarator for the later ones ('int32_t game_first, count').  `decl` is quoted in errors."""
+    m = re.fullmatch(r"([\w\s]*?)\s*(\**)\s*(\w+)\s*(?:\[(\d+)\])?", text.strip())
+    words = [w for w in (m.group(1).split() if m else []) if w not in ("const", "struct")]
+    if not m or len(words) > 1 or not (words or spec):
+        raise CoevoError(f"include/coevo.h: cannot read the declarator {text.strip()!r} in {decl!r}")
+    base = words[0] if words else spec
+    known = structs.get(base) or _SCALARS.get(base)
+    if m.group(2):   # every pointer is an address; const char * is a string
+        if known is None and base not in _POINTED_TO:
+            raise CoevoError(f"include/coevo.h: pointer to the unknown type {base!r} in {decl!r}")
+        t = C.c_char_p if base == "char" else C.c_void_p
+    elif base == "void":
+        t = None
+    elif known is not None:
+        t = known
+    else:
+        raise CoevoError(f"include/coevo.h: unknown type {base!r} in {decl!r}")
+    if m.group(4):
+        t = t * int(m.group(4))
+    return m.group(3), t, base
+
+
+def parse_header(text, mirror=lambda name, fields: type(name, (C.Structure,), {"_fields_": fields})):
+    """the text of include/coevo.h -> ({COEVO_X: int}, {struct name: ctypes.Structure class}, {entry point: (restype,
+    [argtypes])}).  The grammar is the header's, not C's: comments, ``#define NAME`` + a decimal or hex literal, a
+    parenthesised negative or a product of earlier names, ``typedef struct [tag] { fields } name;`` and prototypes.  Whatever
+    does not fit raises CoevoError with the declaration quoted; nothing is guessed.  mirror(name, fields) makes a struct's class."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    consts, structs, sigs = {}, {}, {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(.*)$", text, flags=re.M):
+        v = value.strip()
+        v = v[1:-1].strip() if v.startswith("(") and v.endswith(")") else v
+        factors = [f.strip() for f in v.split("*")]
+        if re.fullmatch(r"-?(0|[1-9]\d*)|0[xX][0-9a-fA-F]+", v):
+            consts[name] = int(v, 0)
+        elif all(f in consts for f in factors):
+            consts[name] = math.prod(consts[f] for f in factors)
+        elif v:   # a bare '#define COEVO_H' is the include guard
+            raise CoevoError(f"include/coevo.h: not a literal or a product of earlier names: '#define {name}{value.rstrip()}'")
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus.*?^[ \t]*#[ \t]*endif.*?$", "", text, flags=re.S | re.M)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+
+    def struct(m):
+        decl, fields = f"struct {m.group(2)}", []
+        for line in filter(None, (d.strip() for d in m.group(1).split(";"))):
+            spec = None
+            for part in line.split(","):
+                field, t, spec = _declare(part, structs, f"{decl}: {' '.join(line.split())}", spec)
+                if t is None:
+                    raise CoevoError(f"include/coevo.h: a void field in {decl}: {line!r}")
+                fields.append((field, t))
+        structs[m.group(2)] = mirror(m.group(2), fields)
+        return ""
+    text = re.sub(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"(.*?\w)\s*\((.*)\)", decl)
+        if not m:
+            raise CoevoError(f"include/coevo.h: neither a typedef struct nor a prototype: {decl!r}")
+        name, res, _ = _declare(m.group(1), structs, decl)
+        args = [] if m.group(2).strip() == "void" else [_declare(p, structs, decl)[1] for p in m.group(2).split(",")]
+        if None in args:
+            raise CoevoError(f"include/coevo.h: a void argument in {decl!r}")
+        sigs[name] = (res, args)
+    return consts, structs, sigs
 
 
 class PCG64State(C.Structure):
-    _fields_ = [("state_hi", C.c_uint64), ("state_lo", C.c_uint64), ("inc_hi", C.c_uint64), ("inc_lo", C.c_uint64)]
+    """coevo_pcg64, derived like the others but under Python field names without the header's pcg_ prefix (state_hi, state_lo,
+    inc_hi, inc_lo): the recorded launch scripts under tests/golden name them so"""
 
     @classmethod
     def from_seed(cls, seed):
@@ -56,295 +110,70 @@ class PCG64State(C.Structure):
         return cls(st["state"] >> 64, st["state"] & m, st["inc"] >> 64, st["inc"] & m)
 
 
-class PerturbJob(C.Structure):   # coevo_fc_perturb_job
-    _fields_ = [("parent_slab", C.c_void_p), ("parent_idx", C.c_void_p), ("child_slab", C.c_void_p),
-                ("sigma_dev", C.c_void_p), ("dist_ref", C.c_void_p), ("dist_partial", C.c_void_p),
-                ("child_first", C.c_int32), ("n_children", C.c_int32), ("D", C.c_int32),
-                ("stream_lo_first", C.c_uint32), ("stream_hi", C.c_uint32), ("pad", C.c_int32)]
+def _mirror(name, fields):
+    if name != "coevo_pcg64":
+        return type(name, (C.Structure,), {"_fields_": fields})
+    PCG64State._fields_ = [(f[len("pcg_"):], t) for f, t in fields]
+    return PCG64State
 
 
-class Perturb16Job(C.Structure):   # coevo_fc16_perturb_job: PerturbJob's fields over fp16 slabs
-    _fields_ = list(PerturbJob._fields_)
+def _header_text():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise CoevoError(f"{HEADER_PATH} is missing: the binding is derived from the header ({e})") from e
 
 
-class FinalizeJob(C.Structure):  # coevo_fc_finalize_job
-    _fields_ = [("dist_partial", C.c_void_p), ("dist", C.c_void_p), ("head", C.c_void_p), ("n_blocks", C.c_int32),
-                ("n", C.c_int32), ("first", C.c_int32), ("pad", C.c_int32)]
+K, STRUCTS, _SIGS = parse_header(_header_text(), _mirror)
+
+OBS_STRIDE, LOGIT_STRIDE, FC_MAX_ROWS = K["COEVO_OBS_STRIDE"], K["COEVO_LOGIT_STRIDE"], K["COEVO_FC_MAX_ROWS"]
+MPE_STATE_DOUBLES, STAMP_SLOTS = K["COEVO_MPE_STATE_DOUBLES"], K["COEVO_STAMP_SLOTS"]
+ST_NAMES = {K["COEVO_ST_BAD_INPUT"]: "input contains inf or NaN",
+            K["COEVO_ST_BAD_FC1"]: "output contains inf or NaN after fc1",
+            K["COEVO_ST_BAD_FC2"]: "output contains inf or NaN after fc2",
+            K["COEVO_ST_BAD_OUT"]: "output contains inf or NaN",
+            K["COEVO_ST_NO_ACTION"]: "no action selected (current_best_position = -1)",
+            K["COEVO_ST_SYNC_TIMEOUT"]: "persistent rollout: a workgroup timed out waiting for the other rows of its games "
+                                        "(COEVO_ST_SYNC_TIMEOUT)",
+            K["COEVO_ST_BAD_TASK"]: "fp16 forward: a task with a bad width, row count or unaligned net offset was skipped "
+                                    "(COEVO_ST_BAD_TASK)"}
+
+DQN_LOGIT_STRIDE, DQN_MAX_ROWS = K["COEVO_DQN_LOGIT_STRIDE"], K["COEVO_DQN_MAX_ROWS"]
+DQN_FC1_TILED = K["COEVO_DQN_FC1_TILED"]   # or-ed into the channel argument of the layout-dependent DeepQN entry points
+DQP_SKIP_BN = K["COEVO_DQP_SKIP_BN"]       # the BatchNorm affine keeps its words (Co-ES)
 
 
-class ResetSeg(C.Structure):     # coevo_reset_seg
-    _fields_ = [("game_first", C.c_int32), ("count", C.c_int32), ("first_ordinal", C.c_uint64)]
+def _dtype(struct):
+    """numpy view of a header struct (one without padding)"""
+    dt = np.dtype([(f, np.dtype(t)) for f, t in struct._fields_])
+    assert dt.itemsize == C.sizeof(struct), struct
+    return dt
 
 
-class FinalPack(C.Structure):    # coevo_final_pack
-    _fields_ = [("out", C.c_void_p), ("dist", C.c_void_p), ("n_roles", C.c_int32), ("n_local", C.c_int32), ("hof", C.c_int32),
-                ("dist_pitch", C.c_int32), ("dist_first", C.c_int32), ("reserved", C.c_int32)]
+TASK_DTYPE, DQN_TASK_DTYPE = _dtype(STRUCTS["coevo_fc_task"]), _dtype(STRUCTS["coevo_dqn_task"])
+TASK_RESIDENT = K["COEVO_TASK_RESIDENT"]   # coevo_fc_task.reserved bit
+# COEVO_TASK_TILED: a shared-opponent task reads W2 from the net's tile-major twin, W2_FLOATS floats that start
+# (reserved >> TASK_TWIN_SHIFT) * TASK_TWIN_UNIT floats into the slab
+TASK_TILED, TASK_TWIN_SHIFT, TASK_TWIN_UNIT = K["COEVO_TASK_TILED"], K["COEVO_TASK_TWIN_SHIFT"], K["COEVO_TASK_TWIN_UNIT"]
+W2_FLOATS = K["COEVO_FC_W2_FLOATS"]
 
 
-class RolloutDesc(C.Structure):
-    _fields_ = [("slab", C.c_void_p), ("heavy", C.c_void_p), ("n_heavy", C.c_int32), ("heavy_max_rows", C.c_int32),
-                ("light", C.c_void_p), ("n_light", C.c_int32), ("light_max_rows", C.c_int32),
-                ("state", C.c_void_p), ("n_games", C.c_int32), ("n_cycles", C.c_int32),
-                ("row_game", C.c_void_p), ("row_slot", C.c_void_p), ("game_rows", C.c_void_p),
-                ("actions", C.c_void_p), ("status", C.c_void_p), ("game_limit", C.c_void_p),
-                ("rewards", C.c_void_p), ("pos_first", C.c_int32), ("n_cohorts", C.c_int32),
-                ("state_alt", C.c_void_p), ("actions_by_game", C.c_void_p), ("light_stamps", C.c_void_p),
-                ("heavy_begin", C.c_void_p), ("light_begin", C.c_void_p),
-                ("merged", C.c_int32), ("concurrent_hint", C.c_int32), ("stamps_armed", C.c_int32), ("sync_cleared", C.c_int32),
-                ("sync_words", C.c_void_p), ("pack", C.c_void_p)]
+def task_tiled_flags(twin_off):
+    """coevo_fc_task.reserved of a task whose net's W2 twin starts twin_off floats into the slab"""
+    assert twin_off % TASK_TWIN_UNIT == 0 and 0 <= twin_off // TASK_TWIN_UNIT < 1 << (31 - TASK_TWIN_SHIFT)
+    return TASK_TILED | (twin_off // TASK_TWIN_UNIT) << TASK_TWIN_SHIFT
 
 
-class HostCohort(C.Structure):        # coevo_host_cohort
-    _fields_ = [("heavy", C.c_void_p), ("light", C.c_void_p), ("games", C.c_void_p), ("n_heavy", C.c_int32),
-                ("heavy_max_rows", C.c_int32), ("n_light", C.c_int32), ("light_max_rows", C.c_int32),
-                ("n_games", C.c_int32), ("row_first", C.c_int32), ("n_rows", C.c_int32), ("reserved", C.c_int32)]
-
-
-class HostRolloutDesc(C.Structure):   # coevo_host_rollout_desc
-    _fields_ = [("slab", C.c_void_p), ("state", C.c_void_p), ("game_rows", C.c_void_p), ("game_limit", C.c_void_p),
-                ("obs_host", C.c_void_p), ("obs_dev", C.c_void_p), ("actions_host", C.c_void_p),
-                ("actions_dev", C.c_void_p), ("status", C.c_void_p), ("cohorts", C.c_void_p), ("phase_us", C.c_void_p),
-                ("n_games", C.c_int32), ("n_rows", C.c_int32), ("n_cycles", C.c_int32), ("n_cohorts", C.c_int32),
-                ("pos_first", C.c_int32), ("zero_copy", C.c_int32), ("reset_ordinals", C.c_void_p),
-                ("reset_rng", PCG64State)]
-
-
-class FrameCohort(C.Structure):       # coevo_frame_cohort
-    _fields_ = [("tasks", C.c_void_p * 2), ("rows", C.c_void_p * 2), ("frames_host", C.c_void_p),
-                ("frames_dev", C.c_void_p), ("actions_host", C.c_void_p), ("actions_dev", C.c_void_p),
-                ("workspace", C.c_void_p), ("n_tasks", C.c_int32 * 2), ("max_rows", C.c_int32 * 2),
-                ("game_first", C.c_int32), ("n_games", C.c_int32)]
-
-
-class FramesRolloutDesc(C.Structure):   # coevo_frames_rollout_desc
-    _fields_ = [("slab", C.c_void_p), ("status", C.c_void_p), ("game_state", C.c_void_p), ("acc", C.c_void_p),
-                ("game_ordinal0", C.c_void_p), ("limit", C.c_void_p), ("cohorts", C.c_void_p), ("phase_us", C.c_void_p),
-                ("generation", C.c_int64), ("ordinals_per_gen", C.c_int64), ("seed", C.c_uint64),
-                ("n_games", C.c_int32), ("n_cohorts", C.c_int32), ("C", C.c_int32), ("n_actions", C.c_int32),
-                ("T", C.c_int32), ("reserved", C.c_int32)]
-
-
-class GaSelectRole(C.Structure):
-    _fields_ = [("dist", C.c_void_p), ("rewards", C.c_void_p), ("diversity", C.c_void_p), ("fitness", C.c_void_p),
-                ("order", C.c_void_p), ("best_dist", C.c_void_p), ("game_first", C.c_int32), ("slot", C.c_int32)]
-
-
-class GaAdaptArgs(C.Structure):     # coevo_ga_adapt_args
-    _fields_ = [("rewards", C.c_void_p), ("gen_dev", C.c_void_p), ("hist", C.c_void_p), ("sig_hist", C.c_void_p),
-                ("sigma64", C.c_void_p), ("sigma32", C.c_void_p), ("sigma32_prev", C.c_void_p), ("sig_min", C.c_double),
-                ("sig_max", C.c_double), ("eval_first_game", C.c_int32), ("cap", C.c_int32), ("adaptive", C.c_int32),
-                ("reserved", C.c_int32)]
-
-
-class GaPromoteRole(C.Structure):   # coevo_ga_promote_role, and coevo_ga16_promote_role (the same fields, untyped regions)
-    _fields_ = [("pop", C.c_void_p), ("hof", C.c_void_p), ("elite", C.c_void_p), ("order", C.c_void_p),
-                ("D", C.c_int32), ("elites_from_pop", C.c_int32), ("best_to_pop0", C.c_int32), ("reserved", C.c_int32)]
-
-
-class CoevoError(RuntimeError):
-    pass
-
+PerturbJob, Perturb16Job = STRUCTS["coevo_fc_perturb_job"], STRUCTS["coevo_fc16_perturb_job"]
+FinalizeJob, ResetSeg, FinalPack = STRUCTS["coevo_fc_finalize_job"], STRUCTS["coevo_reset_seg"], STRUCTS["coevo_final_pack"]
+RolloutDesc = STRUCTS["coevo_rollout_desc"]
+HostCohort, HostRolloutDesc = STRUCTS["coevo_host_cohort"], STRUCTS["coevo_host_rollout_desc"]
+FrameCohort, FramesRolloutDesc = STRUCTS["coevo_frame_cohort"], STRUCTS["coevo_frames_rollout_desc"]
+GaSelectRole, GaAdaptArgs = STRUCTS["coevo_ga_select_role"], STRUCTS["coevo_ga_adapt_args"]
+GaPromoteRole = STRUCTS["coevo_ga_promote_role"]   # also serves coevo_ga16_promote_role: the same fields, untyped regions
 
 _lib = None
-_SIGS = {
-    "coevo_version": (C.c_int, []),
-    "coevo_build_flags": (C.c_char_p, []),
-    "coevo_fc_param_count": (C.c_int64, [C.c_int]),
-    "coevo_fc_slab_stride": (C.c_int64, [C.c_int]),
-    "coevo_fc_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_fc_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_fc_forward_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_fc16_slab_stride": (C.c_int64, [C.c_int]),
-    "coevo_fc16_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_fc16_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_fc16_forward_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_mpe16_policy_cycle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_mpe16_rollout": (C.c_int, [C.POINTER(RolloutDesc), C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_fc16_perturb_blocks": (C.c_int64, [C.c_int]),
-    "coevo_fc16_perturb_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                          C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p]),
-    "coevo_fc16_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_fc16_distance_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                               C.c_void_p]),
-    "coevo_fc16_perturb_dist_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_fc16_distance_finalize_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_fc16_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_ga16_promote": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_es16_partial_floats": (C.c_int64, [C.c_int]),
-    "coevo_es16_fitness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_es16_partial": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                     C.c_void_p, C.c_void_p]),
-    "coevo_es16_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p]),
-    "coevo_fc_forward_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_mpe_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, PCG64State, C.c_uint64, C.c_void_p]),
-    "coevo_mpe_reset_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, PCG64State, C.c_void_p]),
-    "coevo_mpe_reset_multi_arm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, PCG64State, C.c_void_p, C.c_int,
-                                            C.c_void_p]),
-    "coevo_mpe_reset_multi_prep": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, PCG64State, C.c_void_p, C.c_int,
-                                             C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_ga_select_adapt": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                        C.c_void_p]),
-    "coevo_ga_promote_tick": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_ga_promote_tick_tiled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_fc_w2_tile_major": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_fc_perturb_dist_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_fc_distance_finalize_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_mpe_reset_gen": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, PCG64State, C.c_int64, C.c_void_p,
-                                      C.c_int64, C.c_void_p]),
-    "coevo_mpe_observe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_mpe_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                 C.c_void_p]),
-    "coevo_mpe_host_reset": (C.c_int, [C.c_void_p, C.c_int, PCG64State, C.c_void_p]),
-    "coevo_mpe_host_reset_games": (C.c_int, [C.c_void_p, C.c_int, PCG64State, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
-    "coevo_mpe_host_observe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_mpe_host_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
-    "coevo_mpe_host_step_games": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_host_rollout_create": (C.c_void_p, [C.c_int, C.c_int]),
-    "coevo_host_rollout_destroy": (None, [C.c_void_p]),
-    "coevo_host_rollout_threads": (C.c_int, [C.c_void_p]),
-    "coevo_host_rollout_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_mpe_host_rollout": (C.c_int, [C.c_void_p, C.POINTER(HostRolloutDesc), C.c_void_p]),
-    "coevo_host_placement_choose": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int,
-                                              C.c_void_p, C.c_void_p]),
-    "coevo_host_rollout_placement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_host_rollout_alloc": (C.c_void_p, [C.c_void_p, C.c_size_t]),
-    "coevo_host_rollout_debug_seed_counters": (C.c_int, [C.c_void_p, C.c_uint32]),
-    "coevo_dqn_host_frames_rollout": (C.c_int, [C.c_void_p, C.POINTER(FramesRolloutDesc), C.c_void_p]),
-    "coevo_synth_frame_host": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int]),
-    "coevo_mpe_rewards": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_mpe_policy_cycle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_mpe_cycle_kernel_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "coevo_mpe_persistent_sync_words": (C.c_int, [C.c_int]),
-    "coevo_mpe_persistent_fits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "coevo_mpe_rollout_persistent": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                               C.c_int, C.c_void_p]),
-    "coevo_rollout_ctx_create": (C.c_void_p, [C.c_int]),
-    "coevo_rollout_ctx_destroy": (None, [C.c_void_p]),
-    "coevo_ga_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_ga_select_gathered": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_ga_promote": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_ga_promote_rebuild": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32,
-                                           C.c_void_p, C.c_void_p]),
-    "coevo_mpe_final_step_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_fc_distance_finalize_multi_tick": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_rollout_ctx_reserve_cohorts": (C.c_int, [C.c_void_p, C.c_int]),
-    "coevo_rollout_ctx_cohort_stream": (C.c_void_p, [C.c_void_p, C.c_int]),
-    "coevo_rollout_ctx_reset_timing": (C.c_int, [C.c_void_p]),
-    "coevo_rollout_ctx_light_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int]),
-    "coevo_mpe_rollout": (C.c_int, [C.POINTER(RolloutDesc), C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_mpe_policy_cycle_stamped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p]),
-    "coevo_dqn_param_count": (C.c_int64, [C.c_int, C.c_int]),
-    "coevo_dqn_slab_stride": (C.c_int64, [C.c_int, C.c_int]),
-    "coevo_dqn_workspace_bytes": (C.c_int64, [C.c_int]),
-    "coevo_dqn_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_dqn_forward_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_dqn_forward_argmax_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_int, C.c_void_p]),
-    "coevo_dqn_forward_hidden_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_dqn_out_synth_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                           C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                           C.c_void_p]),
-    "coevo_dqn16_slab_stride": (C.c_int64, [C.c_int, C.c_int]),
-    "coevo_dqn16_workspace_bytes": (C.c_int64, [C.c_int]),
-    "coevo_dqn16_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_dqn16_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_dqn16_forward_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_dqn16_forward_hidden": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_dqn16_out_synth_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                             C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                             C.c_void_p]),
-    "coevo_dqn16_perturb_blocks": (C.c_int64, [C.c_int, C.c_int]),
-    "coevo_dqn16_perturb_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                           C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]),
-    "coevo_dqn16_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_dqn_es16_partial_floats": (C.c_int64, [C.c_int, C.c_int]),
-    "coevo_dqn_es16_partial": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32,
-                                         C.c_uint32, C.c_void_p, C.c_void_p]),
-    "coevo_dqn_es16_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
-                                       C.c_void_p]),
-    "coevo_timing_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "coevo_timing_end": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "coevo_dqn_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_dqn_relayout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_dqn_perturb_blocks": (C.c_int64, [C.c_int, C.c_int]),
-    "coevo_dqn_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                    C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int,
-                                    C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_dqn_es_partial": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_dqn_es_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int,
-                                     C.c_void_p, C.c_float, C.c_void_p]),
-    "coevo_net_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
-    "coevo_synth_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                   C.c_uint64, C.c_void_p]),
-    "coevo_mpe_policy_cycle_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_mpe_policy_cycle_merged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                C.c_int, C.c_int, C.c_void_p]),
-    "coevo_mpe_final_step": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                       C.c_void_p]),
-    "coevo_noise_rounds": (C.c_int, []),
-    "coevo_philox4x32": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_philox_normals": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_fc_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                   C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
-    "coevo_fc_perturb_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                         C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
-    "coevo_es_partial": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                   C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_es_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
-                                 C.c_float, C.c_void_p]),
-    "coevo_centered_ranks": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_fc_rebuild_elites": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint64,
-                                          C.c_uint32, C.c_void_p, C.c_void_p]),
-    "coevo_fc_perturb_gen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                       C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_fc_perturb_blocks": (C.c_int64, [C.c_int]),
-    "coevo_fc_perturb_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                        C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p]),
-    "coevo_fc_distance_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                             C.c_void_p]),
-    "coevo_gather_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_ga_adapt_sigma": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                       C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p]),
-    "coevo_counter_add": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    "coevo_fc_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    "coevo_es_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float,
-                                  C.c_void_p]),
-    "coevo_fc_diversity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "coevo_fc_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_sharing_score": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "coevo_ga_fitness": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]),
-    "coevo_rank_desc": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-}
 
 
 def exported_symbols():

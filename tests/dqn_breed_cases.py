@@ -16,13 +16,14 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from coevonet_amd import lib as L
 from oracle import ref_port as rp
 from tests import breed_cases as bc
 
 F32 = np.float32
 M32 = bc.M32
 BLOCK = bc.BLOCK                  # slab positions per workgroup of dqn_perturb_kernel = per distance partial
-TILED = 0x100                     # COEVO_DQN_FC1_TILED, or-ed into the channel argument (include/coevo.h)
+TILED = L.DQN_FC1_TILED           # COEVO_DQN_FC1_TILED, or-ed into the channel argument
 FC1_IN, FC1_OUT = 3136, 512
 _quiet = dict(over="ignore", invalid="ignore", divide="ignore", under="ignore")
 

@@ -13,10 +13,11 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from coevonet_amd import lib as L
 from oracle import ref_port as rp
 from tests.fc_edge_nets import last_maximum, same_bits_up_to_nan   # noqa: F401  (re-exported for the two test files)
 
-NO_ACTION = 16            # COEVO_ST_NO_ACTION (include/coevo.h): the only bit the DeepQN forward raises
+NO_ACTION = L.K["COEVO_ST_NO_ACTION"]   # the only bit the DeepQN forward raises
 MIN_NORMAL = np.float32(2.0 ** -126)
 SENT_A, SENT_L = -7, np.float32(777.0)
 TENSORS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "conv3.weight", "conv3.bias", "fc1.weight",

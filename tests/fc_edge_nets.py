@@ -7,10 +7,12 @@ No GPU and no libcoevo needed: tests/test_fc_forward_edges_gpu.py imports the li
 import numpy as np
 import torch
 
+from coevonet_amd import lib as L
 from oracle import ref_port as rp
 
 H1, H2, NACT = rp.H1, rp.H2, rp.NACT
-BAD_INPUT, BAD_FC1, BAD_FC2, BAD_OUT, NO_ACTION, SYNC_TIMEOUT = 1, 2, 4, 8, 16, 32   # COEVO_ST_* (include/coevo.h)
+BAD_INPUT, BAD_FC1, BAD_FC2, BAD_OUT, NO_ACTION, SYNC_TIMEOUT = (
+    L.K["COEVO_ST_" + n] for n in ("BAD_INPUT", "BAD_FC1", "BAD_FC2", "BAD_OUT", "NO_ACTION", "SYNC_TIMEOUT"))
 MIN_NORMAL = np.float32(2.0 ** -126)
 
 

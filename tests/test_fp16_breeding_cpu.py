@@ -1,9 +1,6 @@
 """Float16 Co-GA breeding without a GPU: the CPU restatement (tests/ga16_checker.py) against torch's half update and against
-numpy's float16 evaluation of the reference's distance formula, the rounding edges, the new C-ABI symbols in the header
-and the binding, and HalfGAEngine's refusals."""
-import os
-import re
-
+numpy's float16 evaluation of the reference's distance formula, the rounding edges and HalfGAEngine's refusals (the new C-ABI
+symbols in the header and the binding: tests/test_abi.py)."""
 import numpy as np
 import pytest
 import torch
@@ -13,9 +10,6 @@ from coevonet_amd.fcnetwork import FCNetworkHalf, LINEAR_KEYS
 from oracle import ref_port as rp
 from tests import ga16_checker as gk
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_INT = ("coevo_fc16_perturb_dist", "coevo_fc16_distance", "coevo_fc16_distance_finalize", "coevo_fc16_gather",
-           "coevo_ga16_promote")
 # largest gap, in fp16 ulps of the reference's value, between the contract's distance (fp64 sum of the squared fp16
 # differences, one rounding of the square root) and numpy's float16 np.linalg.norm (sequential fp32 dot rounded to half before
 # the square root) over the 272 pairs of distance_pairs(): measured with numpy 2.x on x86-64
@@ -112,23 +106,6 @@ def test_sharing_score_route_matches_the_reference_expression():
     want = np.sum(np.maximum(0, 1 - d / np.mean(d)))
     assert got.dtype == np.float32 and abs(float(got) - float(want)) <= 1e-5 * float(want)
     assert gk.rank_desc([1.0, 3.0, 3.0, 2.0]) == [2, 1, 3, 0]
-
-
-def test_header_declares_and_lib_binds_the_fp16_breeding_symbols():
-    text = open(os.path.join(REPO, "include", "coevo.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NEW_INT:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", text), f"{name} is not declared in include/coevo.h"
-        assert name in L.exported_symbols(), f"{name} is not bound in lib.py"
-    assert re.search(r"\bint64_t\s+coevo_fc16_perturb_blocks\s*\(", text)
-    assert "coevo_fc16_perturb_blocks" in L.exported_symbols()
-    # the fp32 entry points' argument lists, slab pointers untyped
-    assert L._SIGS["coevo_fc16_perturb_dist"] == L._SIGS["coevo_fc_perturb_dist"]
-    assert L._SIGS["coevo_fc16_distance_finalize"] == L._SIGS["coevo_fc_distance_finalize"]
-    assert L._SIGS["coevo_fc16_gather"] == L._SIGS["coevo_fc_gather"]
-    assert L._SIGS["coevo_ga16_promote"] == L._SIGS["coevo_ga_promote"]
-    assert re.search(r"typedef struct coevo_ga16_promote_role\s*\{\s*void \*pop, \*hof, \*elite;", text)
-    assert re.search(r"#define COEVO_VERSION 103\b", text)
 
 
 def test_half_engine_refuses_out_of_scope_arguments_before_the_library_is_loaded(monkeypatch):

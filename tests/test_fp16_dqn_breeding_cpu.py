@@ -1,9 +1,6 @@
-"""Float16 DeepQN breeding without a GPU: the new C-ABI symbols in the header and the binding, the refusals of the entry points
-and of HalfDQNGAEngine, the CPU restatement (tests/dqn_ga16_checker.py) against torch's half update and against numpy's float16
-evaluation of the reference's distance formula, and the one named deviation from it."""
-import os
-import re
-
+"""Float16 DeepQN breeding without a GPU: the refusals of the entry points and of HalfDQNGAEngine, the CPU restatement
+(tests/dqn_ga16_checker.py) against torch's half update and against numpy's float16 evaluation of the reference's distance
+formula, and the one named deviation from it.  (The new C-ABI symbols in the header and the binding: tests/test_abi.py.)"""
 import numpy as np
 import pytest
 import torch
@@ -12,35 +9,13 @@ from coevonet_amd import lib as L
 from oracle import ref_port as rp
 from tests import dqn_ga16_checker as dk
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = ((4, 6), (3, 18), (6, 6))
 # largest gap, in fp16 ulps of the reference's value, between the contract's distance (fp64 sum of the squared fp16 differences,
 # one rounding of the square root) and numpy's float16 np.linalg.norm over the 15 pairs of distance_pairs(): measured with
 # numpy 2.x on x86-64
 MEASURED_MAX_ULPS = 1.0
-ERR_ARG = -1
-SKIP_BN, ANTITHETIC, FROM_ORDER, COPY = 1, 2, 4, 8
-
-
-def test_header_declares_and_lib_binds_the_fp16_dqn_breeding_symbols():
-    import coevonet_amd
-    text = open(os.path.join(REPO, "include", "coevo.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in ("coevo_dqn16_perturb_dist", "coevo_dqn16_distance"):
-        assert re.search(r"\bint\s+" + name + r"\s*\(", text), f"{name} is not declared in include/coevo.h"
-        assert name in L.exported_symbols(), f"{name} is not bound in lib.py"
-    assert re.search(r"\bint64_t\s+coevo_dqn16_perturb_blocks\s*\(", text)
-    assert "coevo_dqn16_perturb_blocks" in L.exported_symbols()
-    # coevo_dqn_perturb's argument list without E, slab pointers untyped
-    want = list(L._SIGS["coevo_dqn_perturb"][1])
-    del want[12]
-    assert L._SIGS["coevo_dqn16_perturb_dist"] == (L._SIGS["coevo_dqn_perturb"][0], want)
-    assert re.search(r"#define COEVO_VERSION 103\b", text)
-    from coevonet_amd.dqn_ga_half import HalfDQNGAEngine, HalfSynthRollout
-    assert coevonet_amd.HalfDQNGAEngine is HalfDQNGAEngine and coevonet_amd.HalfSynthRollout is HalfSynthRollout
-    assert {"HalfDQNGAEngine", "HalfSynthRollout"} <= set(coevonet_amd.__all__)
-    from coevonet_amd.build import SOURCES
-    assert "dqn16_offspring.hip" in SOURCES
+ERR_ARG = L.K["COEVO_ERR_ARG"]
+SKIP_BN, ANTITHETIC, FROM_ORDER, COPY = (L.K["COEVO_DQP_" + n] for n in ("SKIP_BN", "ANTITHETIC", "FROM_ORDER", "COPY"))
 
 
 def test_perturb_blocks_is_one_block_per_256_pieces():
@@ -88,7 +63,13 @@ def test_distance_refuses_and_empty_calls_are_ok():
 
 
 def test_half_dqn_engine_refuses_out_of_scope_arguments_before_the_library_is_loaded(monkeypatch):
-    from coevonet_amd.dqn_ga_half import HalfDQNGAEngine
+    import coevonet_amd
+    from coevonet_amd.build import SOURCES
+    from coevonet_amd.dqn_ga_half import HalfDQNGAEngine, HalfSynthRollout
+
+    assert coevonet_amd.HalfDQNGAEngine is HalfDQNGAEngine and coevonet_amd.HalfSynthRollout is HalfSynthRollout
+    assert {"HalfDQNGAEngine", "HalfSynthRollout"} <= set(coevonet_amd.__all__)
+    assert "dqn16_offspring.hip" in SOURCES
 
     def no_load():
         raise AssertionError("the library was loaded")

@@ -1,7 +1,7 @@
 """float16 DeepQN without a GPU: DeepQNHalf's initialisation, dtypes, accessors, checkpoints and mutation against the
 reference's float16 fixture (tests/golden/deepqn_forward_f16.json) and torch, the C checker (tests/dqn16_checker.py) against
-the reference's logits and on its edges, and the symbols of the float16 DeepQN ABI."""
-import ctypes
+the reference's logits and on its edges, and the float16 slab and workspace sizes (the symbols of the float16 DeepQN ABI:
+tests/test_abi.py)."""
 import hashlib
 
 import numpy as np
@@ -20,8 +20,6 @@ from tests.util import DQN_FRAME_KINDS, Bag, dqn_golden_frames, load_golden, sha
 # test_checker_vs_reference_fixture), and the bound the test asserts: that maximum plus one ulp
 MEASURED_ULPS = 4.25
 BOUND_ULPS = MEASURED_ULPS + 1.0
-DQN16_SYMBOLS = ["coevo_dqn16_slab_stride", "coevo_dqn16_pack", "coevo_dqn16_unpack", "coevo_dqn16_workspace_bytes",
-                 "coevo_dqn16_forward_argmax"]
 
 
 def fixture_net(c, mutated=True):
@@ -301,17 +299,10 @@ def test_checker_exact_tie_takes_the_first_index():
     assert st == 0 and lg[2] == lg[4] == 0.5 and a == 2
 
 
-def test_symbols_declared_exported_and_bound():
-    import os
-    import re
+def test_dqn16_slab_stride_and_workspace_sizes():
+    """(the entry points in the header, the library and the binding: tests/test_abi.py)"""
     from coevonet_amd.build import build
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(repo, "include", "coevo.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(coevo_[a-z0-9_]+)\s*\(", text))
     build()
-    dll = ctypes.CDLL(L.LIB_PATH)
-    for s in DQN16_SYMBOLS:
-        assert s in declared and hasattr(dll, s) and s in L.exported_symbols(), s
     lib = L.load()
     assert lib.coevo_version() == 103
     # the slab: a multiple of 4 words, about 0.52 of the fp32 slab; bad shapes are argument errors

@@ -1,11 +1,10 @@
 """Float16 Co-ES over DeepQN without a GPU: the CPU restatement (tests/dqn_es16_checker.py) against numpy's own half arithmetic
 for what the reference executes - np.dot(noises16.T, fit16), scale * dot, base16 += upd -, which entries move, the stored noise
-against the perturbed net of an all-zero parent, the new C-ABI symbols in the library, the header and the binding, and
-HalfDQNESEngine's export and refusals."""
+against the perturbed net of an all-zero parent, the new kernels and partial sizes in the library, and HalfDQNESEngine's export
+and refusals.  (The new C-ABI symbols in the library, the header and the binding: tests/test_abi.py.)"""
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,7 +16,6 @@ from tests import dqn_ga16_checker as dk
 from tests import es16_checker as ek
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_ABI = ("coevo_dqn_es16_partial_floats", "coevo_dqn_es16_partial", "coevo_dqn_es16_apply")
 NEW_KERNELS = ("dqn16_es_partial_kernel", "dqn16_es_apply_kernel")
 # largest gap, in fp16 ulps of numpy's value, between dot16 with the canonical ES_CHUNKS = 8 chunk sums and numpy's sequential
 # half np.dot over the inputs of half_inputs() ((C, n) = (3, 6), 8 and 16 individuals, sigma 0.05): measured with numpy 2.x on
@@ -129,22 +127,17 @@ def test_noise_is_the_rounded_fp32_noise_of_the_perturbed_net():
         assert (tiny == 0).any() and (tiny != 0).any() and (np.abs(tiny) < 6.1e-5).all(), "subnormal and zero noise16"
 
 
-def test_library_header_and_binding_have_the_dqn_es16_symbols():
+def test_library_has_the_dqn_es16_kernels_and_partial_sizes():
+    """(the entry points in the header, the library and the binding: tests/test_abi.py)"""
     from coevonet_amd.build import SOURCES, build
     assert "dqn16_es.hip" in SOURCES
     build()
     dll = ctypes.CDLL(L.LIB_PATH)
     text = open(os.path.join(REPO, "include", "coevo.h")).read()
     assert "evolutionary_strategy.py:120-148" in text and "Atari/deepqn.py:158-172" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NEW_ABI:
-        assert hasattr(dll, name), f"{name} is not exported by libcoevo.so"
-        assert name in L.exported_symbols(), f"{name} is not bound in lib.py"
-        assert re.search(r"\b(int|int64_t)\s+" + name + r"\s*\(", text), f"{name} is not declared in include/coevo.h"
     blob = open(L.LIB_PATH, "rb").read()
     for kernel in NEW_KERNELS:
         assert kernel.encode() in blob, f"{kernel} is not in libcoevo.so"
-    assert re.search(r"#define COEVO_VERSION 103\b", text)
     dll.coevo_dqn_es16_partial_floats.restype = ctypes.c_int64
     dll.coevo_dqn16_slab_stride.restype = ctypes.c_int64
     for C, n in ((0, 6), (7, 6), (4, 0), (4, 33), (4 | L.DQN_FC1_TILED, 6), (4 | 0x1000, 6)):

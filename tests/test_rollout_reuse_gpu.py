@@ -19,7 +19,7 @@ from tests.util import Bag
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-FORM = {"tile32": 0, "lean16": 2, "small": 3}   # COEVO_CYCLE_FORM_* (include/coevo.h)
+FORM = {n: L.K["COEVO_CYCLE_FORM_" + n.upper()] for n in ("tile32", "lean16", "small")}
 
 
 class Setup:
