@@ -33,8 +33,8 @@ __host__ __device__ inline uint64_t pcg_output(u128 s)
     return (x >> r) | (x << ((64 - r) & 63));
 }
 
-// state after `delta` further steps of the 128-bit LCG (O(log delta))
-__host__ __device__ inline u128 pcg_advance(u128 state, u128 inc, uint64_t delta)
+// state after `delta` further steps of the 128-bit LCG (O(log delta)); delta is 128 bits wide like numpy's advance()
+__host__ __device__ inline u128 pcg_advance(u128 state, u128 inc, u128 delta)
 {
     u128 acc_mult = 1, acc_plus = 0, cur_mult = pcg_mult(), cur_plus = inc;
     while (delta > 0) {
@@ -51,16 +51,20 @@ __host__ __device__ inline u128 pcg_advance(u128 state, u128 inc, uint64_t delta
 
 // numpy Generator semantics of one PettingZoo reset: choice(2) = one buffered 32-bit draw (the low half of a
 // 64-bit output for even ordinals, the kept high half for odd ones; Lemire range 2 => top bit), then ten
-// uniform(-1,1) doubles.  Two resets consume 21 raw 64-bit outputs.
+// uniform(-1,1) doubles.  Two resets consume 21 raw 64-bit outputs, so reset `ordinal` stands (ordinal >> 1) * 21 outputs
+// into the stream: a product that leaves 64 bits from ordinal 1756832768924719202 on, hence formed in 128 bits.
 __host__ __device__ __forceinline__ void mpe_reset_game(double *st, int n, int g, coevo_pcg64 rng, uint64_t ordinal);
 
+// unsigned_first (coevo_mpe_reset): first_ordinal carries the entry point's uint64_t word - no generation, no clamp
 __global__ void mpe_reset_kernel(double *st, int n, int game_first, int count, coevo_pcg64 rng,
-                                 int64_t first_ordinal, const int32_t *gen_dev, int64_t ordinals_per_gen)
+                                 int64_t first_ordinal, const int32_t *gen_dev, int64_t ordinals_per_gen, int unsigned_first)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
+    // an int64 sum: exact while first_ordinal + gen * ordinals_per_gen stays inside int64, i.e. for |first_ordinal| < 2^62
+    // whenever gen * ordinals_per_gen < 2^62 (2^31 generations of 2^31 games); beyond that it is the caller's overflow
     int64_t first = first_ordinal + (gen_dev ? (int64_t)(*gen_dev) * ordinals_per_gen : 0);
-    if (first < 0) first = 0;  // a batch that is disabled in this generation (e.g. no previous evaluation yet)
+    if (first < 0 && !unsigned_first) first = 0;  // a batch that is disabled in this generation (e.g. no previous evaluation yet)
     mpe_reset_game(st, n, game_first + i, rng, (uint64_t)first + (uint64_t)i);
 }
 
@@ -89,7 +93,7 @@ __host__ __device__ __forceinline__ void mpe_reset_game(double *st, int n, int g
 {
     const u128 inc = ((u128)rng.pcg_inc_hi << 64) | rng.pcg_inc_lo;
     u128 s = ((u128)rng.pcg_state_hi << 64) | rng.pcg_state_lo;
-    s = pcg_advance(s, inc, (ordinal >> 1) * 21);
+    s = pcg_advance(s, inc, (u128)(ordinal >> 1) * 21);
     s = s * pcg_mult() + inc;
     const uint64_t c = pcg_output(s);
     const uint32_t half = (ordinal & 1) ? (uint32_t)(c >> 32) : (uint32_t)c;
@@ -254,7 +258,7 @@ extern "C" int coevo_mpe_reset_gen(double *state, int n_games, int game_first, i
     if (!state || n_games <= 0 || game_first < 0 || count < 0 || game_first + count > n_games) return COEVO_ERR_ARG;
     if (count == 0) return COEVO_OK;
     hipLaunchKernelGGL(coevo::mpe_reset_kernel, dim3((count + 127) / 128), dim3(128), 0, (hipStream_t)stream,
-                       state, n_games, game_first, count, rng, first_ordinal, gen_dev, ordinals_per_gen);
+                       state, n_games, game_first, count, rng, first_ordinal, gen_dev, ordinals_per_gen, 0);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }
@@ -310,7 +314,7 @@ extern "C" int coevo_mpe_reset(double *state, int n_games, int game_first, int c
     if (count == 0) return COEVO_OK;
     hipLaunchKernelGGL(coevo::mpe_reset_kernel, dim3((count + 127) / 128), dim3(128), 0, (hipStream_t)stream,
                        state, n_games, game_first, count, rng, (int64_t)first_ordinal, (const int32_t *)nullptr,
-                       (int64_t)0);
+                       (int64_t)0, 1);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }
@@ -359,7 +363,7 @@ static void mpe_reset_list_host(double *st, int n, coevo_pcg64 rng, const int64_
                 c = pcg_output(s);
             }                       // (odd: the pair's word is `c`, the stream stands behind the even game's ten doubles)
         } else {
-            s = pcg_advance(s0, inc, (ordinal >> 1) * 21);
+            s = pcg_advance(s0, inc, (u128)(ordinal >> 1) * 21);
             s = s * pcg_mult() + inc;
             c = pcg_output(s);
             if (ordinal & 1) s = pcg_advance(s, inc, 10);

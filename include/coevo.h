@@ -147,7 +147,8 @@ typedef struct {
 
 /* state = [COEVO_MPE_STATE_DOUBLES][n_games] fp64.  Games game_first .. game_first+count-1 take reset ordinals
  * first_ordinal .. of the single seeded stream (quirk Q6; ordinal 0 is the reset inside initialize_env,
- * utils/game_logic_functions.py:54); each game jumps straight to its ordinal, so shards need no common prefix. */
+ * utils/game_logic_functions.py:54); each game jumps straight to its ordinal, so shards need no common prefix.  Any
+ * uint64_t ordinal is one (the stream position (ordinal >> 1) * 21 is formed in 128 bits, as numpy's advance() takes it). */
 int coevo_mpe_reset(double *state, int n_games, int game_first, int count, coevo_pcg64 rng, uint64_t first_ordinal,
                     void *stream);
 /* up to COEVO_MAX_JOBS (game range, first ordinal) segments in one launch (a cohort's three role phases + the evaluation

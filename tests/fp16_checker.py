@@ -73,6 +73,46 @@ def play_game(stream, net_a0, net_a1, net_adv, limit=None, max_cycles=25, ordina
             "margins": margins[:steps].tolist(), "status": st.value, "ordinal": o}
 
 
+def play_game_steps(stream, net_a0, net_a1, net_adv, limit=None, max_cycles=25, ordinal=None, poke=None):
+    """fc16_play_game's loop in Python on the same pieces (oracle_mpe_reset / _observe / _world_step, fc16_forward): the twin
+    of rp.play_game_steps, for tests that edit a game's state after the reset with poke(MpeState).  With no poke it returns
+    play_game's rewards, steps, actions and status bit for bit."""
+    o = stream.next_ordinal() if ordinal is None else ordinal
+    O, L = rp.lib(), lib()
+    nets = [np.ascontiguousarray(n, dtype=np.float32) for n in (net_adv, net_a0, net_a1)]
+    s = rp.MpeState()
+    O.oracle_mpe_reset(*stream.st, o, C.byref(s))
+    if poke is not None:
+        poke(s)
+    cum, rew, acc, act = [0.0] * 3, [0.0] * 3, [0.0] * 3, (C.c_int * 3)(0, 0, 0)
+    sel = world_steps = timesteps = 0
+    trunc, actions = False, []
+    obs, logits, st = np.zeros(10, dtype=np.float32), np.zeros(NACT, dtype=np.float32), C.c_int(0)
+    rg, ra = C.c_double(0), C.c_double(0)
+    while True:
+        agent = sel
+        O.oracle_mpe_observe(C.byref(s), agent, _fp(obs))
+        a = L.fc16_forward(_fp(nets[agent]), 8 if agent == 0 else 10, _fp(obs), _fp(logits), C.byref(st))
+        a = max(a, 0)
+        actions.append(int(a))
+        sel = (agent + 1) % 3
+        act[agent] = int(a)
+        if sel == 0:
+            O.oracle_mpe_world_step(C.byref(s), act, C.byref(rg), C.byref(ra))
+            rew = [ra.value, rg.value, rg.value]
+            world_steps += 1
+            trunc = world_steps >= max_cycles
+        else:
+            rew = [0.0, 0.0, 0.0]
+        cum[agent] = 0.0
+        cum = [c + r for c, r in zip(cum, rew)]
+        acc[agent] += cum[sel]
+        timesteps += 1
+        if (limit is not None and timesteps >= limit) or trunc:
+            break
+    return {"rewards": [acc[1], acc[2], acc[0]], "steps": timesteps, "actions": actions, "status": st.value, "ordinal": o}
+
+
 def ulp16(v):
     """the fp16 spacing at |v|"""
     return float(np.spacing(np.abs(np.float16(v))))

@@ -339,12 +339,18 @@ def oracle_games(s, first, limits, n_cycles, poke=None, choose=None, affected=No
 
 
 def run(s, form, first, limits, poke_game=None):
-    """one rollout of every game on the Setup's DeviceRollout -> (rewards, status word, last action words [n_games][3])"""
+    """one rollout of every game on the Setup's DeviceRollout -> (rewards, status word, last action words [n_games][3]).
+    poke_game: a game whose adversary's x becomes inf after the reset, or {game: [COEVO_MPE_STATE_DOUBLES] state column}"""
     ro, p, n = s.ro, s.plan, s.n_cycles
     ro.status.zero_()
     ro.set_limits(limits)
     ro.reset(0, p.n_games, first)
-    if poke_game is not None:
+    if isinstance(poke_game, dict):
+        games = sorted(poke_game)
+        cols = np.stack([np.asarray(poke_game[g], dtype=np.float64) for g in games], axis=1)
+        assert cols.shape == (L.MPE_STATE_DOUBLES, len(games))
+        ro.state.index_copy_(1, torch.tensor(games, dtype=torch.int64, device=DEV), torch.from_numpy(cols).to(DEV))
+    elif poke_game is not None:
         ro.state[0, poke_game] = float("inf")   # x of the adversary of that game: a buffer the test owns
     if form == "plain":
         for c in range(n):
