@@ -2030,14 +2030,24 @@ extern "C" int coevo_debug_read_phase_stamps(unsigned long long *host_out, int n
 }
 #endif
 
+static bool rows_outside(int max_rows, int limit) { return max_rows < 1 || max_rows > limit; }
+
+// what every fused env-step launch refuses: a missing buffer, or a cycle that would read the buffer it writes
+static bool bad_fused_cycle(const double *state_prev, double *state_next, int n_games, const int32_t *row_game,
+                            const int32_t *row_slot, const int32_t *act_prev, int32_t *act_cur, int cycle, int32_t *status)
+{
+    return !state_prev || !state_next || !row_game || !row_slot || !act_prev || !act_cur || !status || n_games <= 0 ||
+           cycle < 0 || state_prev == state_next || act_prev == act_cur;
+}
+
 extern "C" int coevo_fc_forward_argmax(const float *slab, const coevo_fc_task *tasks, int n_tasks,
                                        int max_rows_per_task, const float *obs, int32_t *actions, float *logits,
                                        int32_t *status, void *stream)
 {
     if (!slab || !tasks || !obs || !actions || !status || n_tasks < 0) return COEVO_ERR_ARG;
-    if (max_rows_per_task < 1 || max_rows_per_task > COEVO_FC_MAX_ROWS) return COEVO_ERR_ARG;
-    coevo::FcArgs a{slab, tasks, obs, nullptr, nullptr, nullptr, 0, actions, logits, status, nullptr,
-                    nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0};
+    if (rows_outside(max_rows_per_task, COEVO_FC_MAX_ROWS)) return COEVO_ERR_ARG;
+    coevo::FcArgs a{};   // (here and below: fields by name, every field a launch mode does not name stays zero)
+    a.slab = slab; a.tasks = tasks; a.obs = obs; a.actions = actions; a.logits = logits; a.status = status;
     return coevo::launch_fc<coevo::MODE_OBS>(a, n_tasks, max_rows_per_task, (hipStream_t)stream);
 }
 
@@ -2062,9 +2072,10 @@ extern "C" int coevo_mpe_policy_cycle_stamped(const float *slab, const coevo_fc_
 {
     if (!slab || !tasks || !state || !row_game || !row_slot || !actions || !status) return COEVO_ERR_ARG;
     if (n_tasks < 0 || n_games <= 0) return COEVO_ERR_ARG;
-    if (max_rows_per_task < 1 || max_rows_per_task > COEVO_FC_MAX_ROWS) return COEVO_ERR_ARG;
-    coevo::FcArgs a{slab, tasks, nullptr, state, row_game, row_slot, n_games, actions, nullptr, status,
-                    reinterpret_cast<unsigned long long *>(stamps), nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0};
+    if (rows_outside(max_rows_per_task, COEVO_FC_MAX_ROWS)) return COEVO_ERR_ARG;
+    coevo::FcArgs a{};
+    a.slab = slab; a.tasks = tasks; a.state = state; a.row_game = row_game; a.row_slot = row_slot; a.n_games = n_games;
+    a.actions = actions; a.status = status; a.stamps = reinterpret_cast<unsigned long long *>(stamps);
     return coevo::launch_fc<coevo::MODE_STATE>(a, n_tasks, max_rows_per_task, (hipStream_t)stream);
 }
 
@@ -2074,14 +2085,13 @@ extern "C" int coevo_mpe_policy_cycle_fused(const float *slab, const coevo_fc_ta
                                             const int32_t *act_prev, int32_t *act_cur, const int32_t *game_limit,
                                             int cycle, int pos_first, int32_t *status, uint64_t *stamps, void *stream)
 {
-    if (!slab || !tasks || !state_prev || !state_next || !row_game || !row_slot || !act_prev || !act_cur || !status)
+    if (!slab || !tasks || n_tasks < 0 || rows_outside(max_rows_per_task, COEVO_FC_MAX_ROWS) ||
+        bad_fused_cycle(state_prev, state_next, n_games, row_game, row_slot, act_prev, act_cur, cycle, status))
         return COEVO_ERR_ARG;
-    if (n_tasks < 0 || n_games <= 0 || cycle < 0 || state_prev == state_next || act_prev == act_cur)
-        return COEVO_ERR_ARG;
-    if (max_rows_per_task < 1 || max_rows_per_task > COEVO_FC_MAX_ROWS) return COEVO_ERR_ARG;
-    coevo::FcArgs a{slab, tasks, nullptr, state_prev, row_game, row_slot, n_games, nullptr, nullptr, status,
-                    reinterpret_cast<unsigned long long *>(stamps), state_next, act_prev, act_cur, game_limit, cycle,
-                    pos_first, nullptr, 0, 0};
+    coevo::FcArgs a{};
+    a.slab = slab; a.tasks = tasks; a.state = state_prev; a.row_game = row_game; a.row_slot = row_slot; a.n_games = n_games;
+    a.status = status; a.stamps = reinterpret_cast<unsigned long long *>(stamps); a.state_next = state_next;
+    a.act_prev = act_prev; a.act_cur = act_cur; a.game_limit = game_limit; a.cycle = cycle; a.pos_first = pos_first;
     return coevo::launch_fc<coevo::MODE_FUSED>(a, n_tasks, max_rows_per_task, (hipStream_t)stream);
 }
 
@@ -2098,7 +2108,8 @@ extern "C" int coevo_mpe_cycle_kernel_form(int n_heavy, int n_light, int heavy_m
     // every task of <= 8 rows and no more workgroups in flight than CUs: the small-launch kernel (COEVO_SMALL_KERNEL=0: A/B).
     // (Two per CU share their SIMDs' vector ALU: a rank of 4 - 360 workgroups of <= 8 rows - 27.6-30.5 us per launch against
     // 21.8 for the lean kernel's 270 with 16-row matrix-core tiles; a rank of 8 - 231 - 16.4 against 21.0.)
-    static const bool small_ok = !(getenv("COEVO_SMALL_KERNEL") && getenv("COEVO_SMALL_KERNEL")[0] == '0');
+    static const char *const small_env = getenv("COEVO_SMALL_KERNEL");
+    static const bool small_ok = !(small_env && small_env[0] == '0');
     if (small_ok && heavy_max_rows >= 1 && heavy_max_rows <= 8 && 2 * wgs <= slots) return COEVO_CYCLE_FORM_SMALL;
     if (heavy_max_rows >= 1 && heavy_max_rows <= 16 && wgs <= 2 * slots) return COEVO_CYCLE_FORM_LEAN16;
     // If one net per streaming workgroup does not fit the slots in a single round, pair the nets: the second round would
@@ -2187,15 +2198,14 @@ extern "C" int coevo_mpe_policy_cycle_merged(const float *slab, const coevo_fc_t
                                              int32_t *status, uint64_t *stamps, int concurrent_launches,
                                              int heavy_max_rows, void *stream)
 {
-    if (!slab || !heavy_tasks || !light_tasks || !state_prev || !state_next || !row_game || !row_slot || !act_prev ||
-        !act_cur || !status)
+    if (!slab || !heavy_tasks || !light_tasks || n_heavy <= 0 || n_light <= 0 || rows_outside(light_max_rows, 8) ||
+        bad_fused_cycle(state_prev, state_next, n_games, row_game, row_slot, act_prev, act_cur, cycle, status))
         return COEVO_ERR_ARG;
-    if (n_heavy <= 0 || n_light <= 0 || n_games <= 0 || cycle < 0 || state_prev == state_next || act_prev == act_cur)
-        return COEVO_ERR_ARG;
-    if (light_max_rows < 1 || light_max_rows > 8) return COEVO_ERR_ARG;
-    coevo::FcArgs a{slab, heavy_tasks, nullptr, state_prev, row_game, row_slot, n_games, nullptr, nullptr, status,
-                    reinterpret_cast<unsigned long long *>(stamps), state_next, act_prev, act_cur, game_limit, cycle,
-                    pos_first, light_tasks, n_heavy, n_light};
+    coevo::FcArgs a{};
+    a.slab = slab; a.tasks = heavy_tasks; a.state = state_prev; a.row_game = row_game; a.row_slot = row_slot; a.n_games = n_games;
+    a.status = status; a.stamps = reinterpret_cast<unsigned long long *>(stamps); a.state_next = state_next;
+    a.act_prev = act_prev; a.act_cur = act_cur; a.game_limit = game_limit; a.cycle = cycle; a.pos_first = pos_first;
+    a.light_tasks = light_tasks; a.n_heavy = n_heavy; a.n_light = n_light;
     const int form = coevo_mpe_cycle_kernel_form(n_heavy, n_light, heavy_max_rows, light_max_rows, concurrent_launches);
     if (form < 0) return form;
     hipStream_t s = (hipStream_t)stream;
@@ -2232,13 +2242,13 @@ extern "C" int coevo_fc_forward_merged(const float *slab, const coevo_fc_task *h
                                        int32_t *actions, float *logits, int32_t *status, void *stream)
 {
     if (!slab || !heavy_tasks || !light_tasks || !obs || !actions || !status) return COEVO_ERR_ARG;
-    if (n_heavy <= 0 || n_light <= 0 || heavy_max_rows < 1 || heavy_max_rows > 16 || light_max_rows < 1 || light_max_rows > 8)
-        return COEVO_ERR_ARG;
+    if (n_heavy <= 0 || n_light <= 0 || rows_outside(heavy_max_rows, 16) || rows_outside(light_max_rows, 8)) return COEVO_ERR_ARG;
     const int cus = coevo::device_cu_count();
     if (cus <= 0) return COEVO_ERR_HIP;
     if (n_heavy + n_light > 4 * cus) return COEVO_ERR_ARG;
-    coevo::FcArgs a{slab, heavy_tasks, obs, nullptr, nullptr, nullptr, 0, actions, logits, status, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, 0, 0, light_tasks, n_heavy, n_light};
+    coevo::FcArgs a{};
+    a.slab = slab; a.tasks = heavy_tasks; a.obs = obs; a.actions = actions; a.logits = logits; a.status = status;
+    a.light_tasks = light_tasks; a.n_heavy = n_heavy; a.n_light = n_light;
     const dim3 grid(n_heavy + n_light), block(256);
     hipStream_t s = (hipStream_t)stream;
     coevo::dispatch_rows(light_max_rows, [&](auto R) {

@@ -6,6 +6,7 @@
 // own streams (cohort 0: the caller's).  With d->merged == 0 the older two-launch form is used instead: [side stream]
 // the shared-opponent launch || [main stream] the per-individual launch, joined by an event.  Nothing here synchronises
 // with the host; a single-cohort sequence can also be captured into a hipGraph by the caller.
+// coevo_mpe16_rollout plays an fp16 slab through the same driver (enqueue_rollout below) with its own per-cycle launcher.
 #include <cstdlib>
 #include <vector>
 
@@ -136,154 +137,204 @@ extern "C" int coevo_rollout_ctx_light_times(void *ctx, float *ms_out, int max_o
     return n;
 }
 
-extern "C" int coevo_mpe_rollout(const coevo_rollout_desc *d, void *ctx, int time_light, void *stream)
+// ---------------------------------------------------------------------------------------------------------------------
+// The rollout driver.  coevo_mpe_rollout and coevo_mpe16_rollout are enqueue_rollout() with their own per-cycle launcher;
+// everything a descriptor means apart from "launch cycle c of cohort k" is written here, once.
+
+static int cohort_count(const coevo_rollout_desc *d) { return d->n_cohorts > 1 ? d->n_cohorts : 1; }
+
+// The buffer-parity rule (coevo.h, coevo_rollout_desc): state buffer 0 (d->state) holds the reset state, cycle c derives its
+// state from the one cycle c-1 left and its owner rows write it to buffer c & 1 (d->state_alt is buffer 1) - except cycle 0,
+// which plays on the reset state and writes none; every cycle writes its actions to action buffer c & 1.
+// So the state AND the actions that cycle c left are in buffer buffer_after(c); c = n_cycles - 1 is what the closing step
+// reads (-1: no cycle ran, the reset state).
+static int buffer_after(int cycle) { return cycle <= 0 ? 0 : cycle & 1; }
+static double *state_buffer(const coevo_rollout_desc *d, int b) { return b ? d->state_alt : d->state; }
+static int32_t *action_buffer(const coevo_rollout_desc *d, int b)
+{
+    return d->actions_by_game ? d->actions_by_game + (size_t)b * 3 * (size_t)d->n_games : nullptr;   // null: unfused step
+}
+
+struct cycle_buffers {
+    const double *st_prev;
+    double *st_next;
+    const int32_t *act_prev;
+    int32_t *act_cur;
+};
+
+static cycle_buffers buffers_of_cycle(const coevo_rollout_desc *d, int cyc)
+{
+    // (cycle 0 never writes st_next: it only has to differ from st_prev)
+    return {state_buffer(d, buffer_after(cyc - 1)), state_buffer(d, cyc == 0 ? 1 : cyc & 1), action_buffer(d, (cyc + 1) & 1),
+            action_buffer(d, cyc & 1)};
+}
+
+// [n_cohorts][n_cycles][COEVO_STAMP_SLOTS][2]
+static uint64_t *stamps_of(const coevo_rollout_desc *d, int k, int cyc)
+{
+    return d->light_stamps ? d->light_stamps + 2 * COEVO_STAMP_SLOTS * ((size_t)k * d->n_cycles + cyc) : nullptr;
+}
+
+// [n_cohorts][coevo_mpe_persistent_sync_words(n_games)]
+static int32_t *sync_words_of(const coevo_rollout_desc *d, int k)
+{
+    return d->sync_words + (size_t)k * (size_t)coevo_mpe_persistent_sync_words(d->n_games);
+}
+
+// Every refusal of both entry points, in front of every launch.  fp16: the float16 entry has the fused env step only and no
+// persistent form.
+static int refuse(const coevo_rollout_desc *d, const coevo_rollout_ctx *c, bool fp16)
 {
     if (!d || !d->slab || !d->state || !d->row_game || !d->row_slot || !d->status) return COEVO_ERR_ARG;
-    if ((d->state_alt == nullptr) != (d->actions_by_game == nullptr)) return COEVO_ERR_ARG;
+    if (fp16 ? (!d->state_alt || !d->actions_by_game) : ((d->state_alt == nullptr) != (d->actions_by_game == nullptr)))
+        return COEVO_ERR_ARG;
     if (!d->state_alt && (!d->game_rows || !d->actions)) return COEVO_ERR_ARG;
     if (d->n_games <= 0 || d->n_cycles < 0 || d->n_heavy < 0 || d->n_light < 0) return COEVO_ERR_ARG;
     if ((d->n_heavy > 0 && !d->heavy) || (d->n_light > 0 && !d->light)) return COEVO_ERR_ARG;
-    auto *c = static_cast<coevo_rollout_ctx *>(ctx);
-    hipStream_t main_s = (hipStream_t)stream;
-    // HIP events cannot be read back from inside a captured graph (external event-record nodes are rejected by this
-    // runtime), so event timing is for eager enqueues only; graph replays use the kernels' own clock stamps instead
-    auto record_timing = [&](hipEvent_t e) { return hipEventRecord(e, main_s); };
-    if (d->light_stamps && d->n_cycles > 0 && !d->stamps_armed) {  // [cycle][2] = {UINT64_MAX, 0}, re-armed by every enqueue / replay
+    if (fp16 && d->sync_words) return COEVO_ERR_UNSUPPORTED;
+    const int K = cohort_count(d);
+    if (K == 1) return COEVO_OK;
+    if (!c || !d->state_alt || !d->heavy_begin || !d->light_begin || K > COEVO_MAX_COHORTS) return COEVO_ERR_ARG;
+    if (d->heavy_begin[0] != 0 || d->light_begin[0] != 0 || d->heavy_begin[K] != d->n_heavy || d->light_begin[K] != d->n_light)
+        return COEVO_ERR_ARG;
+    for (int k = 0; k < K; ++k)
+        if (d->heavy_begin[k + 1] < d->heavy_begin[k] || d->light_begin[k + 1] < d->light_begin[k]) return COEVO_ERR_ARG;
+    // the lanes must exist already: streams cannot be created while the caller is capturing a graph
+    return (int)c->lanes.size() < K - 1 ? COEVO_ERR_ARG : COEVO_OK;
+}
+
+// one cohort's share of the task tables and the stream its chain of cycles runs on
+struct cohort {
+    int k, K;
+    const coevo_fc_task *heavy;
+    int n_heavy;
+    const coevo_fc_task *light;
+    int n_light;
+    hipStream_t s;
+};
+
+// what a per-cycle launcher answers besides an error (< 0)
+enum { CYCLE_ENQUEUED = 0, COHORT_PLAYED = 1, ROLLOUT_CLOSED = 2 };
+
+// launch_cycle(cohort, cycle, its buffers, its stamps) enqueues ONE env-cycle of one cohort on cohort.s.  It may answer
+// COHORT_PLAYED (its launch plays every remaining cycle of the cohort) or ROLLOUT_CLOSED (and closed the books as well).
+// A template, not a function pointer: the pipelined trainers enqueue K x n_cycles launches per generation eagerly.
+template <class LaunchCycle>
+static int enqueue_rollout(const coevo_rollout_desc *d, coevo_rollout_ctx *c, hipStream_t main_s, bool fp16,
+                           LaunchCycle &&launch_cycle)
+{
+    const int bad = refuse(d, c, fp16);
+    if (bad) return bad;
+    const int K = cohort_count(d);
+    if (d->light_stamps && d->n_cycles > 0 && !d->stamps_armed) {  // {UINT64_MAX, 0}, re-armed by every enqueue / replay
         hipLaunchKernelGGL(stamps_init_kernel, dim3(1), dim3(256), 0, main_s, d->light_stamps,
-                           (d->n_cohorts > 1 ? d->n_cohorts : 1) * d->n_cycles * COEVO_STAMP_SLOTS);
+                           K * d->n_cycles * COEVO_STAMP_SLOTS);
         COEVO_HIP_CHECK(hipGetLastError());
     }
-    const bool fused = d->state_alt != nullptr && d->actions_by_game != nullptr;
-    static const bool persistent_ok = !(getenv("COEVO_PERSISTENT") && getenv("COEVO_PERSISTENT")[0] == '0');   // A/B
-    const size_t act_stride = 3 * (size_t)d->n_games;
-    const int K = d->n_cohorts > 1 ? d->n_cohorts : 1;
     if (K > 1) {
-        if (!c || !fused || !d->heavy_begin || !d->light_begin || K > COEVO_MAX_COHORTS) return COEVO_ERR_ARG;
-        if (d->heavy_begin[0] != 0 || d->light_begin[0] != 0 || d->heavy_begin[K] != d->n_heavy ||
-            d->light_begin[K] != d->n_light)
-            return COEVO_ERR_ARG;
-        for (int k = 0; k < K; ++k)
-            if (d->heavy_begin[k + 1] < d->heavy_begin[k] || d->light_begin[k + 1] < d->light_begin[k]) return COEVO_ERR_ARG;
-        // the lanes must exist already: streams cannot be created while the caller is capturing a graph
-        if ((int)c->lanes.size() < K - 1) return COEVO_ERR_ARG;
-        COEVO_HIP_CHECK(hipEventRecord(c->start, main_s));
         // One stream per cohort, forked from / joined to the caller's stream only.  (Under graph capture this runtime
-        // tolerates mutual waits between the origin stream and a forked stream - the K = 1 pair below - but two forked
-        // streams that wait on each other send hip::Stream::EndCapture into endless recursion.)  Inside a cohort the
-        // shared-opponent launch and the per-individual launch of a cycle therefore run back to back; the overlap of
-        // matrix-core work with weight streaming now comes from the other cohorts' launches.
+        // tolerates mutual waits between the origin stream and a forked stream - the two-launch pair of coevo_mpe_rollout -
+        // but two forked streams that wait on each other send hip::Stream::EndCapture into endless recursion.)  Inside a
+        // cohort the launches of a cycle therefore run back to back; the overlap of matrix-core work with weight
+        // streaming comes from the other cohorts' launches.
+        COEVO_HIP_CHECK(hipEventRecord(c->start, main_s));
         for (int k = 1; k < K; ++k) COEVO_HIP_CHECK(hipStreamWaitEvent(c->lanes[k - 1].s, c->start, 0));
     }
-    bool closed_in_launch = false;
-    // one cohort's chain of cycles: per cycle the shared-opponent launch on `hs` || the per-individual launch on `ls`
-    // (hs == ls: back to back)
-    auto chain = [&](int k, const coevo_fc_task *heavy, int n_heavy, const coevo_fc_task *light, int n_light,
-                     hipStream_t ls, hipStream_t hs, hipEvent_t fork, hipEvent_t join) -> int {
-        const bool two = c && hs != ls && n_heavy > 0 && n_light > 0;
-        // a cohort whose workgroups are all resident at once (coevo_mpe_persistent_fits): its n_cycles as ONE persistent launch
-        if (persistent_ok && fused && d->merged && d->sync_words && n_heavy + n_light > 0 && d->n_cycles > 0) {
-            const int conc = d->concurrent_hint > K ? d->concurrent_hint : K;
-            if (coevo_mpe_persistent_fits(n_heavy, n_light, d->heavy_max_rows, d->light_max_rows, conc) == 1) {
-                // one cohort = every game of the call: its launch closes the books too (no closing launch below)
-                const bool closes = K == 1 && d->rewards != nullptr;
-                closed_in_launch = closes;
-                return coevo_mpe_rollout_persistent(
-                    d->slab, heavy, n_heavy, light, n_light, d->light_max_rows, d->heavy_max_rows, d->state, d->state_alt,
-                    d->n_games, d->row_game, d->row_slot, d->actions_by_game, d->game_limit, d->n_cycles, d->pos_first, d->status,
-                    d->light_stamps ? d->light_stamps + 2 * COEVO_STAMP_SLOTS * ((size_t)k * d->n_cycles) : nullptr,
-                    d->sync_words + (size_t)k * (size_t)(4 + 6 * (size_t)d->n_games), conc, closes ? d->rewards : nullptr,
-                    closes ? d->pack : nullptr, d->sync_cleared, ls);
-            }
-        }
+    bool closed = false;
+    for (int k = 0; k < K; ++k) {   // enqueue order = cohort by cohort; the chains only meet again at the `done` events
+        const int hb = K > 1 ? d->heavy_begin[k] : 0, he = K > 1 ? d->heavy_begin[k + 1] : d->n_heavy;
+        const int lb = K > 1 ? d->light_begin[k] : 0, le = K > 1 ? d->light_begin[k + 1] : d->n_light;
+        const cohort co{k, K, d->heavy ? d->heavy + hb : nullptr, he - hb, d->light ? d->light + lb : nullptr, le - lb,
+                        k ? c->lanes[k - 1].s : main_s};
         for (int cyc = 0; cyc < d->n_cycles; ++cyc) {
-            int rc;
-            // fused env step: cycle c reads the state of cycle c-1 (buffer (c-1)&1; buffer 0 holds the reset state)
-            // and the actions of cycle c-1, derives its own state in registers, the owner rows write it to buffer c&1
-            const double *st_prev = (cyc == 0) ? d->state : (((cyc - 1) & 1) ? d->state_alt : d->state);
-            double *st_next = (cyc & 1) ? d->state_alt : d->state;
-            if (cyc == 0) st_next = d->state_alt;  // never written in cycle 0; only has to differ from st_prev
-            const int32_t *act_prev = fused ? d->actions_by_game + (size_t)((cyc + 1) & 1) * act_stride : nullptr;
-            int32_t *act_cur = fused ? d->actions_by_game + (size_t)(cyc & 1) * act_stride : nullptr;
-            auto policy = [&](const coevo_fc_task *tasks, int n_tasks, int max_rows, uint64_t *stamps, hipStream_t s) {
-                if (fused)
-                    return coevo_mpe_policy_cycle_fused(d->slab, tasks, n_tasks, max_rows, st_prev, st_next, d->n_games,
-                                                        d->row_game, d->row_slot, act_prev, act_cur, d->game_limit,
-                                                        cyc, d->pos_first, d->status, stamps, s);
-                return coevo_mpe_policy_cycle_stamped(d->slab, tasks, n_tasks, max_rows, d->state, d->n_games,
-                                                      d->row_game, d->row_slot, d->actions, d->status, stamps, s);
-            };
-            if (fused && d->merged && n_heavy > 0 && n_light > 0 && d->light_max_rows <= 8) {
-                rc = coevo_mpe_policy_cycle_merged(
-                    d->slab, heavy, n_heavy, light, n_light, d->light_max_rows, st_prev, st_next, d->n_games, d->row_game,
-                    d->row_slot, act_prev, act_cur, d->game_limit, cyc, d->pos_first, d->status,
-                    d->light_stamps ? d->light_stamps + 2 * COEVO_STAMP_SLOTS * ((size_t)k * d->n_cycles + cyc) : nullptr,
-                    d->concurrent_hint > K ? d->concurrent_hint : K, d->heavy_max_rows, ls);
-                if (rc) return rc;
-                continue;
-            }
-            hipStream_t heavy_s = two ? hs : ls;
-            if (two) {
-                COEVO_HIP_CHECK(hipEventRecord(fork, ls));
-                COEVO_HIP_CHECK(hipStreamWaitEvent(hs, fork, 0));
-            }
-            if (n_heavy > 0) {
-                rc = policy(heavy, n_heavy, d->heavy_max_rows, nullptr, heavy_s);
-                if (rc) return rc;
-                if (two) COEVO_HIP_CHECK(hipEventRecord(join, hs));
-            }
-            if (n_light > 0) {
-                const bool timed = K == 1 && time_light && c && (size_t)(2 * c->pairs_used + 1) < c->timing.size();
-                if (timed) COEVO_HIP_CHECK(record_timing(c->timing[2 * c->pairs_used]));
-                rc = policy(light, n_light, d->light_max_rows,
-                            d->light_stamps ? d->light_stamps + 2 * COEVO_STAMP_SLOTS * ((size_t)k * d->n_cycles + cyc)
-                                            : nullptr, ls);
-                if (rc) return rc;
-                if (timed) {
-                    COEVO_HIP_CHECK(record_timing(c->timing[2 * c->pairs_used + 1]));
-                    ++c->pairs_used;
-                }
-            }
-            if (two) COEVO_HIP_CHECK(hipStreamWaitEvent(ls, join, 0));
-            if (!fused) {
-                rc = coevo_mpe_step(d->state, d->n_games, d->game_rows, d->actions, cyc, d->game_limit, d->pos_first, ls);
-                if (rc) return rc;
-            }
+            const int rc = launch_cycle(co, cyc, buffers_of_cycle(d, cyc), stamps_of(d, k, cyc));
+            if (rc < 0) return rc;
+            closed |= rc == ROLLOUT_CLOSED;
+            if (rc != CYCLE_ENQUEUED) break;
         }
-        return COEVO_OK;
-    };
-    if (K == 1) {
-        const int rc = chain(0, d->heavy, d->n_heavy, d->light, d->n_light, main_s, c ? c->side : main_s,
-                             c ? c->fork : nullptr, c ? c->join : nullptr);
-        if (rc) return rc;
-    } else {
-        // enqueue order = cohort by cohort; the chains only meet again at the `done` events below
-        for (int k = 0; k < K; ++k) {
-            const int hb = d->heavy_begin[k], lb = d->light_begin[k];
-            hipStream_t ks = k ? c->lanes[k - 1].s : main_s;
-            const int rc = chain(k, d->heavy ? d->heavy + hb : nullptr, d->heavy_begin[k + 1] - hb,
-                                 d->light ? d->light + lb : nullptr, d->light_begin[k + 1] - lb, ks, ks, nullptr, nullptr);
+    }
+    for (int k = 1; k < K; ++k) {
+        COEVO_HIP_CHECK(hipEventRecord(c->lanes[k - 1].done, c->lanes[k - 1].s));
+        COEVO_HIP_CHECK(hipStreamWaitEvent(main_s, c->lanes[k - 1].done, 0));
+    }
+    // the closing step; without rewards the caller closes the rollout itself (coevo_mpe_final_step), e.g. after several
+    // per-cohort calls on different streams
+    if (!d->rewards || closed) return COEVO_OK;
+    if (!d->state_alt) return coevo_mpe_rewards(d->state, d->n_games, d->rewards, main_s);
+    const int last = d->n_cycles - 1;   // -1: no cycle ran, the books are the reset state's zeros
+    const double *st_last = state_buffer(d, buffer_after(last));
+    const int32_t *act_last = action_buffer(d, buffer_after(last));
+    if (d->pack)
+        return coevo_mpe_final_step_pack(st_last, d->n_games, act_last, last, d->game_limit, d->pos_first, d->rewards,
+                                         d->pack->out, d->pack->dist, d->pack->n_roles, d->pack->n_local, d->pack->hof,
+                                         d->pack->dist_pitch, d->pack->dist_first, main_s);
+    return coevo_mpe_final_step(st_last, d->n_games, act_last, last, d->game_limit, d->pos_first, d->rewards, main_s);
+}
+
+// HIP events cannot be read back from inside a captured graph (external event-record nodes are rejected by this runtime), so
+// the event bracket (coevo_timing_begin / _end) is for eager enqueues of a single-cohort rollout only; graph replays use the
+// kernels' own clock stamps instead
+static bool event_timed(const cohort &co, const coevo_rollout_ctx *c, int time_light) { return co.K == 1 && time_light && c; }
+
+extern "C" int coevo_mpe_rollout(const coevo_rollout_desc *d, void *ctx, int time_light, void *stream)
+{
+    auto *c = static_cast<coevo_rollout_ctx *>(ctx);
+    static const char *const persistent_env = getenv("COEVO_PERSISTENT");
+    static const bool persistent_ok = !(persistent_env && persistent_env[0] == '0');   // A/B
+    return enqueue_rollout(d, c, (hipStream_t)stream, false,
+                           [=](const cohort &co, int cyc, const cycle_buffers &b, uint64_t *stamps) -> int {
+        const bool fused = d->state_alt != nullptr;
+        const int conc = d->concurrent_hint > co.K ? d->concurrent_hint : co.K;
+        hipStream_t ls = co.s;
+        // a cohort whose workgroups are all resident at once (coevo_mpe_persistent_fits): its n_cycles as ONE persistent launch
+        if (cyc == 0 && persistent_ok && fused && d->merged && d->sync_words && co.n_heavy + co.n_light > 0 &&
+            coevo_mpe_persistent_fits(co.n_heavy, co.n_light, d->heavy_max_rows, d->light_max_rows, conc) == 1) {
+            // one cohort = every game of the call: its launch closes the books too
+            const bool closes = co.K == 1 && d->rewards != nullptr;
+            const int rc = coevo_mpe_rollout_persistent(
+                d->slab, co.heavy, co.n_heavy, co.light, co.n_light, d->light_max_rows, d->heavy_max_rows, d->state, d->state_alt,
+                d->n_games, d->row_game, d->row_slot, d->actions_by_game, d->game_limit, d->n_cycles, d->pos_first, d->status,
+                stamps, sync_words_of(d, co.k), conc, closes ? d->rewards : nullptr, closes ? d->pack : nullptr,
+                d->sync_cleared, ls);
+            return rc ? rc : closes ? ROLLOUT_CLOSED : COHORT_PLAYED;
+        }
+        if (fused && d->merged && co.n_heavy > 0 && co.n_light > 0 && d->light_max_rows <= 8)
+            return coevo_mpe_policy_cycle_merged(d->slab, co.heavy, co.n_heavy, co.light, co.n_light, d->light_max_rows, b.st_prev,
+                                                 b.st_next, d->n_games, d->row_game, d->row_slot, b.act_prev, b.act_cur,
+                                                 d->game_limit, cyc, d->pos_first, d->status, stamps, conc, d->heavy_max_rows, ls);
+        // the two-launch form: [side stream] the shared-opponent launch || [ls] the per-individual launch, joined by an event
+        // (a single cohort with a context only; otherwise back to back on ls)
+        const bool two = co.K == 1 && c && c->side != ls && co.n_heavy > 0 && co.n_light > 0;
+        hipStream_t hs = two ? c->side : ls;
+        auto policy = [&](const coevo_fc_task *tasks, int n_tasks, int max_rows, uint64_t *st, hipStream_t s) {
+            if (fused)
+                return coevo_mpe_policy_cycle_fused(d->slab, tasks, n_tasks, max_rows, b.st_prev, b.st_next, d->n_games,
+                                                    d->row_game, d->row_slot, b.act_prev, b.act_cur, d->game_limit, cyc,
+                                                    d->pos_first, d->status, st, s);
+            return coevo_mpe_policy_cycle_stamped(d->slab, tasks, n_tasks, max_rows, d->state, d->n_games, d->row_game,
+                                                  d->row_slot, d->actions, d->status, st, s);
+        };
+        int rc;
+        if (two) {
+            COEVO_HIP_CHECK(hipEventRecord(c->fork, ls));
+            COEVO_HIP_CHECK(hipStreamWaitEvent(hs, c->fork, 0));
+        }
+        if (co.n_heavy > 0) {
+            rc = policy(co.heavy, co.n_heavy, d->heavy_max_rows, nullptr, hs);
             if (rc) return rc;
+            if (two) COEVO_HIP_CHECK(hipEventRecord(c->join, hs));
         }
-        for (int k = 1; k < K; ++k) {
-            COEVO_HIP_CHECK(hipEventRecord(c->lanes[k - 1].done, c->lanes[k - 1].s));
-            COEVO_HIP_CHECK(hipStreamWaitEvent(main_s, c->lanes[k - 1].done, 0));
+        if (co.n_light > 0) {
+            const bool timed = event_timed(co, c, time_light);
+            if (timed && (rc = coevo_timing_begin(c, ls))) return rc;
+            rc = policy(co.light, co.n_light, d->light_max_rows, stamps, ls);
+            if (rc) return rc;
+            if (timed && (rc = coevo_timing_end(c, ls))) return rc;
         }
-    }
-    if (fused) {
-        if (!d->rewards) return COEVO_OK;  // the caller closes the rollout itself (coevo_mpe_final_step), e.g. after
-                                            // several per-cohort calls on different streams
-        if (closed_in_launch) return COEVO_OK;   // (the persistent launch did)
-        const int last = d->n_cycles - 1;  // -1: no cycle ran, the books are the reset state's zeros
-        const double *st_last = (last <= 0) ? d->state : ((last & 1) ? d->state_alt : d->state);
-        const int32_t *act_last = d->actions_by_game + (size_t)((last < 0 ? 0 : last) & 1) * act_stride;
-        if (d->pack)
-            return coevo_mpe_final_step_pack(st_last, d->n_games, act_last, last, d->game_limit, d->pos_first, d->rewards,
-                                             d->pack->out, d->pack->dist, d->pack->n_roles, d->pack->n_local, d->pack->hof,
-                                             d->pack->dist_pitch, d->pack->dist_first, main_s);
-        return coevo_mpe_final_step(st_last, d->n_games, act_last, last, d->game_limit, d->pos_first, d->rewards, main_s);
-    }
-    if (d->rewards) return coevo_mpe_rewards(d->state, d->n_games, d->rewards, main_s);
-    return COEVO_OK;
+        if (two) COEVO_HIP_CHECK(hipStreamWaitEvent(ls, c->join, 0));
+        if (!fused) return coevo_mpe_step(d->state, d->n_games, d->game_rows, d->actions, cyc, d->game_limit, d->pos_first, ls);
+        return CYCLE_ENQUEUED;
+    });
 }
 
 namespace coevo {
@@ -297,68 +348,18 @@ int launch_fc16_cycle(const void *slab, const coevo_fc_task *heavy, int n_heavy,
 // coevo_mpe_rollout for an fp16 slab: the fused env step only, one launch per env-cycle and cohort, no persistent form
 extern "C" int coevo_mpe16_rollout(const coevo_rollout_desc *d, void *ctx, int time_light, void *stream)
 {
-    if (!d || !d->slab || !d->state || !d->row_game || !d->row_slot || !d->status) return COEVO_ERR_ARG;
-    if (!d->state_alt || !d->actions_by_game) return COEVO_ERR_ARG;
-    if (d->n_games <= 0 || d->n_cycles < 0 || d->n_heavy < 0 || d->n_light < 0) return COEVO_ERR_ARG;
-    if ((d->n_heavy > 0 && !d->heavy) || (d->n_light > 0 && !d->light)) return COEVO_ERR_ARG;
-    if (d->sync_words) return COEVO_ERR_UNSUPPORTED;
     auto *c = static_cast<coevo_rollout_ctx *>(ctx);
-    hipStream_t main_s = (hipStream_t)stream;
-    const int K = d->n_cohorts > 1 ? d->n_cohorts : 1;
-    if (d->light_stamps && d->n_cycles > 0 && !d->stamps_armed) {
-        hipLaunchKernelGGL(stamps_init_kernel, dim3(1), dim3(256), 0, main_s, d->light_stamps,
-                           K * d->n_cycles * COEVO_STAMP_SLOTS);
-        COEVO_HIP_CHECK(hipGetLastError());
-    }
-    if (K > 1) {
-        if (!c || !d->heavy_begin || !d->light_begin || K > COEVO_MAX_COHORTS) return COEVO_ERR_ARG;
-        if (d->heavy_begin[0] != 0 || d->light_begin[0] != 0 || d->heavy_begin[K] != d->n_heavy ||
-            d->light_begin[K] != d->n_light)
-            return COEVO_ERR_ARG;
-        for (int k = 0; k < K; ++k)
-            if (d->heavy_begin[k + 1] < d->heavy_begin[k] || d->light_begin[k + 1] < d->light_begin[k]) return COEVO_ERR_ARG;
-        if ((int)c->lanes.size() < K - 1) return COEVO_ERR_ARG;   // streams cannot be created while a graph is captured
-        // one stream per cohort, forked from / joined to the caller's stream only (see coevo_mpe_rollout)
-        COEVO_HIP_CHECK(hipEventRecord(c->start, main_s));
-        for (int k = 1; k < K; ++k) COEVO_HIP_CHECK(hipStreamWaitEvent(c->lanes[k - 1].s, c->start, 0));
-    }
-    const size_t act_stride = 3 * (size_t)d->n_games;
-    for (int k = 0; k < K; ++k) {   // enqueue order = cohort by cohort; the chains only meet again at the `done` events
-        const int hb = K > 1 ? d->heavy_begin[k] : 0, he = K > 1 ? d->heavy_begin[k + 1] : d->n_heavy;
-        const int lb = K > 1 ? d->light_begin[k] : 0, le = K > 1 ? d->light_begin[k + 1] : d->n_light;
-        hipStream_t ks = k ? c->lanes[k - 1].s : main_s;
-        for (int cyc = 0; cyc < d->n_cycles; ++cyc) {
-            // cycle c reads the state of cycle c-1 (buffer (c-1)&1; buffer 0 holds the reset state) and its actions
-            const double *st_prev = (cyc == 0) ? d->state : (((cyc - 1) & 1) ? d->state_alt : d->state);
-            double *st_next = (cyc & 1) ? d->state_alt : d->state;
-            if (cyc == 0) st_next = d->state_alt;   // never written in cycle 0; only has to differ from st_prev
-            const bool timed = K == 1 && time_light && c && (size_t)(2 * c->pairs_used + 1) < c->timing.size();
-            if (timed) COEVO_HIP_CHECK(hipEventRecord(c->timing[2 * c->pairs_used], main_s));
-            const int rc = coevo::launch_fc16_cycle(
-                d->slab, d->heavy ? d->heavy + hb : nullptr, he - hb, d->light ? d->light + lb : nullptr, le - lb, st_prev,
-                st_next, d->n_games, d->row_game, d->row_slot, d->actions_by_game + (size_t)((cyc + 1) & 1) * act_stride,
-                d->actions_by_game + (size_t)(cyc & 1) * act_stride, d->game_limit, cyc, d->pos_first, d->status,
-                d->light_stamps ? d->light_stamps + 2 * COEVO_STAMP_SLOTS * ((size_t)k * d->n_cycles + cyc) : nullptr, ks);
-            if (rc) return rc;
-            if (timed) {
-                COEVO_HIP_CHECK(hipEventRecord(c->timing[2 * c->pairs_used + 1], main_s));
-                ++c->pairs_used;
-            }
-        }
-    }
-    for (int k = 1; k < K; ++k) {
-        COEVO_HIP_CHECK(hipEventRecord(c->lanes[k - 1].done, c->lanes[k - 1].s));
-        COEVO_HIP_CHECK(hipStreamWaitEvent(main_s, c->lanes[k - 1].done, 0));
-    }
-    if (!d->rewards) return COEVO_OK;   // the caller closes the rollout itself (coevo_mpe_final_step)
-    const int last = d->n_cycles - 1;   // -1: no cycle ran, the books are the reset state's zeros
-    const double *st_last = (last <= 0) ? d->state : ((last & 1) ? d->state_alt : d->state);
-    const int32_t *act_last = d->actions_by_game + (size_t)((last < 0 ? 0 : last) & 1) * act_stride;
-    if (d->pack)
-        return coevo_mpe_final_step_pack(st_last, d->n_games, act_last, last, d->game_limit, d->pos_first, d->rewards,
-                                         d->pack->out, d->pack->dist, d->pack->n_roles, d->pack->n_local, d->pack->hof,
-                                         d->pack->dist_pitch, d->pack->dist_first, main_s);
-    return coevo_mpe_final_step(st_last, d->n_games, act_last, last, d->game_limit, d->pos_first, d->rewards, main_s);
+    return enqueue_rollout(d, c, (hipStream_t)stream, true,
+                           [=](const cohort &co, int cyc, const cycle_buffers &b, uint64_t *stamps) -> int {
+        const bool timed = event_timed(co, c, time_light);
+        int rc;
+        if (timed && (rc = coevo_timing_begin(c, co.s))) return rc;
+        rc = coevo::launch_fc16_cycle(d->slab, co.heavy, co.n_heavy, co.light, co.n_light, b.st_prev, b.st_next, d->n_games,
+                                      d->row_game, d->row_slot, b.act_prev, b.act_cur, d->game_limit, cyc, d->pos_first,
+                                      d->status, stamps, co.s);
+        if (rc) return rc;
+        return timed ? coevo_timing_end(c, co.s) : CYCLE_ENQUEUED;
+    });
 }
 
 COEVO_DEFINE_TU_FLAGS(rollout_api)

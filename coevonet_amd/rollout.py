@@ -125,6 +125,7 @@ class RolloutPlan:
         self.heavy_max = int(max([t[2] for t in tasks["heavy"]], default=0))
         self.light_max = int(max([t[2] for t in tasks["light"]], default=0))
         self.device = device
+        self.heavy = self.light = None
         if device is not None:
             self.row_game = torch.from_numpy(self.row_game_np).to(device)
             self.row_slot = torch.from_numpy(self.row_slot_np).to(device)
@@ -184,6 +185,17 @@ class RolloutPlan:
                     out.append(buckets[x][q])
         return out
 
+    def cohort_tasks(self, k):
+        """cohort k's share of the task tables: (heavy pointer, n_heavy, heavy max rows, light pointer, n_light, light max
+        rows).  A pointer is the device address of the cohort's first task, None without one (or without device tables);
+        max rows are the cohort's own (<= heavy_max / light_max of the whole plan)."""
+        out = ()
+        for tasks, tnp, begin in ((self.heavy, self.heavy_np, self.heavy_begin_np), (self.light, self.light_np, self.light_begin_np)):
+            b, e = int(begin[k]), int(begin[k + 1])
+            ptr = tasks.data_ptr() + b * L.TASK_DTYPE.itemsize if (tasks is not None and e > b) else None
+            out += (ptr, e - b, int(max(tnp["n_rows"][b:e], default=0)))
+        return out
+
     def distinct_weight_bytes_per_cycle(self):
         """algorithmic bytes of one env-cycle: every distinct weight set that acts, once."""
         seen = {}
@@ -199,12 +211,21 @@ def effective_steps(limit, max_cycles):
     return cap if limit is None else min(int(limit), cap)
 
 
+def last_buffer(n_cycles):
+    """which of the two state buffers, and of the two action buffers, holds what the last of n_cycles cycles left for the
+    closing step.  The rule of coevo_rollout_desc (include/coevo.h): buffer 0 holds the reset state, cycle c writes its state
+    to buffer c & 1 - cycle 0 writes none - and its actions to action buffer c & 1 (no cycle: the reset state)"""
+    last = int(n_cycles) - 1
+    return last & 1 if last > 0 else 0
+
+
 class DeviceRollout:
     """Env copies resident on the GPU.  One C-ABI call (coevo_mpe_rollout) enqueues every cycle of every cohort: per
     cycle and cohort ONE merged launch (shared-opponent workgroups on the matrix cores + per-individual streaming
     workgroups, env step fused in); ``merged=False`` keeps the two-launch form (shared-opponent launch on a side stream
     beside the streaming launch) for A/B runs.  ``precision="float16"`` plays float16 nets (FCNetworkHalf) out of an fp16 slab
-    through coevo_mpe16_rollout."""
+    through coevo_mpe16_rollout.  ``desc`` is the descriptor template the constructor fills; every call hands the C side a
+    copy of its own (_call_desc) and no method writes to the template."""
 
     def __init__(self, plan: RolloutPlan, slab: torch.Tensor, env_seed=sa.ENV_SEED, timing_pairs=0, fused_step=True,
                  merged=None, precision="float32"):
@@ -242,6 +263,7 @@ class DeviceRollout:
         self._graphs = {}
         # what the last arming reset launch cleared and nobody has run on since: {cohort: (n_cycles, stamps re-armed?)}
         self._armed = {}
+        self._pending_stamps = 0   # cycles of the last timed rollout whose clock stamps collect_stamps() has not read yet
         self._timed_ms = []
         self._span_ms, self._span_cycles = [], 0
         self.ctx = L.load().coevo_rollout_ctx_create(int(timing_pairs))
@@ -309,8 +331,7 @@ class DeviceRollout:
             if not 0 < n_cycles <= self.stamp_cycles:
                 raise ValueError(f"arm: {n_cycles} cycles (1 .. {self.stamp_cycles})")
             first, count = (0, self.n_cohorts) if k is None else (int(k), 1)
-            stamps = (self.stamps.data_ptr() + 16 * L.STAMP_SLOTS * first * n_cycles) if self.time_light else None
-            sync = (self.sync_words.data_ptr() + 4 * first * self.sync_words_per_cohort) if self.sync_words is not None else None
+            stamps, sync = self._cohort_scratch(first, n_cycles)
             if stamps or sync:
                 L.call("coevo_mpe_reset_multi_prep", L._p(self.state), self.plan.n_games, _ct.cast(arr, _ct.c_void_p), len(segs),
                        self.rng, stamps, count * n_cycles * L.STAMP_SLOTS if stamps else 0, sync,
@@ -335,6 +356,43 @@ class DeviceRollout:
         for c in cohorts:
             self._armed.pop(c, None)
 
+    def _cohort_scratch(self, k, n_cycles):
+        """(stamps address, sync-words address) of cohort k, None where the rollout has none: the stamps are laid out
+        [cohort][n_cycles][STAMP_SLOTS] pairs of 8-byte ticks FOR THIS n_cycles, the sync words [cohort][sync_words_per_cohort]
+        int32; cohort 0's are the whole rollout's"""
+        stamps = (self.stamps.data_ptr() + 16 * L.STAMP_SLOTS * int(k) * int(n_cycles)) if self.time_light else None
+        sync = (self.sync_words.data_ptr() + 4 * int(k) * self.sync_words_per_cohort) if self.sync_words is not None else None
+        return stamps, sync
+
+    def _call_desc(self, n_cycles, cohort=None, armed=False, final=True, pack=None):
+        """the descriptor of ONE call: a copy of the template self.desc (the C side reads it during the call, and during graph
+        capture, only) for n_cycles cycles of every cohort, or of cohort `cohort` alone; see enqueue / enqueue_cohort"""
+        d = L.RolloutDesc()
+        L.C.memmove(L.C.byref(d), L.C.byref(self.desc), L.C.sizeof(d))
+        d.n_cycles = int(n_cycles)
+        stamps, sync = self._cohort_scratch(cohort or 0, n_cycles)
+        d.light_stamps = stamps
+        d.stamps_armed = 1 if (armed and stamps) else 0
+        d.sync_cleared = 1 if (armed and sync) else 0   # (zeroed by the persistent launch itself, or by the reset launch: armed)
+        if cohort is not None:
+            # its own tasks and scratch; the row limits stay the plan's (as in a call that runs every cohort: one kernel form)
+            d.heavy, d.n_heavy, _, d.light, d.n_light, _ = self.plan.cohort_tasks(cohort)
+            d.n_cohorts, d.heavy_begin, d.light_begin = 0, None, None
+            d.concurrent_hint = self.n_cohorts
+            if sync:
+                d.sync_words = sync
+        if not final:
+            assert d.state_alt, "only the fused-step rollout can leave its books open"
+            d.rewards = None
+        elif pack is not None:
+            out, dist, n_roles, n_local, hof, pitch, first = pack
+            d._pack = L.FinalPack(L._p(out), L._p(dist), int(n_roles), int(n_local), int(hof), int(pitch), int(first), 0)
+            d.pack = L.C.addressof(d._pack)   # (the attribute keeps the record alive as long as the descriptor)
+        return d
+
+    def _ctx(self):
+        return self.ctx if (self.overlap or self.n_cohorts > 1) else None
+
     def run(self, n_cycles):
         """enqueue n_cycles world cycles + the rewards kernel.  With use_graph the enqueue is captured once per
         (cycle count, timed?) into a hipGraph and replayed: the fork/join between the two policy launches then costs a
@@ -342,27 +400,25 @@ class DeviceRollout:
         n_cycles = int(n_cycles)
         assert n_cycles <= self.stamp_cycles
         self._take_arm(range(self.n_cohorts), n_cycles, False)
-        ctx = self.ctx if (self.overlap or self.n_cohorts > 1) else None
         timed = bool(self.time_light)
-        if self.use_graph:
-            # kernel timing inside a replayed graph comes from the kernel's own 100 MHz clock stamps
-            self.desc.light_stamps = L._p(self.stamps) if timed else None
-            key = (n_cycles, timed, bool(self.overlap))
-            g = self._graphs.get(key)
-            if g is None:
-                self.desc.n_cycles = n_cycles
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    L.call(self._entry, L.C.byref(self.desc), ctx, 0)
-                self._graphs[key] = g
-            g.replay()
-            if timed:
-                self._pending_stamps = n_cycles
+        if not self.use_graph:
+            d = self._call_desc(n_cycles)
+            d.light_stamps = None   # an eager run is timed with events
+            L.call(self._entry, L.C.byref(d), self._ctx(), 1 if timed else 0)
             return
-        self.desc.light_stamps = None
-        self.desc.n_cycles = n_cycles
-        L.call(self._entry, L.C.byref(self.desc), ctx, 1 if timed else 0)
+        # kernel timing inside a replayed graph comes from the kernel's own 100 MHz clock stamps
+        key = (n_cycles, timed, bool(self.overlap))
+        g = self._graphs.get(key)
+        if g is None:
+            d = self._call_desc(n_cycles)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                L.call(self._entry, L.C.byref(d), self._ctx(), 0)
+            self._graphs[key] = g
+        g.replay()
+        if timed:
+            self._pending_stamps = n_cycles
 
     def enqueue(self, n_cycles, final=True, armed=False, pack=None):
         """plain enqueue on the current stream (no graph of its own): for callers that capture a larger graph.
@@ -372,26 +428,8 @@ class DeviceRollout:
         armed: the reset launch in front of it re-armed the clock stamps and zeroed the sync words of EVERY cohort for this
         n_cycles (reset_segments(arm=(None, n_cycles)), or arm=(0, n_cycles) with one cohort); raises ValueError otherwise"""
         self._take_arm(range(self.n_cohorts), n_cycles, armed)
-        self.desc.light_stamps = L._p(self.stamps) if self.time_light else None
-        self.desc.n_cycles = int(n_cycles)
-        self.desc.stamps_armed = 1 if (armed and self.time_light) else 0
-        self.desc.sync_cleared = 1 if (armed and self.sync_words is not None) else 0
-        keep = self.desc.rewards
-        fp = None
-        if not final:
-            assert self.desc.state_alt, "only the fused-step rollout can leave its books open"
-            self.desc.rewards = None
-        elif pack is not None:
-            out, dist, n_roles, n_local, hof, pitch, first = pack
-            fp = L.FinalPack(L._p(out), L._p(dist), int(n_roles), int(n_local), int(hof), int(pitch), int(first), 0)
-            self.desc.pack = L.C.addressof(fp)
-        try:
-            L.call(self._entry, L.C.byref(self.desc), self.ctx if (self.overlap or self.n_cohorts > 1) else None, 0)
-        finally:
-            self.desc.rewards = keep
-            self.desc.pack = None
-            self.desc.stamps_armed = 0
-            self.desc.sync_cleared = 0
+        d = self._call_desc(n_cycles, armed=armed, final=final, pack=pack)
+        L.call(self._entry, L.C.byref(d), self._ctx(), 0)
         if self.time_light:
             self._pending_stamps = int(n_cycles)
 
@@ -401,25 +439,7 @@ class DeviceRollout:
         armed: reset_segments(arm=(k, n_cycles)) (or arm=(None, n_cycles)) ran in front of it; raises ValueError otherwise"""
         assert self.n_cohorts > 1 and self.desc.merged
         self._take_arm((int(k),), n_cycles, armed)
-        p = self.plan
-        hb, he = int(p.heavy_begin_np[k]), int(p.heavy_begin_np[k + 1])
-        lb, le = int(p.light_begin_np[k]), int(p.light_begin_np[k + 1])
-        tsz = L.TASK_DTYPE.itemsize
-        d = L.RolloutDesc()
-        L.C.memmove(L.C.byref(d), L.C.byref(self.desc), L.C.sizeof(d))
-        d.heavy = (p.heavy.data_ptr() + hb * tsz) if he > hb else None
-        d.n_heavy = he - hb
-        d.light = (p.light.data_ptr() + lb * tsz) if le > lb else None
-        d.n_light = le - lb
-        d.n_cohorts, d.heavy_begin, d.light_begin = 0, None, None
-        d.concurrent_hint = self.n_cohorts
-        d.n_cycles = int(n_cycles)
-        d.rewards = None
-        d.light_stamps = (self.stamps.data_ptr() + 16 * L.STAMP_SLOTS * k * int(n_cycles)) if self.time_light else None
-        d.stamps_armed = 1 if (armed and self.time_light) else 0
-        if self.sync_words is not None:   # this cohort's own scratch (zeroed by the launch, or by the reset launch: armed)
-            d.sync_words = self.sync_words.data_ptr() + 4 * k * self.sync_words_per_cohort
-            d.sync_cleared = 1 if armed else 0
+        d = self._call_desc(n_cycles, cohort=int(k), armed=armed, final=False)
         L._check(getattr(L.load(), self._entry)(L.C.byref(d), self.ctx, 0, stream.cuda_stream), self._entry)
         if self.time_light:
             self._pending_stamps = int(n_cycles)
@@ -429,8 +449,7 @@ class DeviceRollout:
         pack = (out [n_roles][n_local][4] fp64, dist [n_roles][pitch] fp32, n_roles, n_local, hof, pitch, first): this rank's
         record of the fitness all-gather written by the same launch (coevo_mpe_final_step_pack)"""
         n, last = self.plan.n_games, int(n_cycles) - 1
-        st_last = self.state2[0] if last <= 0 or (last & 1) == 0 else self.state2[1]
-        act = self.actions_by_game[(last if last > 0 else 0) & 1]
+        st_last, act = self.state2[last_buffer(n_cycles)], self.actions_by_game[last_buffer(n_cycles)]
         if pack is not None:
             out, dist, n_roles, n_local, hof, pitch, first = pack
             L.call("coevo_mpe_final_step_pack", L._p(st_last), n, L._p(act), last, L._p(self.limits), self.pos_first,
@@ -530,17 +549,12 @@ class HostEnvRollout:
             rows = p.cohort_row_begin_np if p.cohort_row_begin_np is not None else np.array([0, p.n_rows])
             self._cohort_games = [np.ascontiguousarray(np.nonzero(p.game_cohort_np == k)[0], dtype=np.int32)
                                   for k in range(K)]
-            tsz = L.TASK_DTYPE.itemsize
             self._cohorts = (L.HostCohort * K)()
             for k in range(K):
-                hb, he = int(p.heavy_begin_np[k]), int(p.heavy_begin_np[k + 1])
-                lb, le = int(p.light_begin_np[k]), int(p.light_begin_np[k + 1])
+                heavy, n_heavy, heavy_rows, light, n_light, light_rows = p.cohort_tasks(k)
                 self._cohorts[k] = L.HostCohort(
-                    heavy=(p.heavy.data_ptr() + hb * tsz) if he > hb else None,
-                    light=(p.light.data_ptr() + lb * tsz) if le > lb else None,
-                    games=self._cohort_games[k].ctypes.data, n_heavy=he - hb,
-                    heavy_max_rows=int(max(p.heavy_np["n_rows"][hb:he], default=0)), n_light=le - lb,
-                    light_max_rows=int(max(p.light_np["n_rows"][lb:le], default=0)),
+                    heavy=heavy, light=light, games=self._cohort_games[k].ctypes.data, n_heavy=n_heavy,
+                    heavy_max_rows=heavy_rows, n_light=n_light, light_max_rows=light_rows,
                     n_games=len(self._cohort_games[k]), row_first=int(rows[k]), n_rows=int(rows[k + 1] - rows[k]))
 
     def close(self):

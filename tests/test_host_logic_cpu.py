@@ -171,6 +171,56 @@ def test_rollout_plan_cohorts_partition_games():
     assert tied.n_cohorts == 1
 
 
+def _assert_cohort_tasks(plan):
+    """cohort_tasks(k) against the tables it slices: counts and row limits from heavy_begin_np / light_begin_np, no pointer
+    without device tables"""
+    for k in range(plan.n_cohorts):
+        hb, he = int(plan.heavy_begin_np[k]), int(plan.heavy_begin_np[k + 1])
+        lb, le = int(plan.light_begin_np[k]), int(plan.light_begin_np[k + 1])
+        want = (None, he - hb, max([int(t["n_rows"]) for t in plan.heavy_np[hb:he]], default=0),
+                None, le - lb, max([int(t["n_rows"]) for t in plan.light_np[lb:le]], default=0))
+        assert plan.cohort_tasks(k) == want, k
+    parts = [plan.cohort_tasks(k) for k in range(plan.n_cohorts)]
+    assert sum(p[1] for p in parts) == len(plan.heavy_np) and sum(p[4] for p in parts) == len(plan.light_np)
+    assert max(p[2] for p in parts) == plan.heavy_max and max(p[5] for p in parts) == plan.light_max
+    return parts
+
+
+def test_cohort_tasks_slices_the_task_tables():
+    npop, nh = 30, 3
+    off = {i: i * 10 for i in range(npop + 2 * nh)}
+    D = {**{i: 10 for i in range(npop + nh)}, **{npop + nh + k: 8 for k in range(nh)}}
+    games = [(npop + nh + k, i, npop + k) for i in range(npop) for k in range(nh)]
+    for K in (1, 2, 3):
+        plan = RolloutPlan(np.array(games), off, D, device=None, n_cohorts=K)
+        parts = _assert_cohort_tasks(plan)
+        assert len(parts) == K and all(p[1] > 0 and p[4] > 0 for p in parts)
+    # cohort 1 holds two individuals with opponents of their own (two rows each): no shared-opponent task there
+    games = [(200, i, 100) for i in range(10)] + [(201 + j, 10 + j, 101 + j) for j in range(2) for _ in range(2)]
+    off = {n: 16 * n for n in list(range(12)) + [100, 101, 102, 200, 201, 202]}
+    D = {n: (8 if n >= 200 else 10) for n in off}
+    plan = RolloutPlan(np.array(games), off, D, device=None, game_cohort=np.array([0] * 10 + [1] * 4))
+    parts = _assert_cohort_tasks(plan)
+    assert parts[0][1:3] == (2, 10) and parts[0][4:] == (10, 1) and parts[1] == (None, 0, 0, None, 6, 2)
+    # one trio plays nine games: three shared-opponent tasks, no per-individual task
+    plan = RolloutPlan(np.array([(200, 0, 100)] * 9), off, D, device=None)
+    assert _assert_cohort_tasks(plan) == [(None, 3, 9, None, 0, 0)]
+
+
+def test_last_buffer_follows_the_parity_rule_of_the_descriptor():
+    """coevo.h: buffer 0 holds the reset state, cycle c writes its state to buffer c & 1 - cycle 0 writes none - and its
+    actions to action buffer c & 1; the closing step reads what the last cycle left, both from buffer last_buffer(n_cycles)"""
+    from coevonet_amd.rollout import last_buffer
+    for n_cycles in (0, 1, 2, 3):
+        state_in, actions_in = 0, 0          # played forward: where the newest state / actions are
+        for c in range(n_cycles):
+            if c > 0:
+                state_in = c & 1
+            actions_in = c & 1
+        assert last_buffer(n_cycles) == state_in == actions_in, n_cycles
+    assert [last_buffer(n) for n in (0, 1, 2, 3)] == [0, 0, 1, 0]
+
+
 @pytest.mark.parametrize("n_local,K", [(9, 2), (201, 2), (200, 3), (11, 3), (10, 2), (7, 7), (5, 1)])
 def test_cohort_partition_is_one_consistent_partition(n_local, K):
     """the rollout plan's game -> cohort map and the breeding / reset ranges come from the same boundaries (odd

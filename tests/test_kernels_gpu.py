@@ -376,8 +376,7 @@ def test_persistent_rollout_equals_per_cycle_launches_over_shapes(npop, nh, heav
     from coevonet_amd.rollout import DeviceRollout
     plan, slab, games, _, _ = _small_launch_setup(npop, nh, heavy_rows, cohorts)
     for k in range(plan.n_cohorts):
-        n_h = int(plan.heavy_begin_np[k + 1] - plan.heavy_begin_np[k])
-        n_l = int(plan.light_begin_np[k + 1] - plan.light_begin_np[k])
+        _, n_h, _, _, n_l, _ = plan.cohort_tasks(k)
         assert L.load().coevo_mpe_persistent_fits(n_h, n_l, plan.heavy_max, plan.light_max, plan.n_cohorts) == 1
     got = []
     for persistent in (True, False):
@@ -439,8 +438,7 @@ def test_small_launch_kernel_matches_oracle(npop, nh, heavy_rows, cohorts, persi
     plan = RolloutPlan(np.array(games), off, D, device=DEV, n_cohorts=cohorts, heavy_rows=heavy_rows)
     assert plan.n_cohorts == cohorts and plan.heavy_max <= heavy_rows <= 8 and plan.light_max == nh
     for k in range(cohorts):
-        n_h = int(plan.heavy_begin_np[k + 1] - plan.heavy_begin_np[k])
-        n_l = int(plan.light_begin_np[k + 1] - plan.light_begin_np[k])
+        _, n_h, _, _, n_l, _ = plan.cohort_tasks(k)
         assert L.load().coevo_mpe_persistent_fits(n_h, n_l, plan.heavy_max, plan.light_max, cohorts) == 1
         # (90 individuals: 270 workgroups, two per CU on some - persistent only; per cycle that shape runs the lean kernel)
         form = L.load().coevo_mpe_cycle_kernel_form(n_h, n_l, plan.heavy_max, plan.light_max, cohorts)

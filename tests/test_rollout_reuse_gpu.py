@@ -44,8 +44,8 @@ class Setup:
 
     def shape(self, k):
         p = self.plan
-        return (int(p.heavy_begin_np[k + 1] - p.heavy_begin_np[k]), int(p.light_begin_np[k + 1] - p.light_begin_np[k]),
-                p.heavy_max, p.light_max, p.n_cohorts)
+        _, n_h, _, _, n_l, _ = p.cohort_tasks(k)
+        return (n_h, n_l, p.heavy_max, p.light_max, p.n_cohorts)
 
     def assert_form(self, form):
         """every cohort takes the form the test is about: ONE persistent launch (conc = K), or that per-cycle kernel"""
@@ -258,7 +258,7 @@ def test_sharded_loop_two_persistent_cohorts_match_oracle_port(monkeypatch):
     assert eng.K == 2 and eng.ro.n_cohorts == 2 and not eng.pipelined and eng.ro.desc.merged and eng.sharded_run
     p = eng.ro.plan
     for k in range(2):
-        n_h, n_l = int(p.heavy_begin_np[k + 1] - p.heavy_begin_np[k]), int(p.light_begin_np[k + 1] - p.light_begin_np[k])
+        _, n_h, _, _, n_l, _ = p.cohort_tasks(k)
         assert L.load().coevo_mpe_persistent_fits(n_h, n_l, p.heavy_max, p.light_max, 2) == 1
     torch.manual_seed(5)
     np.random.seed(5)
