@@ -22,6 +22,7 @@
 #include "dqn_conv.hip.h"
 #include "dqn16_layout.hip.h"
 #include "fc16_layout.hip.h"
+#include "../../include/coevo_ext.h"
 
 namespace coevo {
 
@@ -36,30 +37,7 @@ namespace coevo {
 // (exact for fp16 values; the reference's .to(float16)), the padding is zeroed.  Else slab -> flat (fp16 values as fp32).
 __global__ __launch_bounds__(256) void dqn16_pack_kernel(float *flat, uint32_t *slab, int C, int n, bool to_slab)
 {
-    const DqnLayout L = dqn16_layout(C, n);
-    const int64_t P = dqn_param_count(C, n);
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= L.stride) return;
-    uint32_t *word = slab + (int64_t)blockIdx.y * L.stride + s;
-    float *f = flat + (int64_t)blockIdx.y * P;
-    if (s >= L.wf && s < L.bf) {
-        const int64_t F_wf = 32LL * C * 64 + 32 + 64LL * 512 + 64 + 64LL * 576 + 64, h = 2 * (s - L.wf);
-        float *f0 = f + F_wf + dqn16_fc1_half_to_flat(h), *f1 = f + F_wf + dqn16_fc1_half_to_flat(h + 1);
-        _Float16 pair[2];
-        if (to_slab) {
-            pair[0] = (_Float16)*f0;
-            pair[1] = (_Float16)*f1;
-            __builtin_memcpy(word, pair, 4);
-        } else {
-            __builtin_memcpy(pair, word, 4);
-            *f0 = (float)pair[0];
-            *f1 = (float)pair[1];
-        }
-        return;
-    }
-    const int64_t p = dqn16_word_to_flat(s, C, n);
-    if (to_slab) *word = (p >= 0) ? __float_as_uint(f16r(f[p])) : 0u;
-    else if (p >= 0) f[p] = __uint_as_float(*word);
+    dqn16_pack_word(flat, slab, C, n, to_slab, 0);
 }
 
 // The conv stack of one frame: dqn_conv_kernel (deepqn.hip) with the contract's three rounding points.  One form serves every
@@ -273,9 +251,11 @@ extern "C" int coevo_dqn16_unpack(const void *slab, float *flat, int n, int C, i
 }
 
 // conv stack + fc1 of every row (hid: post-ReLU fc1 outputs, fp16 values, behind the conv3 activations in the workspace), after
-// the argument checks the two float16 forward entry points share
+// the argument checks the float16 forward entry points share.  fc1_tiled: the slab's fc1 block is wft16 (dqn16_layout.hip.h; the
+// *_tiled entry points of include/coevo_ext.h) and the fc1 launch is dqn16_tiled.hip's
 static int dqn16_hidden_launch(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task, int n_rows_total,
-                               int C, int n_actions, const uint8_t *frames, int32_t *status, void *workspace, hipStream_t s)
+                               int C, int n_actions, const uint8_t *frames, int32_t *status, void *workspace, hipStream_t s,
+                               bool fc1_tiled)
 {
     if (!slab || !tasks || !frames || !status || !workspace) return COEVO_ERR_ARG;
     if (n_tasks <= 0 || n_rows_total <= 0 || !dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;   // (any bit or-ed into C fails here)
@@ -290,18 +270,19 @@ static int dqn16_hidden_launch(const void *slab, const coevo_dqn_task *tasks, in
     else if (C == 6) hipLaunchKernelGGL((dqn16_conv_kernel<6, 6>), cg, cb, 0, s, sl, tasks, n_tasks, n_rows_total, C, n_actions, frames, act);
     else hipLaunchKernelGGL((dqn16_conv_kernel<6, 0>), cg, cb, 0, s, sl, tasks, n_tasks, n_rows_total, C, n_actions, frames, act);
     const dim3 fg(8 * ((n_tasks + 7) / 8), 8);
-    hipLaunchKernelGGL(dqn16_fc1_kernel, fg, dim3(64), 0, s, sl, tasks, n_tasks, C, n_actions, act, hid, status);
+    if (fc1_tiled) dqn16_fc1_tiled_launch(sl, tasks, n_tasks, C, n_actions, act, hid, status, s);
+    else hipLaunchKernelGGL(dqn16_fc1_kernel, fg, dim3(64), 0, s, sl, tasks, n_tasks, C, n_actions, act, hid, status);
     return COEVO_OK;
 }
 
-extern "C" int coevo_dqn16_forward_argmax(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
-                                          int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *actions,
-                                          float *logits, int32_t *status, void *workspace, void *stream)
+static int dqn16_argmax_launch(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task, int n_rows_total,
+                               int C, int n_actions, const uint8_t *frames, int32_t *actions, float *logits, int32_t *status,
+                               void *workspace, void *stream, bool fc1_tiled)
 {
     if (!actions) return COEVO_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int rc = dqn16_hidden_launch(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, status,
-                                       workspace, s);
+                                       workspace, s, fc1_tiled);
     if (rc != COEVO_OK) return rc;
     const float *hid = static_cast<const float *>(workspace) + (size_t)n_rows_total * DQ_FC1_IN;
     hipLaunchKernelGGL(dqn16_out_kernel, dim3(n_rows_total), dim3(64), 0, s, static_cast<const uint32_t *>(slab), tasks, n_tasks, C,
@@ -310,13 +291,47 @@ extern "C" int coevo_dqn16_forward_argmax(const void *slab, const coevo_dqn_task
     return COEVO_OK;
 }
 
+static int dqn16_hidden_checked(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task, int n_rows_total,
+                                int C, int n_actions, const uint8_t *frames, int32_t *status, void *workspace, void *stream,
+                                bool fc1_tiled)
+{
+    const int rc = dqn16_hidden_launch(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, status,
+                                       workspace, (hipStream_t)stream, fc1_tiled);
+    if (rc != COEVO_OK) return rc;
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_dqn16_forward_argmax(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
+                                          int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *actions,
+                                          float *logits, int32_t *status, void *workspace, void *stream)
+{
+    return dqn16_argmax_launch(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, actions, logits,
+                               status, workspace, stream, false);
+}
+
 extern "C" int coevo_dqn16_forward_hidden(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
                                           int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *status,
                                           void *workspace, void *stream)
 {
-    const int rc = dqn16_hidden_launch(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, status,
-                                       workspace, (hipStream_t)stream);
-    if (rc != COEVO_OK) return rc;
-    COEVO_HIP_CHECK(hipGetLastError());
-    return COEVO_OK;
+    return dqn16_hidden_checked(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, status, workspace,
+                                stream, false);
+}
+
+// ---- the same two over a slab whose fc1 block is TILED (include/coevo_ext.h): the conv launch and the output launch are the
+// ones above, the fc1 launch is dqn16_fc1_tiled_kernel (dqn16_tiled.hip); arguments and refusals are their twins'
+extern "C" int coevo_dqn16_forward_argmax_tiled(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
+                                                int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *actions,
+                                                float *logits, int32_t *status, void *workspace, void *stream)
+{
+    return dqn16_argmax_launch(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, actions, logits,
+                               status, workspace, stream, true);
+}
+
+extern "C" int coevo_dqn16_forward_hidden_tiled(const void *slab, const coevo_dqn_task *tasks, int n_tasks, int max_rows_per_task,
+                                                int n_rows_total, int C, int n_actions, const uint8_t *frames, int32_t *status,
+                                                void *workspace, void *stream)
+{
+    return dqn16_hidden_checked(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, status, workspace,
+                                stream, true);
 }

@@ -24,14 +24,7 @@
 
 namespace coevo {
 
-// squared distance of piece u of net a to the same piece of net b: the piece's entries in slab order, padding left out
-__device__ __forceinline__ double dq16_piece_d2(const uint4 &a, const uint4 &b, int u, const DqnLayout &L)
-{
-    if (dq16_fc1_piece(u, L)) return f16_d2_halves(a, b);
-    return f16_d2_words(a, b, [&](int i) { return 4 * (int64_t)u + i < L.total; });   // dqn16_word_to_flat >= 0
-}
-
-// grid (coevo_dqn16_perturb_blocks, n_children): workgroup (bx, c) writes pieces 256 bx .. 256 bx + 255 of child c
+// grid (coevo_dqn16_perturb_blocks, n_children): dq16_perturb_dist_body (dqn16_pieces.hip.h) with the streamed fc1 block's noise
 __global__ __launch_bounds__(256) void dqn16_perturb_dist_kernel(const uint32_t *parent_slab, const int32_t *parent_idx,
                                                                   uint32_t *child_slab, int child_first, int C, int n_actions,
                                                                   const float *sigma_dev, uint64_t seed,
@@ -40,47 +33,10 @@ __global__ __launch_bounds__(256) void dqn16_perturb_dist_kernel(const uint32_t 
                                                                   const uint32_t *dist_ref, double *dist_partial)
 {
     __shared__ double scratch[4];
-    if (gen_dev) stream_hi += 4u * (uint32_t)(*gen_dev + gen_bias);   // generation-indexed noise stream without a host argument
-    const int c = blockIdx.y, bx = blockIdx.x;
-    const uint32_t slo = stream_lo_first + (uint32_t)c;
-    const DqnLayout L = dqn16_layout(C, n_actions);
-    const int u = bx * 256 + (int)threadIdx.x;
-    double d2 = 0.0;
-    if (u < dq16_pieces(L)) {
-        const uint4 pv = reinterpret_cast<const uint4 *>(parent_slab + (int64_t)parent_idx[c] * L.stride)[u];
-        uint4 ov = pv;
-        if (!(flags & COEVO_DQP_COPY)) {
-            const float sigma = *sigma_dev;
-            if (dq16_fc1_piece(u, L)) {
-                float noise[8];
-                dq16_fc1_piece_noise(u, L, C, sigma, seed, slo, stream_hi, noise);
-                _Float16 hin[8], hout[8];
-                __builtin_memcpy(hin, &pv, sizeof(hin));
-#pragma unroll
-                for (int i = 0; i < 8; ++i) hout[i] = (_Float16)f16_child((float)hin[i], noise[i]);
-                __builtin_memcpy(&ov, hout, sizeof(hout));
-            } else {
-                int64_t p[4];
-                bool want[4];
-                dq16_word_piece_flat(u, C, n_actions, p);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) want[i] = dq16_word_moves(4 * (int64_t)u + i, L, (flags & COEVO_DQP_SKIP_BN) != 0);
-                float in[4], out[4], noise[4];
-                dq16_word_piece_noise(p, want, sigma, seed, slo, stream_hi, noise);
-                __builtin_memcpy(in, &pv, sizeof(in));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) out[i] = want[i] ? f16_child(in[i], noise[i]) : in[i];
-                __builtin_memcpy(&ov, out, sizeof(out));
-            }
-        }
-        // a plain store: the rollout reads the child next
-        if (child_slab) reinterpret_cast<uint4 *>(child_slab + (int64_t)(child_first + c) * L.stride)[u] = ov;
-        if (dist_partial) d2 = dq16_piece_d2(ov, reinterpret_cast<const uint4 *>(dist_ref)[u], u, L);
-    }
-    if (dist_partial) {   // uniform over the launch
-        const double tot = block_sum_f64(d2, scratch);
-        if (threadIdx.x == 0) dist_partial[(size_t)c * gridDim.x + bx] = tot;
-    }
+    const Dq16PerturbArgs a{parent_slab, parent_idx, child_slab, child_first, C, n_actions, sigma_dev, seed, stream_lo_first,
+                            stream_hi, flags, gen_dev, gen_bias, dist_ref, dist_partial};
+    dq16_perturb_dist_body(a, scratch, [](int u, const DqnLayout &L, int C, float sigma, uint64_t seed, uint32_t slo, uint32_t shi,
+                                          float (&noise)[8]) { dq16_fc1_piece_noise(u, L, C, sigma, seed, slo, shi, noise); });
 }
 
 // the same partials for nets that are already in a slab (generation 0, uploaded populations): grid (blocks, n)
@@ -113,15 +69,9 @@ extern "C" int coevo_dqn16_perturb_dist(const void *parent_slab, const int32_t *
                                         uint32_t stream_lo_first, uint32_t stream_hi, int flags, const int32_t *gen_dev,
                                         int gen_bias, const void *dist_ref, double *dist_partial, void *stream)
 {
-    if ((dist_ref == nullptr) != (dist_partial == nullptr)) return COEVO_ERR_ARG;
-    if (!dqn_shape_ok(C, n_actions)) return COEVO_ERR_ARG;   // (any bit or-ed into C fails here)
-    if (flags & ~(COEVO_DQP_SKIP_BN | COEVO_DQP_COPY)) return COEVO_ERR_ARG;   // antithetic / from-order: not built for fp16
-    const bool copy = (flags & COEVO_DQP_COPY) != 0;
-    if (!parent_slab || !parent_idx || (!sigma_dev && !copy)) return COEVO_ERR_ARG;
-    if (!child_slab && !(copy && dist_partial)) return COEVO_ERR_ARG;   // NULL child: the distance of existing nets only
-    if (!aligned16(parent_slab) || !aligned16(child_slab) || !aligned16(dist_ref)) return COEVO_ERR_ARG;
-    if (n_children < 0 || child_first < 0 || n_children > 65535) return COEVO_ERR_ARG;
-    if (n_children == 0) return COEVO_OK;
+    const int rc = dqn16_perturb_args(parent_slab, parent_idx, child_slab, child_first, n_children, C, n_actions, sigma_dev, flags,
+                                      dist_ref, dist_partial);
+    if (rc != COEVO_OK) return rc < 0 ? rc : COEVO_OK;
     const dim3 grid(dqn16_blocks(C, n_actions), (unsigned)n_children);
     hipLaunchKernelGGL(dqn16_perturb_dist_kernel, grid, dim3(256), 0, (hipStream_t)stream,
                        static_cast<const uint32_t *>(parent_slab), parent_idx, static_cast<uint32_t *>(child_slab), child_first,

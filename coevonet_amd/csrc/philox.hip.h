@@ -98,9 +98,15 @@ __device__ inline void box_muller(uint32_t a, uint32_t b, float &z0, float &z1)
     z1 = r * s;
 }
 
+// the Philox block of noise quad q (canonical indices 4 q .. 4 q + 3) in stream (stream_lo, stream_hi)
+__device__ inline u32x4 philox_noise_block(uint64_t seed, uint32_t stream_lo, uint32_t stream_hi, uint32_t q)
+{
+    return philox4x32<COEVO_NOISE_ROUNDS>(q, stream_lo, stream_hi, 0x636f6576u, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
 __device__ inline void philox_normal4(uint64_t seed, uint32_t stream_lo, uint32_t stream_hi, uint32_t q, float z[4])
 {
-    const u32x4 o = philox4x32<COEVO_NOISE_ROUNDS>(q, stream_lo, stream_hi, 0x636f6576u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const u32x4 o = philox_noise_block(seed, stream_lo, stream_hi, q);
     box_muller(o.v[0], o.v[1], z[0], z[1]);
     box_muller(o.v[2], o.v[3], z[2], z[3]);
 }

@@ -29,10 +29,16 @@ class HalfSynthRollout(SynthRollout):
     output row of the previous step, its booking, the next frames; coevo_synth_step at t = 0) and the conv-stack and fc1 launches
     of coevo_dqn16_forward_hidden.  ``COEVO_DQN16_FUSED_OUT=0``, read at construction, keeps the four-launch route
     (coevo_synth_step + coevo_dqn16_forward_argmax) for A/B runs: the same words in every buffer the engines read.  It
-    synchronises with nothing, so a generation can be captured into a graph."""
+    synchronises with nothing, so a generation can be captured into a graph.  ``fc1_tiled``: the slab's fc1 block is tiled
+    (include/coevo_ext.h) and the forward pair is coevo_dqn16_forward_hidden_tiled / coevo_dqn16_forward_argmax_tiled; the
+    output row never reads fc1 and keeps its entry point."""
 
-    def __init__(self, game_nets, net_off, ordinal0, C, n_actions, slab, env_seed, ordinals_per_gen, device="cuda"):
+    def __init__(self, game_nets, net_off, ordinal0, C, n_actions, slab, env_seed, ordinals_per_gen, device="cuda", *,
+                 fc1_tiled=False):
         super().__init__(game_nets, net_off, ordinal0, C, n_actions, slab, env_seed, ordinals_per_gen, device)
+        self.fc1_tiled = bool(fc1_tiled)   # (self.Cw stays the plain channel count: every float16 entry point refuses the bit)
+        sfx = "_tiled" if self.fc1_tiled else ""
+        self._hidden_entry, self._argmax_entry = "coevo_dqn16_forward_hidden" + sfx, "coevo_dqn16_forward_argmax" + sfx
         ln = self.lanes[0]
         ln["ws"] = torch.zeros(int(L.load().coevo_dqn16_workspace_bytes(ln["n"])) // 4, dtype=torch.float32, device=device)
         self.fused_out = os.environ.get("COEVO_DQN16_FUSED_OUT", "1") != "0"
@@ -60,11 +66,10 @@ class HalfSynthRollout(SynthRollout):
         else:
             L._check(lib.coevo_synth_step(*env, stream), "coevo_synth_step")
         if t < T and self.fused_out:
-            L._check(lib.coevo_dqn16_forward_hidden(*fwd, L._p(self.status), L._p(ln["ws"]), stream),
-                     "coevo_dqn16_forward_hidden")
+            L._check(getattr(lib, self._hidden_entry)(*fwd, L._p(self.status), L._p(ln["ws"]), stream), self._hidden_entry)
         elif t < T:
-            L._check(lib.coevo_dqn16_forward_argmax(*fwd, ln["actions"][p].data_ptr(), None, L._p(self.status),
-                                                    L._p(ln["ws"]), stream), "coevo_dqn16_forward_argmax")
+            L._check(getattr(lib, self._argmax_entry)(*fwd, ln["actions"][p].data_ptr(), None, L._p(self.status),
+                                                      L._p(ln["ws"]), stream), self._argmax_entry)
 
     def weight_bytes_per_round(self):
         """algorithmic bytes of one round (two agent-steps): every distinct acting fp16 weight set once per agent-step + the
@@ -75,10 +80,16 @@ class HalfSynthRollout(SynthRollout):
 
 
 class HalfDQNGAEngine(DQNGAEngine):
-    """``DQNGAEngine`` on one rank over an fp16 slab (coevo_dqn16_pack's layout, which has no tiled fc1): its constructor, game
-    table, ``load_initial``, tail, ``step`` and ``eval_only``, with the float16 entry points and three hooks - the rollout, the
-    distances of the initial population and the children of a role.  Nets go in and out as flat float32 arrays of fp16 values in
-    parameters() order (``DeepQNHalf.flat()``)."""
+    """``DQNGAEngine`` on one rank over an fp16 slab (coevo_dqn16_pack's layout): its constructor, game table, ``load_initial``,
+    tail, ``step`` and ``eval_only``, with the float16 entry points and three hooks - the rollout, the distances of the initial
+    population and the children of a role.  Nets go in and out as flat float32 arrays of fp16 values in parameters() order
+    (``DeepQNHalf.flat()``).
+
+    ``fc1_layout``: "streamed" (the default) or "tiled" - the slab's fc1 block in the form of include/coevo_ext.h, for
+    v_mfma_f32_16x16x4 tiles in the rollout's fc1 launch.  Upload / download, the rollout's forward pair and the children then go
+    through the ``*_tiled`` entry points; the distances of the initial population stay coevo_dqn16_distance (both nets have one
+    form).  Every result - rewards, fitness, distances, downloaded nets - is the streamed engine's, bit for bit.  ``fc1_tiled``
+    says which form the slab has."""
     _pack_unpack = ("coevo_dqn16_pack", "coevo_dqn16_unpack")   # flat arrays carry fp16 values in float32
     _slab_dtype = torch.int32
     _stride_entry, _pblocks_entry = "coevo_dqn16_slab_stride", "coevo_dqn16_perturb_blocks"
@@ -88,7 +99,7 @@ class HalfDQNGAEngine(DQNGAEngine):
 
     def __init__(self, pop, hof, elites, C, n_actions, T_train, T_eval, device="cuda", env_seed=SYNTH_SEED, philox_seed=0,
                  first_ordinal=1, capacity=1024, sigmas=(0.05, 0.05), sig_min=0.001, sig_max=0.2, adaptive=True, *,
-                 shard=(0, 1), gather=None, frames="device"):
+                 shard=(0, 1), gather=None, frames="device", fc1_layout="streamed"):
         # what float16 does not cover is refused before the library is loaded
         if tuple(shard) != (0, 1):
             raise ValueError(f"HalfDQNGAEngine: precision float16 runs on one rank only, not shard {tuple(shard)}")
@@ -98,18 +109,26 @@ class HalfDQNGAEngine(DQNGAEngine):
             raise ValueError("HalfDQNGAEngine: precision float16 runs on one rank only and takes no gather")
         if not (1 <= elites <= pop and hof >= 1):
             raise ValueError(f"HalfDQNGAEngine: elites {elites} (1 .. population {pop}) or hof {hof} (>= 1) out of range")
+        if fc1_layout not in ("streamed", "tiled"):
+            raise ValueError(f'HalfDQNGAEngine: fc1_layout is "streamed" or "tiled", not {fc1_layout!r}')
+        self._half_tiled = fc1_layout == "tiled"   # (the constructor below builds the rollout: set first)
+        if self._half_tiled:
+            self._pack_unpack = ("coevo_dqn16_pack_tiled", "coevo_dqn16_unpack_tiled")
         super().__init__(pop, hof, elites, C, n_actions, T_train, T_eval, device=device, env_seed=env_seed,
                          philox_seed=philox_seed, first_ordinal=first_ordinal, capacity=capacity, sigmas=sigmas,
                          sig_min=sig_min, sig_max=sig_max, adaptive=adaptive)
+        self.fc1_tiled = self._half_tiled   # (self.Cw stays the plain channel count)
 
     def _rollout(self, games, net_off, ordinal0, env_seed):
-        return HalfSynthRollout(games, net_off, ordinal0, self.C, self.n_actions, self.slab, env_seed, self.per_gen, self.device)
+        return HalfSynthRollout(games, net_off, ordinal0, self.C, self.n_actions, self.slab, env_seed, self.per_gen, self.device,
+                                fc1_tiled=self._half_tiled)
 
     def _initial_distance(self, r):
         L.call("coevo_dqn16_distance", self._ptr(r, "stale"), self._ptr(r, "pop"), self.pop, self.C, self.n_actions,
                L._p(self.dist_partial))
 
     def _breed_children(self, ri, r, c_lo, c_hi, g):
-        L.call("coevo_dqn16_perturb_dist", self._ptr(r, "elite"), self.parent_idx.data_ptr() + 4 * c_lo, self._ptr(r, "pop"),
+        L.call("coevo_dqn16_perturb_dist_tiled" if self.fc1_tiled else "coevo_dqn16_perturb_dist",
+               self._ptr(r, "elite"), self.parent_idx.data_ptr() + 4 * c_lo, self._ptr(r, "pop"),
                1 + c_lo, c_hi - c_lo, self.C, self.n_actions, self.sigma32.data_ptr() + 4 * ri, self.philox_seed, c_lo, ri, 0, g,
                0, self._ptr(r, "stale"), L._p(self.dist_partial))

@@ -586,7 +586,8 @@ class DQNGATrainer:
             from .dqn_ga_half import HalfDQNGAEngine   # (imports this module)
             pop_flat, hof_flat = ({r: half_values(f[r]) for r in ROLES2} for f in (pop_flat, hof_flat))
             self.eng = HalfDQNGAEngine(args.population, args.hof_size, args.elites_number, C, n,
-                                       args.max_timesteps_per_episode, args.max_evaluation_steps, **common)
+                                       args.max_timesteps_per_episode, args.max_evaluation_steps,
+                                       fc1_layout=getattr(args, "coevo_fc1_layout", "streamed"), **common)
         else:
             self.eng = DQNGAEngine(args.population, args.hof_size, args.elites_number, C, n,
                                    args.max_timesteps_per_episode, args.max_evaluation_steps, shard=shard, gather=gather,

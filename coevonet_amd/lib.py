@@ -19,6 +19,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COEVO_LIB") or os.path.join(HERE, "libcoevo.so")  # COEVO_LIB: A/B builds
 HEADER_PATH = os.path.join(HERE, "..", "include", "coevo.h")
+EXT_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_ext.h")   # additions that are not yet part of the pinned ABI
 
 
 class CoevoError(RuntimeError):
@@ -55,13 +56,15 @@ def _declare(text, structs, decl, spec=None):
     return m.group(3), t, base
 
 
-def parse_header(text, mirror=lambda name, fields: type(name, (C.Structure,), {"_fields_": fields})):
+def parse_header(text, mirror=lambda name, fields: type(name, (C.Structure,), {"_fields_": fields}), known=None):
     """the text of include/coevo.h -> ({COEVO_X: int}, {struct name: ctypes.Structure class}, {entry point: (restype,
     [argtypes])}).  The grammar is the header's, not C's: comments, ``#define NAME`` + a decimal or hex literal, a
     parenthesised negative or a product of earlier names, ``typedef struct [tag] { fields } name;`` and prototypes.  Whatever
-    does not fit raises CoevoError with the declaration quoted; nothing is guessed.  mirror(name, fields) makes a struct's class."""
+    does not fit raises CoevoError with the declaration quoted; nothing is guessed.  mirror(name, fields) makes a struct's class.
+    `known`: the structs of a header this one includes (its ``#include "coevo.h"`` line is skipped), usable in its prototypes."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    consts, structs, sigs = {}, {}, {}
+    text = re.sub(r'^[ \t]*#[ \t]*include[ \t]+"coevo\.h"[ \t]*$', "", text, flags=re.M)   # the extension header builds on coevo.h
+    consts, structs, sigs = {}, dict(known or {}), {}
     for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(.*)$", text, flags=re.M):
         v = value.strip()
         v = v[1:-1].strip() if v.startswith("(") and v.endswith(")") else v
@@ -117,15 +120,28 @@ def _mirror(name, fields):
     return PCG64State
 
 
-def _header_text():
+def _header_text(path=None):
+    path = HEADER_PATH if path is None else path
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return f.read()
     except OSError as e:
-        raise CoevoError(f"{HEADER_PATH} is missing: the binding is derived from the header ({e})") from e
+        raise CoevoError(f"{path} is missing: the binding is derived from the header ({e})") from e
 
 
 K, STRUCTS, _SIGS = parse_header(_header_text(), _mirror)
+
+
+def _parse_ext_header(text):
+    """include/coevo_ext.h -> (its constants, its entry points): the reader of coevo.h, which has seen coevo.h's structs; the
+    extension header declares prototypes and constants only, and no name coevo.h declares"""
+    consts, structs, sigs = parse_header(text, known=STRUCTS)
+    if set(structs) != set(STRUCTS) or set(sigs) & set(_SIGS) or set(consts) & set(K):
+        raise CoevoError("include/coevo_ext.h: declares a struct or repeats a name of include/coevo.h")
+    return consts, sigs
+
+
+K_EXT, _EXT_SIGS = _parse_ext_header(_header_text(EXT_HEADER_PATH))
 
 OBS_STRIDE, LOGIT_STRIDE, FC_MAX_ROWS = K["COEVO_OBS_STRIDE"], K["COEVO_LOGIT_STRIDE"], K["COEVO_FC_MAX_ROWS"]
 MPE_STATE_DOUBLES, STAMP_SLOTS = K["COEVO_MPE_STATE_DOUBLES"], K["COEVO_STAMP_SLOTS"]
@@ -180,6 +196,11 @@ def exported_symbols():
     return sorted(_SIGS)
 
 
+def extension_symbols():
+    """the entry points of include/coevo_ext.h, bound by load() beside the pinned ABI's"""
+    return sorted(_EXT_SIGS)
+
+
 def load():
     """dlopen libcoevo.so; raises CoevoError when it has not been built (python -m coevonet_amd.build)."""
     global _lib
@@ -188,7 +209,7 @@ def load():
             raise CoevoError(f"{LIB_PATH} is missing: build the HIP extension first "
                              "(python -m coevonet_amd.build); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in {**_SIGS, **_EXT_SIGS}.items():
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
