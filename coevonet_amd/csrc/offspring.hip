@@ -16,33 +16,164 @@
 
 namespace coevo {
 
-// Standard normals for the four slab positions s0..s0+3 (s0 % 4 == 0).  Everywhere except W1t the four positions
-// map to four consecutive canonical indices inside one Philox block, so one block serves them; W1t (3.7 % of a
-// net) pays one block per element.
-__device__ inline void slab_quad_normals(uint64_t seed, uint32_t slo, uint32_t shi, int64_t s0, int D, int64_t P,
-                                         float z[4])
+// Standard normals of the noise contract at slab positions.  Only fc1.weight is stored against the canonical order (W1t,
+// transposed); everywhere else the four positions of a 16-byte piece are one canonical quad = one Philox block.  All index
+// math is 32-bit (a net is < 2^18 floats).
+//
+// canonical quad of the W2q piece at slab position s0 (o_w2 <= s0 < o_b2, s0 % 4 == 0): W2q[jb][kq][l][0..3] are
+// fc2.w[64 jb + l][4 kq .. 4 kq + 3]
+__device__ __forceinline__ uint32_t w2_piece_quad(int32_t s0, int32_t o_w2)
 {
-    int64_t p[4];
+    const int32_t t = s0 - o_w2;
+    const int32_t l = (t >> 2) & 63, kq = (t >> 8) & 127, jb = t >> 15;
+    return (uint32_t)((o_w2 + (jb * 64 + l) * H1 + kq * 4) >> 2);
+}
+
+// W1t slab position of canonical index p < D * 512: fc1.w[j][k] (p = j D + k) lies at W1t[k][j]
+__device__ __forceinline__ int32_t w1t_slab_of_flat(uint32_t p, int D)
+{
+    const uint32_t j = (D == 8) ? (p >> 3) : (p / 10u);   // fc_dim_ok: D is 8 or 10
+    return (int32_t)((p - j * (uint32_t)D) * H1 + j);
+}
+
+// the piece at s0 (s0 % 4 == 0, s0 < fc_stride(D)); z = 0 at padding words (s >= fc_params(D)), where a piece that is all
+// padding costs no Philox block.  A W1t piece is four canonical quads of which it uses one normal each: whoever writes
+// whole W1t rows goes through w1t_normals_to_lds instead (fc_perturb_block); the rebuild kernels' W1t pieces pass here.
+__device__ inline void slab_quad_normals(uint64_t seed, uint32_t slo, uint32_t shi, int32_t s0, int D, float z[4])
+{
+    const int32_t o_b1 = (int32_t)fc_off_b1(D), o_w2 = (int32_t)fc_off_w2(D), o_b2 = (int32_t)fc_off_b2(D);
+    const int32_t P = (int32_t)fc_params(D);
+    if (s0 >= o_w2 && s0 < o_b2) {
+        philox_normal4(seed, slo, shi, w2_piece_quad(s0, o_w2), z);
+    } else if (s0 >= o_b1) {   // b1 g1 be1 | b2 g2 be2 W3 b3 | padding: slab position = canonical index
+        if (s0 < P) {
+            philox_normal4(seed, slo, shi, (uint32_t)s0 >> 2, z);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) p[i] = (s0 + i < P) ? fc_slab_to_flat(s0 + i, D) : -1;
-    float zz[4];
-    int64_t have = -1;
+            for (int i = 1; i < 4; ++i) z[i] = (s0 + i < P) ? z[i] : 0.0f;
+        } else {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (p[i] < 0) { z[i] = 0.0f; continue; }
-        const int64_t q = p[i] >> 2;
-        if (q != have) { philox_normal4(seed, slo, shi, (uint32_t)q, zz); have = q; }
-        z[i] = zz[p[i] & 3];
+            for (int i = 0; i < 4; ++i) z[i] = 0.0f;
+        }
+    } else {
+        const uint32_t k = (uint32_t)s0 >> 9, j = (uint32_t)s0 & (H1 - 1);   // W1t[k][j .. j + 3]
+        // (one copy of the generator, four trips: unrolled, the four interleaved generators cost ga_promote_kernel a wave of
+        // occupancy)
+        z[0] = z[1] = z[2] = z[3] = 0.0f;
+#pragma unroll 1
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t p = (j + i) * (uint32_t)D + k;
+            float zz[4];
+            philox_normal4(seed, slo, shi, p >> 2, zz);
+            const float v = zz[p & 3];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) z[m] = (m == i) ? v : z[m];
+        }
     }
 }
 
-// one workgroup's 1024 slab positions of child c (block bx of nblocks); shared by the single- and the multi-role launch
+constexpr int W1T_MAX_FLOATS = 10 * H1;   // W1t of the widest net (D = 10): 20 KiB of LDS
+// The whole W1t region's normals by canonical quad: the workgroup's 256 threads run the D * 128 Philox blocks of fc1.weight
+// once each (D / 2 per thread) and drop every normal at its slab position in `lds` ([D][512], the region's own layout).
+// Ends with a barrier.
+__device__ __forceinline__ void w1t_normals_to_lds(uint64_t seed, uint32_t slo, uint32_t shi, int D, float *lds)
+{
+    for (uint32_t q = threadIdx.x; q < (uint32_t)D * (H1 / 4); q += 256) {   // D * 128 is a multiple of 256
+        float zz[4];
+        philox_normal4(seed, slo, shi, q, zz);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lds[w1t_slab_of_flat(4 * q + i, D)] = zz[i];   // at D = 10 a quad straddles two rows j
+    }
+    __syncthreads();
+}
+
+// out = in + sigma * z (-: the odd partner of an antithetic pair) where not kept, stored at ch + s0; returns the piece's share
+// of the squared distance to the reference net, 0 without one
+__device__ __forceinline__ double perturb_apply_piece(float4 pv, const float z[4], const bool keep[4], const bool in_dist[4],
+                                                      float sigma, bool negate, float *ch, const float *dist_ref, int32_t s0)
+{
+    const float in[4] = {pv.x, pv.y, pv.z, pv.w};
+    float out[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float noise = sigma * z[i];  // rounded first, then added (agent.py:28-29)
+        out[i] = keep[i] ? in[i] : in[i] + (negate ? -noise : noise);
+    }
+    *reinterpret_cast<float4 *>(ch + s0) = make_float4(out[0], out[1], out[2], out[3]);
+    double d2 = 0.0;
+    if (dist_ref) {  // fitness-sharing distance of the new child to a reference net, while it is in registers
+        const float4 rv = *reinterpret_cast<const float4 *>(dist_ref + s0);
+        const float ref[4] = {rv.x, rv.y, rv.z, rv.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (in_dist[i]) {
+                const float d = out[i] - ref[i];
+                d2 += (double)d * (double)d;
+            }
+        }
+    }
+    return d2;
+}
+
+// ---- the fp64 block reduction of the fused distance, in the vector ALU
+template <int CTRL>
+__device__ __forceinline__ double dpp_move_f64(double v)
+{
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+template <bool ROW32>
+__device__ __forceinline__ double add_swap_f64(double v)   // v + v[lane ^ 16] (or ^ 32), as add_xor16 / add_xor32
+{
+    typedef unsigned u32x2_h __attribute__((ext_vector_type(2)));
+    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+    const u32x2_h l = ROW32 ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false)
+                            : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const u32x2_h h = ROW32 ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false)
+                            : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
+}
+
+// block_sum_f64 (same order of additions: lane xor 1, 2, 4, 8, 16, 32, then the four waves left to right) with the exchanges
+// of the fp32 tree sums in coevo_common.hip.h - DPP and lane swaps in the vector ALU instead of twelve ds_bpermute - and ONE
+// barrier: consecutive calls of a workgroup alternate between two scratch areas of four doubles (the barrier of call n + 1
+// lies between the reads of call n and the writes of call n + 2).  fp64 addition commutes: the same bits.
+__device__ __forceinline__ double breed_block_sum(double v, double *scratch)
+{
+    v = v + dpp_move_f64<0xB1>(v);    // quad_perm [1,0,3,2]
+    v = v + dpp_move_f64<0x4E>(v);    // quad_perm [2,3,0,1]
+    v = v + dpp_move_f64<0x141>(v);   // row_half_mirror
+    v = v + dpp_move_f64<0x140>(v);   // row_mirror
+    v = add_swap_f64<false>(v);
+    v = add_swap_f64<true>(v);
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
+}
+
+// how many of the blocks that lie in W2 as a whole one workgroup takes, straight-line: the prologue and the generator's
+// constants are paid once, the generators interleave.  2 and 4 measured alike (profiles/r24_breeding_regions.md)
+#ifndef COEVO_BREED_U
+#define COEVO_BREED_U 2
+#endif
+
+// LDS of a breeding workgroup: the W1t region's normals; its first 64 bytes double as the block reductions' scratch
+// (two areas of four doubles)
+struct alignas(16) PerturbLds { float z[W1T_MAX_FLOATS]; };
+
+// one workgroup's 1024 slab positions of child c (block bx of nblocks); shared by the single- and the multi-role launch.
+// Workgroup 0 of a child owns the whole W1t region (blocks 0 .. D/2 - 1, one after the other: same thread per position,
+// one block reduction per block); the workgroups of blocks 1 .. D/2 - 1 leave at once.  Likewise every COEVO_BREED_U-th
+// workgroup of the blocks that lie in W2 as a whole takes COEVO_BREED_U of them and the ones between leave at once.  The grid
+// and dist_partial[(child, block)] stay what coevo_fc_perturb_blocks says.
 __device__ __forceinline__ void fc_perturb_block(const float *parent_slab, const int32_t *parent_idx, float *child_slab,
                                                  int child_first, int D, const float *sigma_dev, uint64_t seed,
                                                  uint32_t stream_lo_first, uint32_t stream_hi, int skip_layernorm,
                                                  const int32_t *gen_dev, const float *dist_ref, double *dist_partial,
-                                                 int c, int bx, int nblocks, double *scratch)
+                                                 int c, int bx, int nblocks, PerturbLds &lds)
 {
+    const int w1t_blocks = D / 2;   // D * 512 / 1024
+    if (bx > 0 && bx < w1t_blocks) return;   // workgroup-uniform
     if (gen_dev) stream_hi += 4u * (uint32_t)(*gen_dev);  // generation-indexed noise stream without a host argument
     // flags: bit 0 = leave LayerNorm affine untouched (ES), bit 1 = antithetic pairs (extension mode): individuals 2m and
     // 2m+1 share noise stream m, the odd one takes -eps
@@ -51,57 +182,92 @@ __device__ __forceinline__ void fc_perturb_block(const float *parent_slab, const
     const uint32_t ind = stream_lo_first + (uint32_t)c;
     const uint32_t slo = antithetic ? (ind >> 1) : ind;
     const bool negate = antithetic && (ind & 1u);
-    const int64_t stride = fc_stride(D), P = fc_params(D);
-    const int64_t s0 = quad_first(bx);
+    const int64_t stride = fc_stride(D);
+    const float sigma = *sigma_dev;
+    const float *par = parent_slab + (int64_t)parent_idx[c] * stride;
+    float *ch = child_slab + (int64_t)(child_first + c) * stride;
+    double *scratch = reinterpret_cast<double *>(lds.z);
+    if (bx == 0) {
+        w1t_normals_to_lds(seed, slo, stream_hi, D, lds.z);
+        const float4 *zl = reinterpret_cast<const float4 *>(lds.z);
+        float4 zv = zl[threadIdx.x];
+        __syncthreads();   // block 0's normals are in registers: its first words are the reductions' scratch from here on
+        const bool keep[4] = {false, false, false, false}, in_dist[4] = {true, true, true, true};   // W1t: no LayerNorm, no padding
+        for (int b = 0; b < w1t_blocks; ++b) {
+            const int32_t s0 = (b * 256 + (int32_t)threadIdx.x) * 4;
+            const float4 pv = *reinterpret_cast<const float4 *>(par + s0);
+            const float z[4] = {zv.x, zv.y, zv.z, zv.w};
+            const double d2 = perturb_apply_piece(pv, z, keep, in_dist, sigma, negate, ch, dist_ref, s0);
+            if (b + 1 < w1t_blocks) zv = zl[(b + 1) * 256 + threadIdx.x];
+            if (dist_partial) {  // workgroup-uniform
+                const double tot = breed_block_sum(d2, scratch + 4 * (b & 1));
+                if (threadIdx.x == 0) dist_partial[(size_t)c * nblocks + b] = tot;
+            }
+        }
+        return;
+    }
+#if COEVO_BREED_U > 1
+    {
+        const int32_t o_w2 = (int32_t)fc_off_w2(D), o_b2 = (int32_t)fc_off_b2(D);
+        const int w2_first = (o_w2 + 1023) >> 10, w2_end = o_b2 >> 10;
+        if (bx >= w2_first && bx < w2_end) {
+            if ((bx - w2_first) % COEVO_BREED_U) return;   // workgroup-uniform
+            const int run = min(COEVO_BREED_U, w2_end - bx);
+            const bool keep[4] = {false, false, false, false}, in_dist[4] = {true, true, true, true};
+            double d2u[COEVO_BREED_U];
+#pragma unroll
+            for (int u = 0; u < COEVO_BREED_U; ++u) {
+                d2u[u] = 0.0;
+                if (u < run) {
+                    const int32_t s0 = ((bx + u) * 256 + (int32_t)threadIdx.x) * 4;
+                    const float4 pv = *reinterpret_cast<const float4 *>(par + s0);
+                    float z[4];
+                    philox_normal4(seed, slo, stream_hi, w2_piece_quad(s0, o_w2), z);
+                    d2u[u] = perturb_apply_piece(pv, z, keep, in_dist, sigma, negate, ch, dist_ref, s0);
+                }
+            }
+            if (dist_partial) {
+#pragma unroll
+                for (int u = 0; u < COEVO_BREED_U; ++u) {
+                    if (u < run) {
+                        const double tot = breed_block_sum(d2u[u], scratch + 4 * (u & 1));
+                        if (threadIdx.x == 0) dist_partial[(size_t)c * nblocks + bx + u] = tot;
+                    }
+                }
+            }
+            return;
+        }
+    }
+#endif
+    const int32_t s0 = (bx * 256 + (int32_t)threadIdx.x) * 4;
     double d2 = 0.0;
-    if (s0 < stride) {
-        const float sigma = *sigma_dev;
-        const float *par = parent_slab + (int64_t)parent_idx[c] * stride;
-        float *ch = child_slab + (int64_t)(child_first + c) * stride;
+    if (s0 < (int32_t)stride) {
         const float4 pv = *reinterpret_cast<const float4 *>(par + s0);
         float z[4];
         bool keep[4], in_dist[4];
-        const int32_t o_w2 = (int32_t)fc_off_w2(D), o_b2 = (int32_t)fc_off_b2(D), s32 = (int32_t)s0;
-        if (s32 >= o_w2 && s32 < o_b2) {
-            // fc2 block (93.8 % of a net): W2q[jb][kq][l][0..3] are the four consecutive canonical indices
-            // fc2.w[64*jb + l][4*kq .. 4*kq+3], one Philox block, never LayerNorm, never padding - 32-bit index math
-            const int32_t t = s32 - o_w2;
-            const int32_t l = (t >> 2) & 63, kq = (t >> 8) & 127, jb = t >> 15;
-            const int32_t p0 = o_w2 + (jb * 64 + l) * H1 + kq * 4;  // multiple of 4
-            philox_normal4(seed, slo, stream_hi, (uint32_t)(p0 >> 2), z);
+        const int32_t o_w2 = (int32_t)fc_off_w2(D), o_b2 = (int32_t)fc_off_b2(D);
+        if (s0 >= o_w2 && s0 < o_b2) {
+            // fc2 block (93.8 % of a net): one Philox block, never LayerNorm, never padding
+            philox_normal4(seed, slo, stream_hi, w2_piece_quad(s0, o_w2), z);
 #pragma unroll
             for (int i = 0; i < 4; ++i) { keep[i] = false; in_dist[i] = true; }
         } else {
-            slab_quad_normals(seed, slo, stream_hi, s0, D, P, z);
+            // b1 g1 be1 | b2 g2 be2 W3 b3 | padding: every region edge but the last parameter is a multiple of 4, so a piece
+            // is LayerNorm or not as a whole
+            slab_quad_normals(seed, slo, stream_hi, s0, D, z);
+            const int32_t g1 = (int32_t)fc_off_g1(D), g2 = (int32_t)fc_off_g2(D), P = (int32_t)fc_params(D);
+            const bool ln = (s0 >= g1 && s0 < g1 + 2 * H1) || (s0 >= g2 && s0 < g2 + 2 * H2);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int64_t s = s0 + i;
-                const bool ln = fc_slab_is_layernorm(s, D);
-                keep[i] = (s >= P) || (skip_layernorm && ln);
-                in_dist[i] = s < P && !ln;
+                const bool pad = s0 + i >= P;
+                keep[i] = pad || (skip_layernorm && ln);
+                in_dist[i] = !pad && !ln;
             }
         }
-        float in[4] = {pv.x, pv.y, pv.z, pv.w}, out[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float noise = sigma * z[i];  // rounded first, then added (agent.py:28-29)
-            out[i] = keep[i] ? in[i] : in[i] + (negate ? -noise : noise);
-        }
-        *reinterpret_cast<float4 *>(ch + s0) = make_float4(out[0], out[1], out[2], out[3]);
-        if (dist_partial) {  // fitness-sharing distance of the new child to a reference net, while it is in registers
-            const float4 rv = *reinterpret_cast<const float4 *>(dist_ref + s0);
-            const float ref[4] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (in_dist[i]) {
-                    const float d = out[i] - ref[i];
-                    d2 += (double)d * (double)d;
-                }
-            }
-        }
+        d2 = perturb_apply_piece(pv, z, keep, in_dist, sigma, negate, ch, dist_ref, s0);
     }
     if (dist_partial) {  // wave-uniform
-        const double tot = block_sum_f64(d2, scratch);
+        const double tot = breed_block_sum(d2, scratch);
         if (threadIdx.x == 0) dist_partial[(size_t)c * nblocks + bx] = tot;
     }
 }
@@ -113,9 +279,9 @@ __global__ __launch_bounds__(256) void fc_perturb_kernel(const float *parent_sla
                                                           int skip_layernorm, const int32_t *gen_dev,
                                                           const float *dist_ref, double *dist_partial)
 {
-    __shared__ double scratch[4];
+    __shared__ PerturbLds lds;
     fc_perturb_block(parent_slab, parent_idx, child_slab, child_first, D, sigma_dev, seed, stream_lo_first, stream_hi,
-                     skip_layernorm, gen_dev, dist_ref, dist_partial, blockIdx.y, blockIdx.x, gridDim.x, scratch);
+                     skip_layernorm, gen_dev, dist_ref, dist_partial, blockIdx.y, blockIdx.x, gridDim.x, lds);
 }
 
 static_assert(sizeof(coevo_fc_perturb_job) == 72, "layout mirrored by coevonet_amd/lib.py PerturbJob");
@@ -124,13 +290,13 @@ struct PerturbJobs { coevo_fc_perturb_job j[COEVO_MAX_JOBS]; };
 __global__ __launch_bounds__(256) void fc_perturb_multi_kernel(PerturbJobs jobs, uint64_t seed, int skip_layernorm,
                                                                 const int32_t *gen_dev)
 {
-    __shared__ double scratch[4];
+    __shared__ PerturbLds lds;
     const coevo_fc_perturb_job &jb = jobs.j[blockIdx.z];
     const int nblocks = (int)quad_blocks(fc_stride(jb.D));
     if ((int)blockIdx.x >= nblocks || (int)blockIdx.y >= jb.n_children) return;   // workgroup-uniform
     fc_perturb_block(jb.parent_slab, jb.parent_idx, jb.child_slab, jb.child_first, jb.D, jb.sigma_dev, seed,
                      jb.stream_lo_first, jb.stream_hi, skip_layernorm, gen_dev, jb.dist_ref, jb.dist_partial, blockIdx.y,
-                     blockIdx.x, nblocks, scratch);
+                     blockIdx.x, nblocks, lds);
 }
 
 // New elites without gathering them from whichever GPU evaluated them: elite e of this generation is individual
@@ -158,7 +324,7 @@ __global__ __launch_bounds__(256) void fc_rebuild_elites_kernel(const float *eli
     const float sigma = *sigma_prev_dev;
     const float4 pv = *reinterpret_cast<const float4 *>(elite_prev + (int64_t)(c % E) * stride + s0);
     float z[4];
-    slab_quad_normals(seed, (uint32_t)c, stream_hi_prev, s0, D, P, z);
+    slab_quad_normals(seed, (uint32_t)c, stream_hi_prev, (int32_t)s0, D, z);
     const float in[4] = {pv.x, pv.y, pv.z, pv.w};
     float out[4];
 #pragma unroll
@@ -241,7 +407,7 @@ __device__ __forceinline__ float4 promote_rebuild(float *elite, const int32_t *o
         if (id > 0 && K < E) {   // (a surplus level re-stores slot E - 1 with the piece it loaded; level E - 1 overwrites it after)
             const int64_t P = fc_params(D);
             float z[4];
-            slab_quad_normals(seed, (uint32_t)c, shi, s0, D, P, z);
+            slab_quad_normals(seed, (uint32_t)c, shi, (int32_t)s0, D, z);
             const float in[4] = {pv.x, pv.y, pv.z, pv.w};
             float out[4];
 #pragma unroll
