@@ -25,7 +25,8 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 # So: export it yourself for a process that runs the host-cores mode after a graph-replaying mode and is short-lived, or do
 # what bench.py does - run the host-cores mode in a process of its own.
 
-__all__ = ["HalfGAEngine", "HalfESEngine", "DeepQNHalf", "HalfDQNGAEngine", "HalfSynthRollout", "HalfDQNESEngine"]
+__all__ = ["HalfGAEngine", "HalfESEngine", "DeepQNHalf", "HalfDQNGAEngine", "HalfSynthRollout", "HalfDQNESEngine",
+           "CrossPlay", "DQNCrossPlay", "test_agents", "cross_play_checkpoints"]
 
 
 def __getattr__(name):
@@ -45,4 +46,7 @@ def __getattr__(name):
     if name == "HalfDQNESEngine":
         from .dqn_es_half import HalfDQNESEngine
         return HalfDQNESEngine
+    if name in ("CrossPlay", "DQNCrossPlay", "test_agents", "cross_play_checkpoints"):
+        from . import crossplay
+        return getattr(crossplay, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -16,6 +16,8 @@
 //   22     goal index, 23 spare
 #include "coevo_common.hip.h"
 
+#include "../../include/coevo_crossplay.h"
+
 namespace coevo {
 
 typedef unsigned __int128 u128;
@@ -66,6 +68,16 @@ __global__ void mpe_reset_kernel(double *st, int n, int game_first, int count, c
     int64_t first = first_ordinal + (gen_dev ? (int64_t)(*gen_dev) * ordinals_per_gen : 0);
     if (first < 0 && !unsigned_first) first = 0;  // a batch that is disabled in this generation (e.g. no previous evaluation yet)
     mpe_reset_game(st, n, game_first + i, rng, (uint64_t)first + (uint64_t)i);
+}
+
+// coevo_mpe_reset_episodes (include/coevo_crossplay.h): the ordinal repeats with period `episodes`, so every trio of a
+// cross-play (E consecutive games) meets the same E initial worlds
+__global__ void mpe_reset_episodes_kernel(double *st, int n, int game_first, int count, coevo_pcg64 rng,
+                                          uint64_t first_ordinal, int episodes)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    mpe_reset_game(st, n, game_first + i, rng, first_ordinal + (uint64_t)(i % episodes));
 }
 
 static_assert(sizeof(coevo_reset_seg) == 16, "layout mirrored by coevonet_amd/lib.py ResetSeg");
@@ -315,6 +327,19 @@ extern "C" int coevo_mpe_reset(double *state, int n_games, int game_first, int c
     hipLaunchKernelGGL(coevo::mpe_reset_kernel, dim3((count + 127) / 128), dim3(128), 0, (hipStream_t)stream,
                        state, n_games, game_first, count, rng, (int64_t)first_ordinal, (const int32_t *)nullptr,
                        (int64_t)0, 1);
+    COEVO_HIP_CHECK(hipGetLastError());
+    return COEVO_OK;
+}
+
+extern "C" int coevo_mpe_reset_episodes(double *state, int n_games, int game_first, int count, coevo_pcg64 rng,
+                                        uint64_t first_ordinal, int episodes, void *stream)
+{
+    if (!state || n_games <= 0 || game_first < 0 || count < 0 || game_first > n_games || count > n_games - game_first ||
+        episodes <= 0)
+        return COEVO_ERR_ARG;
+    if (count == 0) return COEVO_OK;
+    hipLaunchKernelGGL(coevo::mpe_reset_episodes_kernel, dim3((count + 127) / 128), dim3(128), 0, (hipStream_t)stream,
+                       state, n_games, game_first, count, rng, first_ordinal, episodes);
     COEVO_HIP_CHECK(hipGetLastError());
     return COEVO_OK;
 }

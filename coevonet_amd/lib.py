@@ -20,6 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COEVO_LIB") or os.path.join(HERE, "libcoevo.so")  # COEVO_LIB: A/B builds
 HEADER_PATH = os.path.join(HERE, "..", "include", "coevo.h")
 EXT_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_ext.h")   # additions that are not yet part of the pinned ABI
+CROSSPLAY_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_crossplay.h")   # the cross-play entry points, likewise
 
 
 class CoevoError(RuntimeError):
@@ -143,6 +144,18 @@ def _parse_ext_header(text):
 
 K_EXT, _EXT_SIGS = _parse_ext_header(_header_text(EXT_HEADER_PATH))
 
+
+def _parse_crossplay_header(text):
+    """include/coevo_crossplay.h -> (its constants, its entry points), read like coevo_ext.h: prototypes and constants only, and
+    no name that coevo.h or coevo_ext.h declares"""
+    consts, structs, sigs = parse_header(text, known=STRUCTS)
+    if set(structs) != set(STRUCTS) or set(sigs) & (set(_SIGS) | set(_EXT_SIGS)) or set(consts) & (set(K) | set(K_EXT)):
+        raise CoevoError("include/coevo_crossplay.h: declares a struct or repeats a name of include/coevo.h or include/coevo_ext.h")
+    return consts, sigs
+
+
+K_XP, _XP_SIGS = _parse_crossplay_header(_header_text(CROSSPLAY_HEADER_PATH))
+
 OBS_STRIDE, LOGIT_STRIDE, FC_MAX_ROWS = K["COEVO_OBS_STRIDE"], K["COEVO_LOGIT_STRIDE"], K["COEVO_FC_MAX_ROWS"]
 MPE_STATE_DOUBLES, STAMP_SLOTS = K["COEVO_MPE_STATE_DOUBLES"], K["COEVO_STAMP_SLOTS"]
 ST_NAMES = {K["COEVO_ST_BAD_INPUT"]: "input contains inf or NaN",
@@ -201,6 +214,11 @@ def extension_symbols():
     return sorted(_EXT_SIGS)
 
 
+def crossplay_symbols():
+    """the entry points of include/coevo_crossplay.h, bound by load() beside the two other tables"""
+    return sorted(_XP_SIGS)
+
+
 def load():
     """dlopen libcoevo.so; raises CoevoError when it has not been built (python -m coevonet_amd.build)."""
     global _lib
@@ -209,7 +227,7 @@ def load():
             raise CoevoError(f"{LIB_PATH} is missing: build the HIP extension first "
                              "(python -m coevonet_amd.build); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_EXT_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_EXT_SIGS, **_XP_SIGS}.items():
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -5,7 +5,8 @@ Co-GA generation tail of the fully connected engines, the Co-ES update of the fl
 GAEngine / HalfGAEngine (genetic_algorithm.py, ga_half.py), ESEngine / HalfESEngine (evolutionary_strategy.py, es_half.py)
 and DQNGAEngine / HalfDQNGAEngine / DQNESEngine (dqn_population.py, dqn_ga_half.py) differ in precision, strides and kernels,
 not in who plays whom: the seat rules of the reference's generation bodies are written ONCE, here.  slab_layout, NetTable,
-co_ga_games, co_ga_games2, co_es_games, co_es_games2, mean_eval, eval_gate_limits and the sigma rule are plain python - they
+co_ga_games, co_ga_games2, co_es_games, co_es_games2, cross_games, cross_games2 (the game tables of crossplay.py), mean_eval,
+eval_gate_limits and the sigma rule are plain python - they
 touch neither torch nor the library, which this module imports for captured() and the mixins only - and are pinned by
 tests/test_population_cpu.py; the mixins hold the calls the engines made identically (tests/test_ga_launch_scripts_cpu.py,
 tests/test_es_launch_scripts_cpu.py: recorded before they were shared).
@@ -132,6 +133,33 @@ def co_es_games2(net, lo, hi, first_ordinal, pop):
             games.append((me, base[1]) if ri == 0 else (base[0], me))
             ordinal0.append(first_ordinal + 2 * j + ri)
     return games, ordinal0, [tuple(base)] * N_EVAL, [first_ordinal + 2 * pop + j for j in range(N_EVAL)]
+
+
+def cross_games(net, A, B, C, E):
+    """A cross-play of A agent_0 x B agent_1 x C adversary nets, E episodes per trio -> (games as (adversary, agent_0, agent_1)
+    net ids, episode of each game): game ((a B + b) C + c) E + e seats (adversary c, agent_0 a, agent_1 b) in episode e.  The
+    reset ordinal of a game is first_ordinal + its episode: every trio meets the same E initial worlds."""
+    games, episode = [], []
+    for a in range(A):
+        for b in range(B):
+            for c in range(C):
+                seat = (net("cross", "adversary_0", c), net("cross", "agent_0", a), net("cross", "agent_1", b))
+                for e in range(E):
+                    games.append(seat)
+                    episode.append(e)
+    return games, episode
+
+
+def cross_games2(net, A, B, E):
+    """The two-player twin: game (a B + b) E + e seats (first_0 a, second_0 b) in episode e -> (games, episode of each game)"""
+    games, episode = [], []
+    for a in range(A):
+        for b in range(B):
+            seat = (net("cross", "first_0", a), net("cross", "second_0", b))
+            for e in range(E):
+                games.append(seat)
+                episode.append(e)
+    return games, episode
 
 
 def mean_eval(rewards, n_slots):
