@@ -371,6 +371,33 @@ __device__ inline double block_sum_f64(double v, double *scratch)
     return tot;
 }
 
+// The sharing arithmetic on n distances, by one workgroup of 256 threads: sum_i max(0, 1 - d_i / mean(d)), the mean rounded to
+// fp32 as np.mean of an fp32 array is.  np.maximum propagates NaN: a NaN share (mean 0, a NaN distance, inf / inf) makes the
+// total NaN - hence !(sh <= 0), which a NaN passes, not sh > 0.  dist_of(i) -> float; every thread returns the total, which the
+// caller rounds to fp32.  Written once for the score against one agent (sharing_score_kernel, ga_select_kernel) and the niche
+// count of a row of pairwise distances (niche_counts_kernel).
+template <class DistOf>
+__device__ inline double sharing_row_total(DistOf dist_of, int n, double *scratch)
+{
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += (double)dist_of(i);
+    const float sigma = (float)(block_sum_f64(s, scratch) / (double)n);
+    double sc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const float sh = 1.0f - dist_of(i) / sigma;
+        if (!(sh <= 0.0f)) sc += (double)sh;
+    }
+    return block_sum_f64(sc, scratch);
+}
+
+// The GA fitness of one individual from its reward (the last Hall-of-Fame game's, quirk Q2, or the sum over all of them): still
+// divided by hof_size and by (1 + share).  numpy >= 2 evaluates python_float / np.float32 in float32.
+__device__ inline float ga_fitness_value(double reward, int hof, float share)
+{
+    const float total = (float)(reward / (double)hof);
+    return total / (1.0f + share);
+}
+
 // the n_blocks fp64 partials of one net on ONE wavefront: lane-strided sums, then the xor tree (a fixed order); every lane
 // returns the total.  The caller rounds: (float)sqrt for fp32 nets, f16_of_f64(sqrt) for fp16 nets.
 __device__ __forceinline__ double wave_sum_partials(const double *partial, int n_blocks)

@@ -74,25 +74,16 @@ __global__ void gather_f32_kernel(float *dst, const float *src, const int32_t *i
     if (i < n) dst[i] = src[idx[i]];
 }
 
-// score = sum_i max(0, 1 - d_i / mean(d)), mean rounded to fp32 as np.mean of an fp32 array is.  np.maximum propagates NaN:
-// a NaN share (mean 0, a NaN distance, inf / inf) makes the score NaN - hence !(sh <= 0), which a NaN passes, not sh > 0.
+// score = sum_i max(0, 1 - d_i / mean(d)): sharing_row_total (coevo_common.hip.h) on the distances to one agent
 __global__ __launch_bounds__(256) void sharing_score_kernel(const float *dist, int n, float *score)
 {
     __shared__ double scratch[4];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) s += (double)dist[i];
-    const float sigma = (float)(block_sum_f64(s, scratch) / (double)n);
-    double sc = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float sh = 1.0f - dist[i] / sigma;
-        if (!(sh <= 0.0f)) sc += (double)sh;
-    }
-    const double tot = block_sum_f64(sc, scratch);
+    const double tot = sharing_row_total([&](int i) { return dist[i]; }, n, scratch);
     if (threadIdx.x == 0) *score = (float)tot;
 }
 
 // quirk Q2: the reward variable is overwritten by every HoF game, only the LAST one (k = hof-1) survives; it is
-// still divided by hof_size and by (1 + diversity).  numpy >= 2 evaluates python_float / np.float32 in float32.
+// still divided by hof_size and by (1 + diversity) (ga_fitness_value).
 __global__ void ga_fitness_kernel(const double *rewards, int game_first, int pop, int games_per_individual,
                                   int hof, int slot, const float *diversity, float *fitness)
 {
@@ -100,8 +91,7 @@ __global__ void ga_fitness_kernel(const double *rewards, int game_first, int pop
     if (i >= pop) return;
     const int gpi = games_per_individual;
     const double last = rewards[3 * (size_t)(game_first + i * gpi + gpi - 1) + slot];
-    const float total = (float)(last / (double)hof);
-    fitness[i] = total / (1.0f + *diversity);
+    fitness[i] = ga_fitness_value(last, hof, *diversity);
 }
 
 // order = argsort(fitness)[::-1] with a stable ascending sort (ties: higher index first after the reversal);
@@ -165,15 +155,7 @@ __global__ __launch_bounds__(256) void ga_select_kernel(GaSelectArgs a)
     };
     auto dist_of = [&](int i) { return a.gathered ? (float)rec(i)[3] : R.dist[i]; };
     // sharing score (sharing_score_kernel)
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) s += (double)dist_of(i);
-    const float sigma = (float)(block_sum_f64(s, scratch) / (double)n);
-    double sc = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float sh = 1.0f - dist_of(i) / sigma;
-        if (!(sh <= 0.0f)) sc += (double)sh;
-    }
-    const double tot = block_sum_f64(sc, scratch);
+    const double tot = sharing_row_total(dist_of, n, scratch);
     if (threadIdx.x == 0) {
         div_s = (float)tot;
         if (first_slice) *R.diversity = (float)tot;
@@ -183,8 +165,7 @@ __global__ __launch_bounds__(256) void ga_select_kernel(GaSelectArgs a)
     const int gpi = a.games_per_individual;
     for (int i = threadIdx.x; i < n; i += 256) {
         const double last = a.gathered ? rec(i)[R.slot] : R.rewards[3 * (size_t)(R.game_first + i * gpi + gpi - 1) + R.slot];
-        const float total = (float)(last / (double)a.hof);
-        const float fit = total / (1.0f + div_s);
+        const float fit = ga_fitness_value(last, a.hof, div_s);
         f[i] = fit;
         if (first_slice) R.fitness[i] = fit;
     }

@@ -35,8 +35,8 @@ from .fcnetwork import FCNetwork
 from .ga_half import HalfGAEngine
 from .game_logic import create_agent
 from .mpe.simple_adversary import ENV_SEED
-from .population import (N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, CoGASchedule, CoGATail, NetTable, SlabIO,
-                         adapt_mutation_power, captured, co_ga_games, eval_gate_limits, half_route, mean_eval_triple,
+from .population import (GA_SHARING_MODES, N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, CoGASchedule, CoGATail, NetTable,
+                         SlabIO, adapt_mutation_power, captured, co_ga_games, eval_gate_limits, half_route, mean_eval_triple,
                          shard_and_gather, slab_layout)
 from .rollout import DeviceRollout, HostEnvRollout, RolloutPlan, effective_steps
 
@@ -130,6 +130,21 @@ def resident_prefix(budget_bytes, fixed_bytes, individual_bytes, bounds):
     return np.minimum(sizes, int(left // (K * individual_bytes)))
 
 
+SHARING_MAX_POP = L.K_SH["COEVO_SHARING_MAX_POP"]
+
+
+def refuse_sharing_modes_on(pop, shard, rng, population_sharing):
+    """what GAEngine(hof_mean=..., population_sharing=...) does not cover, as a ValueError: a population shard, a population
+    past coevo_rank_desc's limit, and population sharing over the host's breeding (the mode is built for device-built
+    offspring; hof_mean alone runs over either)"""
+    if tuple(shard) != (0, 1):
+        raise ValueError(f"hof_mean / population_sharing run on one rank only, not shard {tuple(shard)}")
+    if pop > SHARING_MAX_POP:
+        raise ValueError(f"hof_mean / population_sharing rank at most {SHARING_MAX_POP} individuals, not {pop}")
+    if population_sharing and rng == "host_reference":
+        raise ValueError('population_sharing needs rng="device_philox", not "host_reference"')
+
+
 DEFAULT_COHORTS = 1       # independent game cohorts per rollout (rollout.RolloutPlan._assign_cohorts); see DESIGN.md
 DEVICE_LOOP_COHORTS = 2   # ... in the host-free loop, where their launches are enqueued eagerly and do overlap
 SMALL_SHARD = 80          # ... unless a rank holds fewer individuals per role than this: then one chain
@@ -143,8 +158,15 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
 
     def __init__(self, pop, hof, elites, limit_train=None, limit_eval=None, max_cycles=25, device="cuda",
                  env_seed=ENV_SEED, rng="device_philox", philox_seed=0, env="device", first_ordinal=1,
-                 shard=(0, 1), gather=None, timing_pairs=4096, cohorts=1, gather_packed=None):
+                 shard=(0, 1), gather=None, timing_pairs=4096, cohorts=1, gather_packed=None, hof_mean=False,
+                 population_sharing=False):
         assert 1 <= elites <= pop and hof >= 1
+        # the two extension modes (NOT the reference's algorithm): fitness over every Hall-of-Fame game instead of
+        # the last one (Q2), and sharing by a niche count per individual over all pairwise distances instead of one score
+        # against the stale agent (Q3).  Off: nothing changes.  Refused before the library is loaded.
+        self.hof_mean, self.population_sharing = bool(hof_mean), bool(population_sharing)
+        if self.hof_mean or self.population_sharing:
+            refuse_sharing_modes_on(pop, shard, rng, self.population_sharing)
         self.pop, self.hof, self.E = pop, hof, elites
         self.rng_mode, self.philox_seed, self.env_mode = rng, int(philox_seed), env
         self.device = device
@@ -249,6 +271,11 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         # the rollout's closing launch, and the all-gathered [rank][role][j][4] buffer the selection reads as it is
         self.pack_local = torch.zeros(3, self.n_local, 4, dtype=torch.float64, device=device)
         self.pack_all = torch.zeros(self.world, 3, self.n_local, 4, dtype=torch.float64, device=device)
+        if self.population_sharing:   # all pairwise distances [pop][pop] and the niche counts [pop] of every role
+            self.pair_dist = {r: torch.zeros(pop, pop, **f32) for r in ROLES}
+            self.niche = {r: torch.zeros(pop, **f32) for r in ROLES}
+            n_scratch = max(int(L.load().coevo_fc_pairwise_scratch_doubles(pop, ROLE_D[r])) for r in ROLES)
+            self.pair_scratch = torch.zeros(n_scratch, dtype=torch.float64, device=device)
         self.parent_idx = torch.tensor([c % elites for c in range(max(pop - 1, 1))], dtype=torch.int32, device=device)
         self.hof_shift_idx = torch.arange(1, max(hof, 2), dtype=torch.int32, device=device)
         self.iota = torch.arange(max(hof, elites, 2), dtype=torch.int32, device=device)
@@ -309,6 +336,9 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
             self._rewards_dev.copy_(self._rewards_pin, non_blocking=True)
             dev_rewards = self._rewards_dev
         per_phase = self.n_local * self.hof
+        if self.hof_mean or self.population_sharing:
+            self._select_shared(dev_rewards, per_phase)
+            return
         if self._fused_host_tail():
             self._ensure_breed_buffers()
             if not getattr(self, "_dist_current", False):   # (generation 0, or a population loaded from the host)
@@ -329,6 +359,35 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         if self.world > 1:
             self.gather(self)  # all-gather of dist[role][lo:hi] and last_reward[:, lo:hi]
         self._select_unfused(lambda ri: self.last_reward[ri].data_ptr(), lambda ri: 0, 1)
+
+    def _select_shared(self, dev_rewards, per_phase):
+        """select() under hof_mean / population_sharing (one rank, the whole population here), launch per step and role:
+        the share - niche counts over all pairwise distances, or today's score against the stale agent -, the fitness with
+        the mode's switches, the ranking, and the best individual's stale-agent distance, which breed_device's fused promotion
+        hands to the children's distances: the stale-agent chain stays valid in either mode"""
+        self._ensure_breed_buffers()
+        flags = ((L.K_SH["COEVO_FIT_HOF_MEAN"] if self.hof_mean else 0)
+                 | (L.K_SH["COEVO_FIT_PER_INDIVIDUAL"] if self.population_sharing else 0))
+        for ri, r in enumerate(ROLES):
+            D = ROLE_D[r]
+            if not getattr(self, "_dist_current", False):
+                L.call("coevo_fc_distance", self._ptr(r, "stale"), self._ptr(r, "pop"), self.pop, D, L._p(self.dist[r]))
+            if self.population_sharing:
+                L.call("coevo_fc_pairwise_distance", self._ptr(r, "pop"), self.pop, D, L._p(self.pair_scratch),
+                       L._p(self.pair_dist[r]))
+                L.call("coevo_niche_counts", L._p(self.pair_dist[r]), self.pop, L._p(self.niche[r]))
+                share = self.niche[r]
+            else:
+                L.call("coevo_sharing_score", L._p(self.dist[r]), self.pop, L._p(self.div[r]))
+                share = self.div[r]
+            L.call("coevo_ga_fitness_shared", L._p(dev_rewards), ri * per_phase, self.pop, self.hof, self.hof, RET_SLOT[r], flags,
+                   L._p(share), L._p(self.fitness[r]))
+            L.call("coevo_rank_desc", L._p(self.fitness[r]), self.pop, L._p(self.order[r]))
+            L.call("coevo_gather_f32", L._p(self.best_dist[r]), L._p(self.dist[r]), L._p(self.order[r]), 1)
+
+    def mean_niche(self):
+        """per role the fp64 mean of the niche counts, computed on the host (population_sharing)"""
+        return [float(np.mean(self.niche[r].cpu().numpy().astype(np.float64))) for r in ROLES]
 
     def breed_device(self, gen, sigmas):
         """elites -> elite buffer, HoF FIFO, population := [best] + (pop-1) mutated clones, all on the device.
@@ -769,9 +828,17 @@ class GATrainer:
 
     def __init__(self, env, args, rng=None, env_mode=None, collect=True, dist_ctx=None):
         # float16: rng "device_philox" + the device env on one rank, or a ValueError before anything else happens
-        self.half = half_route(args, "Co-GA training with precision", rng, env_mode, dist_ctx, "gather_ga")
+        self.half = half_route(args, "Co-GA training with precision", rng, env_mode, dist_ctx, "gather_ga",
+                               extensions=GA_SHARING_MODES)
         self.env, self.args, self.collect = env, args, collect
         self.rng = rng or getattr(args, "coevo_rng", "host_reference")
+        # the extension modes (GAEngine): the host-driven loop of step() on one rank, refused before anything is built
+        hof_mean = bool(getattr(args, "coevo_hof_mean", False))
+        population_sharing = bool(getattr(args, "coevo_population_sharing", False))
+        self.sharing_modes = hof_mean or population_sharing
+        shard, gather = shard_and_gather(dist_ctx, "gather_ga")
+        if self.sharing_modes:
+            refuse_sharing_modes_on(args.population, shard, self.rng, population_sharing)
         env_mode = env_mode or getattr(args, "coevo_env", "device")
         self.first_ordinal = getattr(env, "n_resets", 1)
         pop_flat, hof_flat = initial_population(env, args)   # (create_agent builds FCNetworkHalf under float16)
@@ -789,7 +856,6 @@ class GATrainer:
             self.eng.load_initial(pop_flat, hof_flat)
             self.res.engine = self.eng
             return
-        shard, gather = shard_and_gather(dist_ctx, "gather_ga")
         gather_packed = getattr(dist_ctx, "gather_ga_packed", None) if gather else None
         # the host-free generation loop needs device-built offspring, the device env and a single rank
         self.device_loop = (self.rng == "device_philox" and env_mode == "device" and shard == (0, 1)
@@ -801,6 +867,8 @@ class GATrainer:
                              and getattr(args, "coevo_device_loop", True))
         if self.sharded_loop:
             self.device_loop = False
+        if self.sharing_modes:   # (the host-free loops and their fused coevo_ga_select do not carry the modes)
+            self.device_loop = self.sharded_loop = False
         cohorts = getattr(args, "coevo_cohorts", None)
         if cohorts is None:
             cohorts = DEVICE_LOOP_COHORTS if (self.device_loop or self.sharded_loop) else DEFAULT_COHORTS
@@ -814,7 +882,8 @@ class GATrainer:
                             philox_seed=getattr(args, "coevo_seed", 0), env=env_mode,
                             first_ordinal=self.first_ordinal,
                             env_seed=getattr(env, "seed_value", ENV_SEED) or ENV_SEED, shard=shard, gather=gather,
-                            cohorts=int(cohorts), gather_packed=gather_packed)
+                            cohorts=int(cohorts), gather_packed=gather_packed, hof_mean=hof_mean,
+                            population_sharing=population_sharing)
         self.eng.load_initial(pop_flat, hof_flat)
         self.res.engine = self.eng
         if self.device_loop or self.sharded_loop:
@@ -862,7 +931,9 @@ class GATrainer:
         if self.collect:
             res.game_rewards.append(eng.rewards_host()[:eng.n_main].copy())
             res.fitness.append([eng.fitness[r].cpu().numpy().tolist() for r in ROLES])
-            res.diversity.append([float(eng.div[r].item()) for r in ROLES])
+            # (population sharing has no single score: per role the mean niche count)
+            res.diversity.append(eng.mean_niche() if getattr(eng, "population_sharing", False)
+                                 else [float(eng.div[r].item()) for r in ROLES])
             res.elite_ids.append([eng.elite_ids()[r] for r in ROLES])
         res.seconds.append(time.perf_counter() - t0)
         self.gen += 1

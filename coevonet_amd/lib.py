@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("COEVO_LIB") or os.path.join(HERE, "libcoevo.so")  # C
 HEADER_PATH = os.path.join(HERE, "..", "include", "coevo.h")
 EXT_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_ext.h")   # additions that are not yet part of the pinned ABI
 CROSSPLAY_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_crossplay.h")   # the cross-play entry points, likewise
+SHARING_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_sharing.h")   # the Co-GA population-sharing entry points, likewise
 
 
 class CoevoError(RuntimeError):
@@ -156,6 +157,20 @@ def _parse_crossplay_header(text):
 
 K_XP, _XP_SIGS = _parse_crossplay_header(_header_text(CROSSPLAY_HEADER_PATH))
 
+
+def _parse_sharing_header(text):
+    """include/coevo_sharing.h -> (its constants, its entry points), read like coevo_crossplay.h: prototypes and constants only,
+    and no name that one of the three other headers declares"""
+    consts, structs, sigs = parse_header(text, known=STRUCTS)
+    if (set(structs) != set(STRUCTS) or set(sigs) & (set(_SIGS) | set(_EXT_SIGS) | set(_XP_SIGS))
+            or set(consts) & (set(K) | set(K_EXT) | set(K_XP))):
+        raise CoevoError("include/coevo_sharing.h: declares a struct or repeats a name of include/coevo.h, include/coevo_ext.h "
+                         "or include/coevo_crossplay.h")
+    return consts, sigs
+
+
+K_SH, _SH_SIGS = _parse_sharing_header(_header_text(SHARING_HEADER_PATH))
+
 OBS_STRIDE, LOGIT_STRIDE, FC_MAX_ROWS = K["COEVO_OBS_STRIDE"], K["COEVO_LOGIT_STRIDE"], K["COEVO_FC_MAX_ROWS"]
 MPE_STATE_DOUBLES, STAMP_SLOTS = K["COEVO_MPE_STATE_DOUBLES"], K["COEVO_STAMP_SLOTS"]
 ST_NAMES = {K["COEVO_ST_BAD_INPUT"]: "input contains inf or NaN",
@@ -219,6 +234,11 @@ def crossplay_symbols():
     return sorted(_XP_SIGS)
 
 
+def sharing_symbols():
+    """the entry points of include/coevo_sharing.h, bound by load() beside the three other tables"""
+    return sorted(_SH_SIGS)
+
+
 def load():
     """dlopen libcoevo.so; raises CoevoError when it has not been built (python -m coevonet_amd.build)."""
     global _lib
@@ -227,7 +247,7 @@ def load():
             raise CoevoError(f"{LIB_PATH} is missing: build the HIP extension first "
                              "(python -m coevonet_amd.build); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_EXT_SIGS, **_XP_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_EXT_SIGS, **_XP_SIGS, **_SH_SIGS}.items():
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

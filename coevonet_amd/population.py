@@ -562,6 +562,16 @@ def _half_one_rank_plain(args, what, dist_ctx, gather_name, extensions):
             raise ValueError(f"{what} float16 is not built with args.{attr}")
 
 
+GA_SHARING_MODES = ("coevo_hof_mean", "coevo_population_sharing")   # Co-GA extension modes of the fully connected engine
+
+
+def refuse_ga_sharing_modes(args, what):
+    """the DeepQN trainers have neither mode: named, not ignored"""
+    for attr in GA_SHARING_MODES:
+        if getattr(args, attr, False):
+            raise ValueError(f"{what} is not built with args.{attr}")
+
+
 def half_route(args, what, rng, env_mode, dist_ctx, gather_name, extensions=()):
     """Which engines a trainer of the fully connected nets builds: False = the float32 ones, True = the float16 ones
     (HalfGAEngine / HalfESEngine).  What float16 does not cover is refused here with "`what` float16 ...", the first thing a
