@@ -14,14 +14,13 @@ with ``multi_breed=True``: the three roles' children and distances in one launch
 coevo_fc16_distance_finalize_multi) in place of six."""
 from __future__ import annotations
 
-import ctypes as ct
-
 import numpy as np
 import torch
 
 from . import lib as L
 from .mpe.simple_adversary import ENV_SEED
-from .population import N_EVAL, ROLE_D, ROLES, CoGASchedule, CoGATail, NetTable, SlabIO, co_ga_games, slab_layout
+from .population import (FUSED_MAX_E, FUSED_MAX_HOF, FUSED_MAX_POP, N_EVAL, ROLE_D, ROLES, CoGASchedule, CoGATail, NetTable,
+                         SlabIO, co_ga_games, fused_tail_fits, slab_layout)
 from .rollout import DeviceRollout, RolloutPlan, effective_steps
 
 
@@ -35,6 +34,9 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
     _promote_entry = "coevo_ga16_promote"
     _perturb_dist_entry = "coevo_fc16_perturb_dist"
     _finalize_entry = "coevo_fc16_distance_finalize"
+    _perturb_job = "Perturb16Job"
+    _perturb_multi_entry = "coevo_fc16_perturb_dist_multi"
+    _finalize_multi_entry = "coevo_fc16_distance_finalize_multi"
 
     def __init__(self, pop, hof, elites, limit_train=None, limit_eval=None, max_cycles=25, device="cuda",
                  env_seed=ENV_SEED, philox_seed=0, first_ordinal=1, *, adaptive=False, shard=(0, 1), env="device",
@@ -48,9 +50,9 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
             raise ValueError(f'HalfGAEngine: precision float16 has the device env only, not env="{env}"')
         if rng != "device_philox":
             raise ValueError(f'HalfGAEngine: precision float16 breeds with rng="device_philox" only, not "{rng}"')
-        if not (2 <= pop <= 4096 and 1 <= elites <= min(pop, 8) and 1 <= hof <= 16):
-            raise ValueError(f"HalfGAEngine: population {pop} (2 .. 4096), elites {elites} (1 .. 8, <= population) or "
-                             f"hof {hof} (1 .. 16) out of range")
+        if not (pop >= 2 and 1 <= elites <= pop and hof >= 1 and fused_tail_fits(pop, hof, elites)):   # (the fused tail only)
+            raise ValueError(f"HalfGAEngine: population {pop} (2 .. {FUSED_MAX_POP}), elites {elites} (1 .. {FUSED_MAX_E}, <= "
+                             f"population) or hof {hof} (1 .. {FUSED_MAX_HOF}) out of range")
         self.pop, self.hof, self.E = pop, hof, elites
         self.device, self.philox_seed = device, int(philox_seed)
         self.T_train = effective_steps(limit_train, max_cycles)
@@ -114,23 +116,11 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
             self.sigma[r].fill_(float(sigmas[r]))
         self._promote_roles(elites_from_pop=True, best_to_pop0=True)
         if self.multi_breed:
-            self._breed_children_multi(gen)
+            self._breed_children_multi(0, self.pop - 1, [L._p(self.sigma[r]) for r in ROLES], range(gen * 4, gen * 4 + 3))
         else:
             for ri, r in enumerate(ROLES):
                 self._breed_role_children(ri, r, 0, self.pop - 1, gen * 4 + ri, None, L._p(self.sigma[r]))
         self._dist_current = True
-
-    def _breed_children_multi(self, gen):
-        """_breed_role_children of the three roles as one job each of the two multi launches"""
-        n = self.pop - 1
-        pj, fj = (L.Perturb16Job * 3)(), (L.FinalizeJob * 3)()
-        for ri, r in enumerate(ROLES):
-            pj[ri] = L.Perturb16Job(self._ptr(r, "elite"), self.parent_idx.data_ptr(), self._ptr(r, "pop"), L._p(self.sigma[r]),
-                                    self._ptr(r, "stale"), L._p(self.dist_partial[r]), 1, n, ROLE_D[r], 0, gen * 4 + ri, 0)
-            fj[ri] = L.FinalizeJob(L._p(self.dist_partial[r]), L._p(self.dist[r]), L._p(self.best_dist[r]), self.pblocks[r], n,
-                                   1, 0)
-        L.call("coevo_fc16_perturb_dist_multi", ct.cast(pj, ct.c_void_p), 3, self.philox_seed, 0, None)
-        L.call("coevo_fc16_distance_finalize_multi", ct.cast(fj, ct.c_void_p), 3)
 
     def diversity(self):
         """the sharing score of each role in the last select() (float32)"""

@@ -35,9 +35,9 @@ from .fcnetwork import FCNetwork
 from .ga_half import HalfGAEngine
 from .game_logic import create_agent
 from .mpe.simple_adversary import ENV_SEED
-from .population import (GA_SHARING_MODES, N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, CoGASchedule, CoGATail, NetTable,
-                         SlabIO, adapt_mutation_power, captured, co_ga_games, eval_gate_limits, half_route, mean_eval_triple,
-                         shard_and_gather, slab_layout)
+from .population import (FUSED_MAX_HOF, GA_SHARING_MODES, N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, CoGASchedule, CoGATail,
+                         NetTable, SlabIO, adapt_mutation_power, captured, co_ga_games, eval_gate_limits, fused_tail_fits,
+                         half_route, mean_eval_triple, shard_and_gather, slab_layout)
 from .rollout import DeviceRollout, HostEnvRollout, RolloutPlan, effective_steps
 
 ROLE_SLOT = {"agent_0": 1, "agent_1": 2, "adversary_0": 0}   # env slot the role acts in
@@ -194,8 +194,9 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         # pipelined one-GPU loop has turned the mode on (_enable_hof_tiled); from then on every writer of the "hof" region keeps
         # them: the promotion launch of that loop's tail (coevo_ga_promote_tick_tiled), every other promotion and the
         # launch-per-step FIFO push (_refresh_hof_twins behind them) and uploads (_uploaded).
-        self._hof_tiled, self.hof_twin = False, None
-        if env == "device" and self.world == 1 and hof <= 16 and os.environ.get("COEVO_HOF_TILED", HOF_TILED_DEFAULT) != "0":
+        self._hof_tiled, self.hof_twin, self._twin_off = False, None, {}
+        if (env == "device" and self.world == 1 and hof <= FUSED_MAX_HOF   # (that loop's fused promotion keeps the twins: its limit)
+                and os.environ.get("COEVO_HOF_TILED", HOF_TILED_DEFAULT) != "0"):
             twin0 = -(-total // L.TASK_TWIN_UNIT) * L.TASK_TWIN_UNIT
             store = torch.zeros(twin0 + 3 * hof * L.W2_FLOATS, dtype=torch.float32, device=device)
             self.slab, self.hof_twin = store[:total], store[twin0:]
@@ -222,12 +223,12 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         host_k = int(os.environ.get("COEVO_HOST_COHORTS", "0")) or max(1, min(4, len(games) // 700))
         self.K = max(1, min(int(cohorts) if env == "device" else host_k, self.n_local))
         row_order = "class" if env == "device" else "cohort"
-        self._set_cohort_bounds()
+        # ONE partition for the rollout plan, the breeding and the resets: individual i of this rank belongs to the
+        # cohort whose [bounds[k], bounds[k+1]) holds it
+        self.cohort_bounds, cohort_of = cohort_partition(self.n_local, self.K)
         game_cohort = None
         if self.K > 1:
-            # ONE partition for the rollout plan, the breeding and the resets: individual i of this rank belongs to the
-            # cohort whose [bounds[k], bounds[k+1]) holds it
-            per_ind = np.repeat(cohort_partition(self.n_local, self.K)[1], self.hof)
+            per_ind = np.repeat(cohort_of, self.hof)
             game_cohort = np.concatenate([per_ind, per_ind, per_ind, np.full(N_EVAL, self.K - 1)]).astype(np.int32)
         resident = resident_enabled(env, heavy_rows, self.n_local, pop)
 
@@ -249,8 +250,7 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
                                     n_cohorts=self.K, game_cohort=game_cohort, row_order=row_order,
                                     resident_nets=resident_nets())
         except ValueError:  # tiny populations: the shared opponents have so few rows that they tie all games together
-            self.K = 1
-            self._set_cohort_bounds()
+            self.K, self.cohort_bounds = 1, cohort_partition(self.n_local, 1)[0]
             self.plan = RolloutPlan(np.array(games), table.net_off, table.net_D, device=device, heavy_rows=heavy_rows,
                                     row_order=row_order, resident_nets=resident_nets())
         if env == "device":
@@ -271,7 +271,7 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         # the rollout's closing launch, and the all-gathered [rank][role][j][4] buffer the selection reads as it is
         self.pack_local = torch.zeros(3, self.n_local, 4, dtype=torch.float64, device=device)
         self.pack_all = torch.zeros(self.world, 3, self.n_local, 4, dtype=torch.float64, device=device)
-        if self.population_sharing:   # all pairwise distances [pop][pop] and the niche counts [pop] of every role
+        if self.population_sharing:   # all pairwise distances [pop][pop] and the niche counts [pop] of every role: this mode's only
             self.pair_dist = {r: torch.zeros(pop, pop, **f32) for r in ROLES}
             self.niche = {r: torch.zeros(pop, **f32) for r in ROLES}
             n_scratch = max(int(L.load().coevo_fc_pairwise_scratch_doubles(pop, ROLE_D[r])) for r in ROLES)
@@ -279,8 +279,28 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         self.parent_idx = torch.tensor([c % elites for c in range(max(pop - 1, 1))], dtype=torch.int32, device=device)
         self.hof_shift_idx = torch.arange(1, max(hof, 2), dtype=torch.int32, device=device)
         self.iota = torch.arange(max(hof, elites, 2), dtype=torch.int32, device=device)
+        # partial sums of the children's stale-agent distances (fused into the perturb kernel) + the best's own distance
+        self.pblocks = {r: int(L.load().coevo_fc_perturb_blocks(ROLE_D[r])) for r in ROLES}
+        self.dist_partial = {r: torch.zeros(max(pop - 1, 1) * self.pblocks[r], dtype=torch.float64, device=device) for r in ROLES}
+        self.best_dist = {r: torch.zeros(1, **f32) for r in ROLES}
+        # last Hall-of-Fame game of every local individual (Q2), phase after phase: the index of one gather
+        one = torch.arange(self.n_local, device=device) * hof + hof - 1
+        self._last_game_idx = torch.cat([ph * self.n_local * hof + one for ph in range(3)])
         self.generation = 0
         self.steps_per_generation = 3 * pop * hof * self.T_train + N_EVAL * self.T_eval
+        # ---- everything else an engine ever holds; None: built on first use ----------------------------------
+        self._dist_current = False                       # dist = the stale-agent distances (Q3) of the population in the slab
+        self._rewards_pin = self._rewards_dev = None     # select(), env on the host cores: the rewards' way up
+        self._breeding_pending, self.generation_enqueued = False, 0   # the pipelined loops: children deferred to the next call
+        self._cohort_streams = self._cohort_done = self._tail_done = self._tail_graph = None   # _enqueue_cohort_chains
+        self.sharded_run, self._sharded_tail_graphs = False, {}   # step_sharded
+        # ... and of the device loops: setup_device_loop
+        self.gen_dev = self.sigma64 = self.sigma32 = self.sigma32_prev = self.hist = self.sig_hist = self.loop_args = None
+        self.cap, self.fused_tail, self.pipelined, self._gen_graph = 0, False, False, {}
+
+    def _need_device_loop(self):
+        if self.gen_dev is None:
+            raise RuntimeError("GAEngine: setup_device_loop(args, capacity) has to be called before a device-loop generation")
 
     # ------------------------------------------------------------------ loading weights
     def _uploaded(self, region):
@@ -318,9 +338,8 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
 
     # ------------------------------------------------------------------ one generation (schedule: population.CoGASchedule)
     def eval_rewards(self):
-        """mean reward triple (agent_0, agent_1, adversary_0) of the 10 evaluation games in the last rollout"""
         self.ro.check_status()
-        if hasattr(self.ro, "collect_stamps"):
+        if self.env_mode == "device":
             self.ro.collect_stamps()  # check_status synchronised: this replay's kernel clock stamps are final
         return mean_eval_triple(self.rewards_host()[self.n_main:])
 
@@ -329,7 +348,7 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         if torch.is_tensor(self.ro.rewards):
             dev_rewards = self.ro.rewards
         else:   # env on the host cores: the play_game triples come up once per generation (72 KB at cfg 2)
-            if getattr(self, "_rewards_dev", None) is None:
+            if self._rewards_dev is None:
                 self._rewards_pin = torch.zeros(self.plan.n_games, 3, dtype=torch.float64).pin_memory()
                 self._rewards_dev = torch.zeros(self.plan.n_games, 3, dtype=torch.float64, device=self.device)
             self._rewards_pin.numpy()[:] = self.ro.rewards
@@ -340,38 +359,38 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
             self._select_shared(dev_rewards, per_phase)
             return
         if self._fused_host_tail():
-            self._ensure_breed_buffers()
-            if not getattr(self, "_dist_current", False):   # (generation 0, or a population loaded from the host)
-                for r in ROLES:
-                    L.call("coevo_fc_distance", self._ptr(r, "stale"), self._ptr(r, "pop"), self.pop, ROLE_D[r],
-                           L._p(self.dist[r]))
+            self._stale_distances(ROLES)  # (generation 0, or a population loaded from the host)
             self._select_roles(lambda ri: L._p(dev_rewards), lambda ri: ri * per_phase, self.hof)
             return
         for ph, r in enumerate(ROLES):
-            D = ROLE_D[r]
-            # distances of the local shard to the stale agent (Q3), scores need every rank's distances
-            if not getattr(self, "_dist_current", False):
-                L.call("coevo_fc_distance", self._ptr(r, "stale"), self._ptr(r, "pop", self.lo), self.n_local, D,
-                       self.dist[r].data_ptr() + 4 * self.lo)
+            # distances of the local shard to the stale agent, scores need every rank's distances
+            self._stale_distances((r,), self.lo, self.n_local)
             # last HoF game of every local individual (Q2)
-            idx = ph * per_phase + torch.arange(self.n_local, device=self.device) * self.hof + self.hof - 1
+            idx = self._last_game_idx[ph * self.n_local:(ph + 1) * self.n_local]
             self.last_reward[ph, self.lo:self.hi] = dev_rewards[idx]
         if self.world > 1:
             self.gather(self)  # all-gather of dist[role][lo:hi] and last_reward[:, lo:hi]
         self._select_unfused(lambda ri: self.last_reward[ri].data_ptr(), lambda ri: 0, 1)
+
+    def _stale_distances(self, roles, first=0, n=None, always=False):
+        """dist[first : first + n] (n = None: the whole population) of `roles`: the distances to the stale agent (Q3) in a pass
+        over the slab - unless breed_device() left them current (always: whatever it left)"""
+        if self._dist_current and not always:
+            return
+        for r in roles:
+            L.call("coevo_fc_distance", self._ptr(r, "stale"), self._ptr(r, "pop", first), self.pop if n is None else n,
+                   ROLE_D[r], self.dist[r].data_ptr() + 4 * first)
 
     def _select_shared(self, dev_rewards, per_phase):
         """select() under hof_mean / population_sharing (one rank, the whole population here), launch per step and role:
         the share - niche counts over all pairwise distances, or today's score against the stale agent -, the fitness with
         the mode's switches, the ranking, and the best individual's stale-agent distance, which breed_device's fused promotion
         hands to the children's distances: the stale-agent chain stays valid in either mode"""
-        self._ensure_breed_buffers()
-        flags = ((L.K_SH["COEVO_FIT_HOF_MEAN"] if self.hof_mean else 0)
+        flags =((L.K_SH["COEVO_FIT_HOF_MEAN"] if self.hof_mean else 0)
                  | (L.K_SH["COEVO_FIT_PER_INDIVIDUAL"] if self.population_sharing else 0))
         for ri, r in enumerate(ROLES):
             D = ROLE_D[r]
-            if not getattr(self, "_dist_current", False):
-                L.call("coevo_fc_distance", self._ptr(r, "stale"), self._ptr(r, "pop"), self.pop, D, L._p(self.dist[r]))
+            self._stale_distances((r,))
             if self.population_sharing:
                 L.call("coevo_fc_pairwise_distance", self._ptr(r, "pop"), self.pop, D, L._p(self.pair_scratch),
                        L._p(self.pair_dist[r]))
@@ -453,32 +472,19 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         self.hist = torch.zeros(3, self.cap, dtype=torch.float64, device=dev)
         self.sig_hist = torch.zeros(3, self.cap, dtype=torch.float64, device=dev)
         self.loop_args = (float(args.min_mutation_power), float(args.max_mutation_power), 1 if args.adaptive else 0)
-        self._gen_graph = None
+        self._gen_graph = {}
         # distances to the stale agent: computed once for the initial population, then accumulated by the perturb
         # kernel while it writes each new child (no second pass over the 336 MB population)
-        self._ensure_breed_buffers()
-        for r in ROLES:
-            L.call("coevo_fc_distance", self._ptr(r, "stale"), self._ptr(r, "pop"), self.pop, ROLE_D[r],
-                   L._p(self.dist[r]))
-        # argument blocks of the fused selection / promotion launches (one launch for the three roles)
-        self.fused_tail = self.E <= 8 and self.hof <= 16 and self.pop <= 4096
+        self._stale_distances(ROLES, always=True)
+        # the fused selection / promotion launches (one launch for the three roles)
+        self.fused_tail = fused_tail_fits(self.pop, self.hof, self.E)
         self.pipelined = os.environ.get("COEVO_PIPELINED", "1") != "0"   # breed / reset / roll out cohort by cohort
-
-    def _ensure_breed_buffers(self):
-        """partial sums of the children's stale-agent distances (fused into the perturb kernel) + the best's own distance"""
-        if getattr(self, "pblocks", None) is None:
-            dev = self.device
-            self.pblocks = {r: int(L.load().coevo_fc_perturb_blocks(ROLE_D[r])) for r in ROLES}
-            self.dist_partial = {r: torch.zeros(max(self.pop - 1, 1) * self.pblocks[r], dtype=torch.float64, device=dev)
-                                 for r in ROLES}
-            self.best_dist = {r: torch.zeros(1, dtype=torch.float32, device=dev) for r in ROLES}
 
     def _fused_host_tail(self):
         """the host-driven loop on one GPU with device-built offspring takes the device-resident loop's fused launches:
         selection of the three roles in one (coevo_ga_select), promotion in one (coevo_ga_promote), children with their
         distances fused in - 8 launches instead of ~40 per generation"""
-        return (self.world == 1 and self.rng_mode == "device_philox" and self.pop > 1 and self.E <= 8 and self.hof <= 16
-                and self.pop <= 4096)
+        return self.world == 1 and self.rng_mode == "device_philox" and self.pop > 1 and fused_tail_fits(self.pop, self.hof, self.E)
 
     def _adapt_args(self, with_prev=False):
         mn, mx, adaptive = self.loop_args
@@ -493,12 +499,7 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
 
     def _select_adapt_roles(self, rewards_ptr_of, game_first_of, games_per_individual, gathered=None, with_prev=False):
         """selection of the three roles + the sigma rule (evaluation means, adaptive mutation power) in ONE launch"""
-        roles = (L.GaSelectRole * 3)()
-        for ri, r in enumerate(ROLES):
-            roles[ri] = L.GaSelectRole(None if gathered is not None else L._p(self.dist[r]),
-                                       None if gathered is not None else rewards_ptr_of(ri), L._p(self.div[r]),
-                                       L._p(self.fitness[r]), L._p(self.order[r]), L._p(self.best_dist[r]),
-                                       0 if gathered is not None else game_first_of(ri), RET_SLOT[r])
+        roles = self._select_role_block(rewards_ptr_of, game_first_of, gathered is not None)
         ad = self._adapt_args(with_prev)
         L.call("coevo_ga_select_adapt", roles, 3, self.pop, games_per_individual, self.hof,
                L._p(gathered) if gathered is not None else None, self.n_local if gathered is not None else 0, L.C.byref(ad))
@@ -507,26 +508,23 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         """reset -> 25 cycles -> rewards -> sharing/fitness/rank -> evaluation means + adaptive sigma -> HoF push and
         offspring -> generation counter tick; every launch takes the generation from the device counter, so the
         captured graph is replayed unchanged generation after generation"""
+        self._need_device_loop()
         self._enqueue_resets()
         self.ro.enqueue(self.n_cycles)
         self._enqueue_selection_and_breeding()
 
     def _enqueue_resets(self):
+        """generation 0's segments; the kernel adds the device generation x the ordinals of one generation"""
         assert self.world == 1 and self.env_mode == "device"
-        ro, M = self.ro, 3 * self.pop * self.hof
-        per_gen, per_phase = M + N_EVAL, self.pop * self.hof
-        g = L._p(self.gen_dev)
-        for ph in range(3):
-            L.call("coevo_mpe_reset_gen", L._p(ro.state), self.plan.n_games, ph * per_phase, per_phase, ro.rng,
-                   self.first_ordinal + ph * per_phase, g, per_gen)
-        L.call("coevo_mpe_reset_gen", L._p(ro.state), self.plan.n_games, self.n_main, N_EVAL, ro.rng,
-               self.first_ordinal - per_gen + M, g, per_gen)
+        ro, per_gen = self.ro, self._ordinal_base(1) - self._ordinal_base(0)
+        for first, n, ordinal in self._reset_segments(0, 0, self.pop, True):
+            L.call("coevo_mpe_reset_gen", L._p(ro.state), self.plan.n_games, first, n, ro.rng, ordinal, L._p(self.gen_dev),
+                   per_gen)
 
     def _enqueue_selection_and_breeding(self, breed=True):
         """(Measured: running the three roles' chains as parallel graph branches gains 1 % in the split loop and costs
         30 % inside the single whole-generation graph - this runtime schedules branched graphs badly; kept serial.)"""
-        ro, per_phase = self.ro, self.pop * self.hof
-        g = L._p(self.gen_dev)
+        ro, per_phase, g = self.ro, self.pop * self.hof, L._p(self.gen_dev)
         if self.fused_tail:
             # selection + sigma rule in one launch, promotion (+ the counter's tick when nothing follows) in one: the tail of a
             # pipelined generation is closing step -> these two (round 4: five launches)
@@ -546,9 +544,6 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         L.call("coevo_counter_add", g, 1)
 
     # ------------------------------------------------------------------ pipelined generation (cohort by cohort)
-    def _set_cohort_bounds(self):
-        self.cohort_bounds = cohort_partition(self.n_local, self.K)[0]
-
     def _cohort_individuals(self, k):
         return self.lo + int(self.cohort_bounds[k]), self.lo + int(self.cohort_bounds[k + 1])
 
@@ -561,22 +556,9 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         lo_k, hi_k = self._cohort_individuals(k)
         c_lo, c_hi = max(lo_k, 1) - 1, hi_k - 1
         if c_hi > c_lo:
-            import ctypes as ct
-            pj = (L.PerturbJob * 3)()
-            fj = (L.FinalizeJob * 3)()
-            for ri, r in enumerate(ROLES):
-                part = self.dist_partial[r].data_ptr() + 8 * c_lo * self.pblocks[r]
-                pj[ri] = L.PerturbJob(self._ptr(r, "elite"), self.parent_idx.data_ptr() + 4 * c_lo, self._ptr(r, "pop"),
-                                      self.sigma32.data_ptr() + 4 * ri, self._ptr(r, "stale"), part, 1 + c_lo,
-                                      c_hi - c_lo, ROLE_D[r], c_lo, ri if gen_dev is not None else noise_gen * 4 + ri, 0)
-                fj[ri] = L.FinalizeJob(part, self.dist[r].data_ptr(),
-                                       self.best_dist[r].data_ptr() if c_lo == 0 else None, self.pblocks[r],
-                                       c_hi - c_lo, 1 + c_lo, 0)
-            L.call("coevo_fc_perturb_dist_multi", ct.cast(pj, ct.c_void_p), 3, self.philox_seed, 0, gen_dev)
-            if tick:
-                L.call("coevo_fc_distance_finalize_multi_tick", ct.cast(fj, ct.c_void_p), 3, L._p(self.gen_dev))
-            else:
-                L.call("coevo_fc_distance_finalize_multi", ct.cast(fj, ct.c_void_p), 3)
+            sigma, stream = self.sigma32.data_ptr(), 0 if gen_dev is not None else noise_gen * 4
+            self._breed_children_multi(c_lo, c_hi, (sigma, sigma + 4, sigma + 8), (stream, stream + 1, stream + 2), gen_dev,
+                                       L._p(self.gen_dev) if tick else None)
             return
         if lo_k == 0:
             for r in ROLES:
@@ -585,19 +567,13 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
             L.call("coevo_counter_add", L._p(self.gen_dev), 1)
 
     def _reset_cohort(self, k, gen):
-        lo_k, hi_k = self._cohort_individuals(k)
-        base, M = self._ordinal_base(gen), 3 * self.pop * self.hof
-        per_phase = self.n_local * self.hof
-        segs = [(ph * per_phase + (lo_k - self.lo) * self.hof, (hi_k - lo_k) * self.hof,
-                 base + ph * self.pop * self.hof + lo_k * self.hof) for ph in range(3)]
-        if k == self.K - 1 and gen > 0:
-            segs.append((self.n_main, N_EVAL, self._ordinal_base(gen - 1) + M))
+        segs = self._reset_segments(gen, *self._cohort_individuals(k), k == self.K - 1 and gen > 0)   # (evaluation: the last's)
         self.ro.reset_segments(segs, arm=(k, self.n_cycles))   # (+ the cohort's clock stamps, when launches are timed)
 
     def flush_breeding(self):
         """the pipelined loop breeds generation g+1's population at the start of call g+1; anything that reads the
         population slab before that (export, tests) asks for it here"""
-        if getattr(self, "_breeding_pending", False):
+        if self._breeding_pending:
             torch.cuda.synchronize()
             for k in range(self.K):
                 self._breed_cohort(k, self.generation_enqueued - 1)
@@ -610,6 +586,7 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         rollout and replays the selection graph.  Cohort k+1 is still breeding (Philox / Box-Muller: compute-bound)
         while cohort k's chain already streams weights, and the chains start a breeding time apart, which is the stagger
         they want anyway.  The host knows `gen`; sigma, ranks and distances stay on the device."""
+        self._need_device_loop()
         assert self.world == 1 and self.env_mode == "device" and self.fused_tail and self.K > 1
         if self.hof_twin is not None and not self._hof_tiled and self.plan.heavy is not None:
             self._enable_hof_tiled()
@@ -624,10 +601,9 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         """per cohort stream: deferred breeding of its children -> reset of its games -> its chain of merged launches;
         then, on the caller's stream, the closing step of the rollout"""
         ro = self.ro
-        if gen <= 1:  # the evaluation games of "generation -1" do not exist: disabled in generation 0 only
-            ro.set_limits(eval_gate_limits(self.plan.n_games, self.n_main, self.T_train, self.T_eval, gen))
+        self._gate_evaluation(gen)
         main = torch.cuda.current_stream()
-        if getattr(self, "_cohort_streams", None) is None:
+        if self._cohort_streams is None:
             # cohort 0 on the caller's stream, the others on the rollout context's own lane streams (streams from
             # torch's pool did not overlap with each other here: 356 vs 510 generations/s)
             self._cohort_streams = [main] + [
@@ -635,8 +611,6 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
                 for k in range(1, self.K)]
             self._cohort_done = [torch.cuda.Event() for _ in range(self.K)]
             self._tail_done = torch.cuda.Event()
-            self._tail_graph = None
-            self._breeding_pending = False
         self._tail_done.record(main)  # everything enqueued so far (the previous tail, or the initial uploads)
         for k, s in reversed(list(enumerate(self._cohort_streams))):  # the caller's stream (cohort 0) last
             if k:
@@ -656,7 +630,7 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
     def _packed_exchange(self):
         """the fused exchange of a sharded generation: the rollout's closing launch writes this rank's all-gather record,
         the selection reads the gathered buffer as it is, elites are rebuilt inside the promotion launch"""
-        return (getattr(self, "sharded_run", False) and self.fused_tail and self.gather_packed is not None
+        return (self.sharded_run and self.fused_tail and self.gather_packed is not None
                 and os.environ.get("COEVO_PACKED_EXCHANGE", "1") != "0")
 
     def _pack_args(self):
@@ -674,9 +648,10 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         (+ this rank's all-gather record), ONE collective, selection, promotion (+ elite rebuild), sigma rule, children,
         their distances (+ counter tick) = 7 + the collective, where the separate form took ~32 (a rank of 8: 0.16 ms of a
         0.72 ms generation - profiles/r04_cfg2_shard_1_of_4_kernel_stats.csv)."""
+        self._need_device_loop()
         assert self.env_mode == "device" and self.rng_mode == "device_philox"
         self.sharded_run = True
-        ro, M = self.ro, 3 * self.pop * self.hof
+        ro = self.ro
         if self.K > 1 and self.fused_tail and self.pipelined and ro.desc.merged:
             # as on one GPU: each cohort stream breeds its children (deferred), resets its games, runs its chain
             self._enqueue_cohort_chains(gen)
@@ -684,14 +659,9 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
             self._breeding_pending = self.n_local > 0 and self.pop > 1
             self.generation_enqueued = gen + 1
             return
-        if gen <= 1:  # the evaluation games of "generation -1" do not exist: disabled in generation 0 only
-            ro.set_limits(eval_gate_limits(self.plan.n_games, self.n_main, self.T_train, self.T_eval, gen))
-        base = self._ordinal_base(gen)
-        per_phase = self.n_local * self.hof
-        segs = [(ph * per_phase, per_phase, base + ph * self.pop * self.hof + self.lo * self.hof) for ph in range(3)]
-        if gen > 0:
-            segs.append((self.n_main, N_EVAL, self._ordinal_base(gen - 1) + M))
-        ro.reset_segments(segs, arm=(None, self.n_cycles))   # one launch (three phases + evaluation games + every cohort's arm)
+        self._gate_evaluation(gen)
+        # one launch (three phases + evaluation games + every cohort's arm)
+        ro.reset_segments(self._reset_segments(gen, self.lo, self.hi, gen > 0), arm=(None, self.n_cycles))
         if self._packed_exchange():   # (the closing step + this rank's all-gather record: in the persistent launch, if it is one)
             ro.enqueue(self.n_cycles, armed=True, pack=self._pack_args())
         else:
@@ -700,24 +670,18 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
 
     def _sharded_tail(self, gen, breed):
         """all-gather of the fitness inputs -> selection -> elites (rebuilt) / HoF / best -> sigma rule -> [children]"""
-        ro = self.ro
-        per_phase = self.n_local * self.hof
         packed = self._packed_exchange()
         if packed:
             self.gather_packed(self)   # pack_local (written by the closing step) -> pack_all on every rank
         else:
             # last HoF game of every local individual (Q2) + its stale-agent distance -> every rank (one fused all-gather)
-            if getattr(self, "_last_game_idx", None) is None:  # built once: one gather launch per generation
-                one = torch.arange(self.n_local, device=self.device) * self.hof + self.hof - 1
-                self._last_game_idx = torch.cat([ph * per_phase + one for ph in range(3)])
-            self.last_reward[:, self.lo:self.hi] = ro.rewards[self._last_game_idx].view(3, self.n_local, 3)
+            self.last_reward[:, self.lo:self.hi] = self.ro.rewards[self._last_game_idx].view(3, self.n_local, 3)
             if self.world > 1:
                 self.gather(self)
         # everything after the all-gather replays as one graph from generation 1 on (the elite rebuild and the children then
         # take the generation from the device counter); generation 0 (elites out of the initial population) runs eagerly
         if gen > 0 and self.fused_tail and self.ro.use_graph and (packed or not breed):
-            key = (bool(breed), packed)
-            graphs = self.__dict__.setdefault("_sharded_tail_graphs", {})
+            key, graphs = (bool(breed), packed), self._sharded_tail_graphs
             if key not in graphs:
                 graphs[key] = captured(lambda: self._sharded_tail_post(gen, breed=breed, gen_from_device=True, packed=packed))
             graphs[key].replay()
@@ -756,33 +720,35 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
                     self._best_to_pop0(r)
         if self.fused_tail:
             self._promote_roles(elites_from_pop=(gen == 0), best_to_pop0=(self.lo == 0))
-        for ri, r in enumerate(ROLES):
-            if not breed:
-                break
+        for ri, r in enumerate(ROLES) if breed else ():
             if c_hi > c_lo:
                 self._breed_role_children(ri, r, c_lo, c_hi, gen * 4 + ri, None, self.sigma32.data_ptr() + 4 * ri)
             elif self.lo == 0:  # a shard that holds only the unchanged best
                 self.dist[r][0:1].copy_(self.best_dist[r])
         L.call("coevo_counter_add", g, 1)
 
-    def replay_generation(self, gen):
-        if gen <= 1:  # the evaluation games of "generation -1" do not exist: disabled in generation 0 only
+    def _gate_evaluation(self, gen):
+        """the evaluation games of "generation -1" do not exist: disabled in generation 0 only"""
+        if gen <= 1:
             self.ro.set_limits(eval_gate_limits(self.plan.n_games, self.n_main, self.T_train, self.T_eval, gen))
+
+    def replay_generation(self, gen):
+        self._need_device_loop()
+        self._gate_evaluation(gen)
         if self.ro.use_graph and self.ro.n_cohorts > 1 and self.fused_tail and self.pipelined:
             return self.replay_generation_pipelined(gen)
         if self.ro.use_graph and self.ro.n_cohorts > 1:
             # cohort chains only run side by side when their launches are enqueued eagerly on their own streams (inside a
             # captured graph this runtime schedules them no better than one chain): the resets and the selection /
             # breeding tail are two small graphs, the rollout between them is one C call
-            if self._gen_graph is None:
-                self._gen_graph = [captured(self._enqueue_resets), captured(self._enqueue_selection_and_breeding)]
-            self._gen_graph[0].replay()
+            if not self._gen_graph:
+                self._gen_graph = {"resets": captured(self._enqueue_resets),
+                                   "tail": captured(self._enqueue_selection_and_breeding)}
+            self._gen_graph["resets"].replay()
             self.ro.enqueue(self.n_cycles)
-            self._gen_graph[1].replay()
+            self._gen_graph["tail"].replay()
         elif self.ro.use_graph:
             key = bool(self.ro.time_light)
-            if self._gen_graph is None:
-                self._gen_graph = {}
             if key not in self._gen_graph:
                 self._gen_graph[key] = captured(self.enqueue_generation)
                 # the capture did not execute anything: the counter still holds `gen`
@@ -845,6 +811,7 @@ class GATrainer:
         self.res = GAResult()
         self.gen = 0
         self.stamp_every = 1
+        self._slots = None   # _collect_device_loop: two pinned host slots, built on first use
         if self.half:
             # the host-driven loop of step() over the float16 engine; the adaptive rule stays on the host (_finish_generation)
             self.device_loop = self.sharded_loop = False
@@ -857,19 +824,14 @@ class GATrainer:
             self.res.engine = self.eng
             return
         gather_packed = getattr(dist_ctx, "gather_ga_packed", None) if gather else None
-        # the host-free generation loop needs device-built offspring, the device env and a single rank
-        self.device_loop = (self.rng == "device_philox" and env_mode == "device" and shard == (0, 1)
-                            and getattr(args, "coevo_device_loop", True))
-        # cohort chains overlap only when enqueued eagerly (GAEngine.replay_generation): worth it in the host-free loop
-        # ... and its population-sharded counterpart (GAEngine.step_sharded)
+        # the host-free generation loops need device-built offspring and the device env (and their fused coevo_ga_select does not
+        # carry the sharing modes): GAEngine.replay_generation on a single rank, GAEngine.step_sharded on a population shard
+        host_free = bool(self.rng == "device_philox" and env_mode == "device" and getattr(args, "coevo_device_loop", True)
+                         and not self.sharing_modes)
         force = bool(getattr(args, "coevo_force_sharded_loop", False))  # measurement: the N>1 code path on one GPU
-        self.sharded_loop = (self.rng == "device_philox" and env_mode == "device" and (shard != (0, 1) or force)
-                             and getattr(args, "coevo_device_loop", True))
-        if self.sharded_loop:
-            self.device_loop = False
-        if self.sharing_modes:   # (the host-free loops and their fused coevo_ga_select do not carry the modes)
-            self.device_loop = self.sharded_loop = False
-        cohorts = getattr(args, "coevo_cohorts", None)
+        self.sharded_loop = host_free and (shard != (0, 1) or force)
+        self.device_loop = host_free and not self.sharded_loop
+        cohorts = getattr(args, "coevo_cohorts", None)   # (chains overlap only when enqueued eagerly: the host-free loops)
         if cohorts is None:
             cohorts = DEVICE_LOOP_COHORTS if (self.device_loop or self.sharded_loop) else DEFAULT_COHORTS
             # a small shard (pop 200 over 4 / 8 GPUs: 50 / 25 individuals per role) is ONE launch per env-cycle: its few
@@ -932,7 +894,7 @@ class GATrainer:
             res.game_rewards.append(eng.rewards_host()[:eng.n_main].copy())
             res.fitness.append([eng.fitness[r].cpu().numpy().tolist() for r in ROLES])
             # (population sharing has no single score: per role the mean niche count)
-            res.diversity.append(eng.mean_niche() if getattr(eng, "population_sharing", False)
+            res.diversity.append(eng.mean_niche() if self.sharing_modes and eng.population_sharing
                                  else [float(eng.div[r].item()) for r in ROLES])
             res.elite_ids.append([eng.elite_ids()[r] for r in ROLES])
         res.seconds.append(time.perf_counter() - t0)
@@ -944,7 +906,7 @@ class GATrainer:
         stream (so before anything of generation gen+1 can overwrite the sources), and the PREVIOUS generation's slot -
         long complete - is harvested into the result.  The result therefore lags one generation until finish()."""
         eng = self.eng
-        if getattr(self, "_slots", None) is None:
+        if self._slots is None:
             pin = lambda *shape, dtype: torch.zeros(*shape, dtype=dtype).pin_memory()
             self._slots = [{"rewards": pin(eng.n_main, 3, dtype=torch.float64),
                             "fitness": pin(3, eng.pop, dtype=torch.float32), "div": pin(3, dtype=torch.float32),
@@ -995,7 +957,7 @@ class GATrainer:
                 self.eng.flush_breeding()
                 torch.cuda.synchronize()
                 self.eng.ro.check_status()
-                if self.collect and getattr(self, "_slots", None):  # the lagging last generation
+                if self.collect and self._slots:  # the lagging last generation
                     self._harvest(self._slots[(self.gen - 1) % 2])
                 self.eng.ro.collect_stamps()
                 self._sync_history_from_device(upto=self.gen - 1)

@@ -5,14 +5,15 @@ Co-GA generation tail of the fully connected engines, the Co-ES update of the fl
 GAEngine / HalfGAEngine (genetic_algorithm.py, ga_half.py), ESEngine / HalfESEngine (evolutionary_strategy.py, es_half.py)
 and DQNGAEngine / HalfDQNGAEngine / DQNESEngine (dqn_population.py, dqn_ga_half.py) differ in precision, strides and kernels,
 not in who plays whom: the seat rules of the reference's generation bodies are written ONCE, here.  slab_layout, NetTable,
-co_ga_games, co_ga_games2, co_es_games, co_es_games2, cross_games, cross_games2 (the game tables of crossplay.py), mean_eval,
-eval_gate_limits and the sigma rule are plain python - they
-touch neither torch nor the library, which this module imports for captured() and the mixins only - and are pinned by
+co_ga_games, co_ga_reset_segments, co_ga_games2, co_es_games, co_es_games2, cross_games, cross_games2 (the game tables of
+crossplay.py), mean_eval, eval_gate_limits, fused_tail_fits and the sigma rule are plain python - they touch neither torch
+nor the library, which this module imports for captured() and the mixins only - and are pinned by
 tests/test_population_cpu.py; the mixins hold the calls the engines made identically (tests/test_ga_launch_scripts_cpu.py,
 tests/test_es_launch_scripts_cpu.py: recorded before they were shared).
 """
 from __future__ import annotations
 
+import ctypes as ct
 import os
 
 import numpy as np
@@ -80,6 +81,17 @@ def co_ga_games(net, lo, hi, hof):
     for _ in range(N_EVAL):  # evaluate_current_weights(best trio) = newest HoF members (:12-29, :301)
         games.append((net("hof", "adversary_0", h - 1), net("hof", "agent_0", h - 1), net("hof", "agent_1", h - 1)))
     return games, n_main
+
+
+def co_ga_reset_segments(base, base_prev, pop, hof, lo, n_local, a, b, prev_eval):
+    """Reset ordinals (Q6) of the games that the individuals [a, b) of a rank holding [lo, lo + n_local) play in one generation
+    launch -> [(game_first, count, first_ordinal), ...]: per phase their run of the rank's table, under the ordinals from
+    base (the generation's first) + ph pop hof + a hof on, whichever rank plays them.  prev_eval: + the evaluation games of
+    the generation before behind the rank's main games, under the ordinals behind THAT generation's (base_prev) main games."""
+    segs = [(ph * n_local * hof + (a - lo) * hof, (b - a) * hof, base + ph * pop * hof + a * hof) for ph in range(3)]
+    if prev_eval:
+        segs.append((3 * n_local * hof, N_EVAL, base_prev + 3 * pop * hof))
+    return segs
 
 
 def co_ga_games2(net, lo, hi, hof, first_ordinal, pop):
@@ -248,42 +260,39 @@ class CoGASchedule:
     def _ordinal_base(self, gen):
         return self.first_ordinal + gen * (3 * self.pop * self.hof + N_EVAL)
 
+    def _reset_segments(self, gen, a, b, prev_eval):
+        return co_ga_reset_segments(self._ordinal_base(gen), self._ordinal_base(gen - 1), self.pop, self.hof, self.lo,
+                                    self.n_local, a, b, prev_eval)
+
     def rollout(self, gen, with_prev_eval):
         """plays generation `gen`'s 3*n_local*hof games and, riding along, the 10 evaluation games of gen-1 (they depend only on
         that generation's selection)"""
-        ro, M = self.ro, 3 * self.pop * self.hof
-        ro.set_limits(eval_gate_limits(self.plan.n_games, self.n_main, self.T_train, self.T_eval, 1 if with_prev_eval else 0))
-        base = self._ordinal_base(gen)
-        per_phase = self.n_local * self.hof
+        self.ro.set_limits(eval_gate_limits(self.plan.n_games, self.n_main, self.T_train, self.T_eval, 1 if with_prev_eval else 0))
+        segs = self._reset_segments(gen, self.lo, self.lo + self.n_local, with_prev_eval)
+        if self.one_reset:   # (the three phases are one run of ordinals)
+            assert self.n_local == self.pop
+            segs = [(0, self.n_main, segs[0][2])] + segs[3:]
+        self._reset(segs)
+        self.ro.run(self.n_cycles)
+
+    def _reset(self, segs):
+        """the device env: a launch per segment; the host env: the ordinal of every game (0 for the others)"""
         if self.env_mode == "device":
-            if self.one_reset:
-                assert self.n_local == self.pop
-                ro.reset(0, self.n_main, base)
-            else:
-                for ph in range(3):
-                    ro.reset(ph * per_phase, per_phase, base + ph * self.pop * self.hof + self.lo * self.hof)
-            if with_prev_eval:
-                ro.reset(self.n_main, N_EVAL, self._ordinal_base(gen - 1) + M)
-        else:
-            ords = np.zeros(self.plan.n_games, dtype=np.int64)
-            for ph in range(3):
-                ords[ph * per_phase:(ph + 1) * per_phase] = (base + ph * self.pop * self.hof + self.lo * self.hof
-                                                             + np.arange(per_phase))
-            ords[self.n_main:] = (self._ordinal_base(gen - 1) + M + np.arange(N_EVAL)) if with_prev_eval else 0
-            ro.reset_from_ordinals(ords)
-        ro.run(self.n_cycles)
+            for seg in segs:
+                self.ro.reset(*seg)
+            return
+        ords = np.zeros(self.plan.n_games, dtype=np.int64)
+        for first, n, ordinal in segs:
+            ords[first:first + n] = ordinal + np.arange(n)
+        self.ro.reset_from_ordinals(ords)
 
     def eval_only(self, gen):
         """flush: the evaluation games of generation `gen` alone (main games disabled) -> their mean triple"""
-        ro, M = self.ro, 3 * self.pop * self.hof
+        ro = self.ro
         ro.set_limits(eval_gate_limits(self.plan.n_games, self.n_main, 0, self.T_eval, 1))
         if self.env_mode == "device":
             ro.reset(0, self.n_main, 0)
-            ro.reset(self.n_main, N_EVAL, self._ordinal_base(gen) + M)
-        else:
-            ords = np.zeros(self.plan.n_games, dtype=np.int64)
-            ords[self.n_main:] = self._ordinal_base(gen) + M + np.arange(N_EVAL)
-            ro.reset_from_ordinals(ords)
+        self._reset(self._reset_segments(gen + 1, self.lo, self.lo, True)[3:])   # (as generation gen + 1's launch would)
         ro.run((self.T_eval + 2) // 3)
         return self.eval_rewards()
 
@@ -299,22 +308,42 @@ class CoGASchedule:
         return {r: self.order[r][:self.E].cpu().numpy().astype(int).tolist() for r in ROLES}
 
 
+FUSED_MAX_POP, FUSED_MAX_HOF, FUSED_MAX_E = 4096, 16, 8
+
+
+def fused_tail_fits(pop, hof, elites):
+    """what the fused tail's launches take: coevo_ga_select ranks the population in one workgroup (select.hip), the promotion
+    launches unroll over the Hall of Fame and the elites (promote_roles.hip.h PROMOTE_MAX_HOF, PROMOTE_MAX_E)"""
+    return pop <= FUSED_MAX_POP and hof <= FUSED_MAX_HOF and elites <= FUSED_MAX_E
+
+
 class CoGATail:
     """The generation tail of the fully connected Co-GA engines after the rollout: selection, promotion (elites, Hall of Fame,
     best), children with their stale-agent distances - each launch sequence written once, in its fused form (one launch for
-    the three roles: E <= 8, hof <= 16, pop <= 4096) and its launch-per-step form.  A class names its promotion, child and
-    distance-reduction entry points.  Needs pop, hof, E, philox_seed, slab / base / stride (SlabIO._ptr), dist, div, fitness,
-    order, best_dist, dist_partial, pblocks, parent_idx and, for the launch-per-step forms, iota and hof_shift_idx."""
+    the three roles: fused_tail_fits) and its launch-per-step form.  A class names its promotion, child and distance-reduction
+    entry points and the job struct and entry points of the multi-role breeding.  Needs pop, hof, E, philox_seed, slab / base /
+    stride (SlabIO._ptr), dist, div, fitness, order, best_dist, dist_partial, pblocks, parent_idx and, for the launch-per-step
+    forms, iota and hof_shift_idx."""
     _promote_entry = "coevo_ga_promote"
     _perturb_dist_entry = "coevo_fc_perturb_dist"
     _finalize_entry = "coevo_fc_distance_finalize"
+    _perturb_job = "PerturbJob"
+    _perturb_multi_entry = "coevo_fc_perturb_dist_multi"
+    _finalize_multi_entry = "coevo_fc_distance_finalize_multi"
+    _hof_tiled = False   # (GAEngine may turn it on: the Hall of Fame then has tile-major W2 twins that the rollout reads)
 
-    def _select_roles(self, rewards_ptr_of, game_first_of, games_per_individual):
+    def _select_role_block(self, rewards_ptr_of, game_first_of, gathered=False):
+        """GaSelectRole[3]; gathered: distances and rewards come out of the all-gathered buffer, not from these"""
         roles = (L.GaSelectRole * 3)()
         for ri, r in enumerate(ROLES):
-            roles[ri] = L.GaSelectRole(L._p(self.dist[r]), rewards_ptr_of(ri), L._p(self.div[r]), L._p(self.fitness[r]),
-                                       L._p(self.order[r]), L._p(self.best_dist[r]), game_first_of(ri), RET_SLOT[r])
-        L.call("coevo_ga_select", roles, 3, self.pop, games_per_individual, self.hof)
+            roles[ri] = L.GaSelectRole(None if gathered else L._p(self.dist[r]), None if gathered else rewards_ptr_of(ri),
+                                       L._p(self.div[r]), L._p(self.fitness[r]), L._p(self.order[r]), L._p(self.best_dist[r]),
+                                       0 if gathered else game_first_of(ri), RET_SLOT[r])
+        return roles
+
+    def _select_roles(self, rewards_ptr_of, game_first_of, games_per_individual):
+        L.call("coevo_ga_select", self._select_role_block(rewards_ptr_of, game_first_of), 3, self.pop, games_per_individual,
+               self.hof)
 
     def _select_unfused(self, rewards_ptr_of, game_first_of, games_per_individual):
         for ri, r in enumerate(ROLES):
@@ -332,7 +361,7 @@ class CoGATail:
             roles[ri] = L.GaPromoteRole(self._ptr(r, "pop"), self._ptr(r, "hof"), self._ptr(r, "elite"),
                                         L._p(self.order[r]), ROLE_D[r], 1 if elites_from_pop else 0,
                                         1 if best_to_pop0 else 0, 0)
-        tiled = getattr(self, "_hof_tiled", False)   # (GAEngine: the Hall of Fame has tile-major W2 twins that the rollout reads)
+        tiled = self._hof_tiled
         if tick and rebuild is None and tiled:
             L.call("coevo_ga_promote_tick_tiled", roles, 3, self.E, self.hof, L._p(self.gen_dev), L._p(self.hof_twin))
             return
@@ -366,7 +395,7 @@ class CoGATail:
             L.call("coevo_fc_gather", self._ptr(r, "hof_tmp"), L._p(self.iota), self._ptr(r, "hof"), 0,
                    self.hof - 1, D)
         L.call("coevo_fc_gather", self._ptr(r, "elite"), L._p(self.iota), self._ptr(r, "hof"), self.hof - 1, 1, D)
-        if getattr(self, "_hof_tiled", False):
+        if self._hof_tiled:
             self._refresh_hof_twins()
 
     def _best_to_pop0(self, r):
@@ -389,6 +418,23 @@ class CoGATail:
                L._p(self.dist_partial[r]))
         L.call(self._finalize_entry, L._p(self.dist_partial[r]), self.pblocks[r], c_hi - c_lo, L._p(self.dist[r]), 1 + c_lo,
                L._p(self.best_dist[r]) if c_lo == 0 else None)
+
+    def _breed_children_multi(self, c_lo, c_hi, sigma_ptrs, streams, gen_dev=None, tick=None):
+        """_breed_role_children of the three roles as one job each of the two multi launches: sigma_ptrs[ri], streams[ri] per
+        role; tick: the device counter that the distance reduction increments (a generation's last launch)"""
+        Job = getattr(L, self._perturb_job)
+        pj, fj = (Job * 3)(), (L.FinalizeJob * 3)()
+        for ri, r in enumerate(ROLES):
+            part = self.dist_partial[r].data_ptr() + 8 * c_lo * self.pblocks[r]
+            pj[ri] = Job(self._ptr(r, "elite"), self.parent_idx.data_ptr() + 4 * c_lo, self._ptr(r, "pop"), sigma_ptrs[ri],
+                         self._ptr(r, "stale"), part, 1 + c_lo, c_hi - c_lo, ROLE_D[r], c_lo, streams[ri], 0)
+            fj[ri] = L.FinalizeJob(part, self.dist[r].data_ptr(), self.best_dist[r].data_ptr() if c_lo == 0 else None,
+                                   self.pblocks[r], c_hi - c_lo, 1 + c_lo, 0)
+        L.call(self._perturb_multi_entry, ct.cast(pj, ct.c_void_p), 3, self.philox_seed, 0, gen_dev)
+        if tick is not None:
+            L.call(self._finalize_multi_entry + "_tick", ct.cast(fj, ct.c_void_p), 3, tick)
+        else:
+            L.call(self._finalize_multi_entry, ct.cast(fj, ct.c_void_p), 3)
 
 
 class CoESSchedule:

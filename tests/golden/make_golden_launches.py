@@ -14,6 +14,11 @@ DQNESEngine.generation each wrote the update sequence out and DQNESEngine built 
 fixture from a tree that has its mixin: in such a tree this script only CHECKS it (as do tests/test_ga_launch_scripts_cpu.py
 and tests/test_es_launch_scripts_cpu.py): it replays the same driver and compares record by record.
 
+ga_cohort_launch_scripts.json (COHORT_CASES) was minted the same way at the commit BEFORE population.co_ga_reset_segments
+existed: GAEngine's _breed_cohort / _reset_cohort called directly (they need no stream), its host-driven selection under
+hof_mean / population_sharing and HalfGAEngine's multi-role breeding; in a tree that has the function it is only checked
+(tests/test_ga_cohort_launch_scripts_cpu.py).
+
 A record is a list: ["call", entry point, arguments...], ["ro", method, arguments...], ["ro.new", class, ...] (the tables a
 DeepQN rollout is constructed with), ["upload", role, region, first, n], ["gather"] / ["gather_packed"], ["torch", ...].
 Integers and floats are stored as they are; a pointer as "<engine attribute>[key]+<byte offset>" resolved against the
@@ -52,6 +57,7 @@ import torch  # noqa: E402
 
 FIXTURE = os.path.join(HERE, "ga_launch_scripts.json")
 ES_FIXTURE = os.path.join(HERE, "es_launch_scripts.json")
+COHORT_FIXTURE = os.path.join(HERE, "ga_cohort_launch_scripts.json")
 ENV_KNOBS = ("COEVO_PACKED_EXCHANGE", "COEVO_PIPELINED", "COEVO_HEAVY_ROWS", "COEVO_HOST_COHORTS", "COEVO_DQN_COHORTS",
              "COEVO_DQN_FC1_LAYOUT", "COEVO_PERSISTENT", "COEVO_RESIDENT_MB", "COEVO_FRAME_COHORTS", "COEVO_ES_COHORTS",
              "COEVO_DQN_EVAL_GRAPH", "COEVO_DQN_EVAL_TILED")
@@ -134,10 +140,11 @@ class Recorder:
 
     def call(self, name, *args):
         from coevonet_amd import lib as L
-        sig = L._SIGS[name][1]
+        sig = (L._SIGS.get(name) or L._SH_SIGS[name])[1]   # (coevo.h, or the sharing modes' header)
         assert len(args) == len(sig) - 1, (name, len(args), len(sig))   # (+ the stream, which lib.call appends)
         arrays = {"coevo_fc_perturb_dist_multi": L.PerturbJob, "coevo_fc_distance_finalize_multi": L.FinalizeJob,
-                  "coevo_fc_distance_finalize_multi_tick": L.FinalizeJob}
+                  "coevo_fc_distance_finalize_multi_tick": L.FinalizeJob,
+                  "coevo_fc16_perturb_dist_multi": L.Perturb16Job, "coevo_fc16_distance_finalize_multi": L.FinalizeJob}
         rec = ["call", name]
         for i, (a, typ) in enumerate(zip(args, sig)):
             if isinstance(a, ct.c_void_p) and i == 0 and name in arrays:   # ctypes.cast(jobs, c_void_p): args[1] jobs
@@ -320,17 +327,17 @@ def _gather_packed(eng):
     REC.log.append(["gather_packed"])
 
 
-def _ga(pop, hof, elites, shard=(0, 1), packed=False):
+def _ga(pop, hof, elites, shard=(0, 1), packed=False, **kw):
     from coevonet_amd.genetic_algorithm import GAEngine
     REC.engine = GAEngine(pop, hof, elites, 40, 30, device="cpu", rng="device_philox", env="device", shard=shard,
-                          gather=_gather if shard[1] > 1 else None, gather_packed=_gather_packed if packed else None)
+                          gather=_gather if shard[1] > 1 else None, gather_packed=_gather_packed if packed else None, **kw)
     return REC.engine
 
 
-def ga_host(pop, hof, elites, shard=(0, 1), schedule=False):
+def ga_host(pop, hof, elites, shard=(0, 1), schedule=False, **modes):
     """the host-driven generation: [rollout] select breed_device, twice (the second round finds _dist_current set on the
     fused path; a sharded generation 1 rebuilds the elites), [then the flush of the last evaluation games]"""
-    eng = _ga(pop, hof, elites, shard)
+    eng = _ga(pop, hof, elites, shard, **modes)
     for gen in range(2):
         if schedule:
             eng.rollout(gen, with_prev_eval=gen > 0)
@@ -354,9 +361,9 @@ def ga_sharded_loop(pop, hof, elites, shard, packed=False):
         eng.step_sharded(gen)
 
 
-def ga_half(pop, hof, elites):
+def ga_half(pop, hof, elites, **kw):
     from coevonet_amd.ga_half import HalfGAEngine
-    eng = REC.engine = HalfGAEngine(pop, hof, elites, 40, 30, device="cpu")
+    eng = REC.engine = HalfGAEngine(pop, hof, elites, 40, 30, device="cpu", **kw)
     for gen in range(2):
         eng.rollout(gen)
         eng.select()
@@ -397,6 +404,44 @@ CASES = {
     "dqn_ga_pop_1": lambda: dqn(False, 1),
     "dqn_ga_half": lambda: dqn(True, 3),
     "dqn_ga_half_pop_1": lambda: dqn(True, 1),
+}
+
+
+# ------------------------------------------------------------------------------------------- the cohort and sharing cases
+def ga_cohorts(pop, hof, elites, cohorts, bounds, shard=(0, 1), from_counter=False):
+    """what a cohort's stream is handed in the pipelined loop, generations 0..2, called directly (no stream needed): the
+    deferred breeding of the cohort's children (from generation 1 on: those of generation gen - 1), then the reset of its
+    games.  from_counter: the children of generation gen with the generation read from the device counter, whose tick rides
+    in the distance reduction (the K = 1 tail of the packed exchange), before the reset of generation gen + 1's games."""
+    eng = _ga(pop, hof, elites, shard, cohorts=cohorts)
+    assert eng.K == cohorts and eng.cohort_bounds.tolist() == bounds, (eng.K, eng.cohort_bounds)
+    eng.setup_device_loop(LOOP_ARGS, 16)
+    for gen in range(3):
+        for k in reversed(range(eng.K)):   # (the order of _enqueue_cohort_chains: the caller's stream, cohort 0, last)
+            if from_counter:
+                eng._reset_cohort(k, gen)
+                eng._breed_cohort(k, gen, eng.gen_dev.data_ptr(), True)
+            else:
+                if gen > 0:
+                    eng._breed_cohort(k, gen - 1)
+                eng._reset_cohort(k, gen)
+
+
+COHORT_CASES = {
+    # cohort 0 holds individual 0 (the max(lo_k, 1) - 1 clamp, the best_dist head); the evaluation games go with the last
+    # cohort from generation 1 on
+    "ga_cohorts_2_of_6": lambda: ga_cohorts(6, 2, 2, 2, [0, 3, 6]),
+    "ga_cohorts_2_of_6_from_counter": lambda: ga_cohorts(6, 2, 2, 2, [0, 3, 6], from_counter=True),
+    "ga_cohorts_3_of_7_uneven": lambda: ga_cohorts(7, 3, 2, 3, [0, 2, 4, 7]),
+    # cohort 0 holds only the unchanged best: no breeding launch, dist[0] := best_dist, the counter's tick on its own
+    "ga_cohorts_only_the_best": lambda: ga_cohorts(2, 1, 1, 2, [0, 1, 2]),
+    "ga_cohorts_only_the_best_from_counter": lambda: ga_cohorts(2, 1, 1, 2, [0, 1, 2], from_counter=True),
+    "ga_cohorts_shard_1_of_2": lambda: ga_cohorts(12, 2, 2, 2, [0, 3, 6], shard=(1, 2)),
+    # the launch-per-step selection of the two sharing modes (the second generation finds _dist_current set)
+    "ga_host_hof_mean": lambda: ga_host(5, 3, 2, hof_mean=True),
+    "ga_host_population_sharing": lambda: ga_host(5, 3, 2, population_sharing=True),
+    "ga_host_hof_mean_population_sharing": lambda: ga_host(5, 3, 2, hof_mean=True, population_sharing=True),
+    "ga_half_multi_breed": lambda: ga_half(5, 3, 2, multi_breed=True),
 }
 
 
@@ -492,6 +537,10 @@ def mint_es():
     return mint(ES_CASES)
 
 
+def mint_cohorts():
+    return mint(COHORT_CASES)
+
+
 def first_difference(got, want):
     """-> None, or (case, record index, got record, wanted record) of the first record that differs"""
     for case in sorted(set(got) | set(want)):
@@ -529,4 +578,8 @@ if __name__ == "__main__":
     status |= _check_or_write(mint_es(), ES_FIXTURE, "CoESUpdate",
                               "launch scripts of the Co-ES engines before population.CoESUpdate (make_golden_launches.py); "
                               "the cohort chains of the rollouts and the real graph capture are left to the GPU tests")
+    status |= _check_or_write(mint_cohorts(), COHORT_FIXTURE, "co_ga_reset_segments",
+                              "launch scripts of GAEngine's cohort breeding and resets, of its selection under hof_mean / "
+                              "population_sharing and of HalfGAEngine's multi-role breeding, before "
+                              "population.co_ga_reset_segments (make_golden_launches.py)")
     sys.exit(status)

@@ -514,3 +514,50 @@ def test_co_ga_rollout_resets_every_game_to_its_ordinal_in_the_seeded_stream(one
                 assert ordinal[(ph * n_local + i) * hof + k] == 7 + 2 * per_gen + (ph * pop + lo + i) * hof + k
     assert [ordinal[s.n_main + j] for j in range(N_EVAL)] == [7 + per_gen + 3 * pop * hof + j for j in range(N_EVAL)]
     assert len(ordinal) == s.n_main + N_EVAL and s.ro.limits == [30] * s.n_main + [20] * N_EVAL and s.ro.cycles == 10
+
+
+# ---- co_ga_reset_segments: every (pop, hof, world, rank, cohorts) of a small grid, nothing sampled
+def _cohort_bounds(n_local, K):
+    return [k * n_local // K for k in range(K + 1)]
+
+
+SEGMENT_GRID = [(pop, hof, world, rank, K) for pop, hof in ((2, 1), (6, 2), (7, 3), (12, 2)) for world in (1, 2)
+                if pop % world == 0 for rank in range(world) for K in (1, 2, 3) if K <= pop // world]
+
+
+@pytest.mark.parametrize("pop,hof,world,rank,K", SEGMENT_GRID)
+@pytest.mark.parametrize("gen", [0, 1, 3])
+def test_reset_segments_cover_every_game_of_the_rank_once_under_its_ordinal(pop, hof, world, rank, K, gen):
+    """over the cohorts (the evaluation games with the last, from generation 1 on) the segments cover each of the rank's
+    3 n_local hof games exactly once, game ph n_local hof + (i - lo) hof + j under the ordinal first_ordinal + gen (3 pop hof +
+    N_EVAL) + ph pop hof + i hof + j; the evaluation segment starts behind the main games of generation gen - 1"""
+    first_ordinal, per_gen = 7, 3 * pop * hof + N_EVAL
+    lo, n_local = rank * pop // world, pop // world
+    base, base_prev = first_ordinal + gen * per_gen, first_ordinal + (gen - 1) * per_gen
+    n_main, bounds = 3 * n_local * hof, _cohort_bounds(n_local, K)
+    ordinal = np.full(n_main + N_EVAL, -1, dtype=np.int64)
+    for k in range(K):
+        segs = P.co_ga_reset_segments(base, base_prev, pop, hof, lo, n_local, lo + bounds[k], lo + bounds[k + 1],
+                                      k == K - 1 and gen > 0)
+        assert len(segs) == (4 if k == K - 1 and gen > 0 else 3)
+        for first, n, o in segs:
+            assert (ordinal[first:first + n] == -1).all() and first + n <= len(ordinal)
+            ordinal[first:first + n] = o + np.arange(n)
+        if len(segs) == 4:
+            assert segs[3] == (n_main, N_EVAL, base_prev + 3 * pop * hof)
+    ph, i, j = np.meshgrid(np.arange(3), np.arange(lo, lo + n_local), np.arange(hof), indexing="ij")
+    want = np.full(n_main + N_EVAL, -1, dtype=np.int64)
+    want[(ph * n_local * hof + (i - lo) * hof + j).ravel()] = (first_ordinal + gen * per_gen + ph * pop * hof + i * hof + j).ravel()
+    if gen > 0:
+        want[n_main:] = first_ordinal + (gen - 1) * per_gen + 3 * pop * hof + np.arange(N_EVAL)
+    assert (want[:n_main] >= 0).all() and np.array_equal(ordinal, want)
+
+
+@pytest.mark.parametrize("pop,hof", [(2, 1), (5, 3), (6, 2)])
+def test_reset_segments_of_generation_0_are_what_the_counter_driven_reset_hands_its_kernel(pop, hof):
+    """GAEngine._enqueue_resets: the kernel adds generation x per_gen to the segments of generation 0 with the evaluation games,
+    whose first ordinal therefore lies one generation BEFORE the first"""
+    first_ordinal, per_gen, per_phase = 7, 3 * pop * hof + N_EVAL, pop * hof
+    segs = P.co_ga_reset_segments(first_ordinal, first_ordinal - per_gen, pop, hof, 0, pop, 0, pop, True)
+    assert segs == [(ph * per_phase, per_phase, first_ordinal + ph * per_phase) for ph in range(3)] + [
+        (3 * per_phase, N_EVAL, first_ordinal - per_gen + 3 * per_phase)]
