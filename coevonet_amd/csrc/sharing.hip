@@ -18,27 +18,13 @@
 //   * partial sums go to scratch [slab][i][j] (i < j), and a second launch adds them in slab order, takes the root and writes
 //     dist[i][j] and dist[j][i] from the same words: symmetric bits, no atomics, a fixed order for given (n, D).
 #include "coevo_common.hip.h"
+#include "pairwise_tiles.hip.h"
 
 #include "../../include/coevo_sharing.h"
 
 namespace coevo {
 
-constexpr int PW_TILE = 32;      // nets per tile side
-constexpr int PW_CHUNK = 64;     // entries per net and LDS piece (the stride is a multiple of 64)
-constexpr int PW_ROW = PW_CHUNK + 4;
-constexpr int PW_MAX_SLABS = 64;
-constexpr int PW_TARGET_WGS = 2048;   // ~8 workgroups of 4 waves per CU
-
-static inline int pw_tiles(int n) { return (n + PW_TILE - 1) / PW_TILE; }
-static inline int pw_tile_pairs(int n) { return pw_tiles(n) * (pw_tiles(n) + 1) / 2; }
-// slabs of the parameter axis: enough workgroups at a small population (pop 200: 28 tile pairs), one slab at a large one
-static inline int pw_slabs(int n, int D)
-{
-    const int chunks = (int)(fc_stride(D) / PW_CHUNK);
-    int s = (PW_TARGET_WGS + pw_tile_pairs(n) - 1) / pw_tile_pairs(n);
-    s = s > PW_MAX_SLABS ? PW_MAX_SLABS : s;
-    return s > chunks ? chunks : s;
-}
+static inline int pw_slabs(int n, int D) { return pw_slabs_of(n, (int)(fc_stride(D) / PW_CHUNK)); }
 
 // one thread's four 16-byte pieces of an LDS piece: piece f = threadIdx.x + 256 m covers row f / 16 (0-31 the i-tile, 32-63 the
 // j-tile), entries 4 (f % 16) ..; excluded words (LayerNorm, padding, nets past n) come back as +0.0
@@ -81,13 +67,8 @@ __global__ __launch_bounds__(256) void fc_pairwise_partial_kernel(const float *p
 {
     __shared__ float4 sh[2 * PW_TILE][PW_ROW / 4];
     const int stride = (int)fc_stride(D), P = (int)fc_params(D), g1 = (int)fc_off_g1(D), g2 = (int)fc_off_g2(D);
-    const int nb = (n + PW_TILE - 1) / PW_TILE;
-    int bi = 0, rem = (int)blockIdx.x;   // tile pair number -> (bi, bj), bi <= bj, row by row of the upper triangle
-    while (rem >= nb - bi) { rem -= nb - bi; ++bi; }
-    const int bj = bi + rem;
-    const int i0 = bi * PW_TILE, j0 = bj * PW_TILE;
-    const int chunks = stride / PW_CHUNK, slab = (int)blockIdx.y;
-    const int c_lo = (int)((int64_t)slab * chunks / n_slabs), c_hi = (int)((int64_t)(slab + 1) * chunks / n_slabs);
+    const PwBlock B = pw_block(n, stride / PW_CHUNK, n_slabs);
+    const int i0 = B.i0, j0 = B.j0, c_lo = B.c_lo, c_hi = B.c_hi, slab = B.slab;
     const int tj = threadIdx.x & 15, ti = threadIdx.x >> 4;
     double acc00 = 0.0, acc01 = 0.0, acc10 = 0.0, acc11 = 0.0;   // (ti, tj), (ti, tj + 16), (ti + 16, tj), (ti + 16, tj + 16)
     float4 next[4];

@@ -11,7 +11,10 @@ one GPU.  The rounding points are the float16 contract of DESIGN.md "float16 net
 One cohort, device env, ``device_philox`` offspring; the caller passes the mutation powers per generation, so the host's
 adaptive rule sits on top.  ``GATrainer`` / ``genetic_algorithm_train`` build this engine under ``args.precision == "float16"``
 with ``multi_breed=True``: the three roles' children and distances in one launch each (coevo_fc16_perturb_dist_multi,
-coevo_fc16_distance_finalize_multi) in place of six."""
+coevo_fc16_distance_finalize_multi) in place of six.
+
+``hof_mean`` / ``population_sharing``: the two Co-GA extension modes of ``GAEngine`` (not the reference's
+algorithm), the pairwise distances in the float16 contract (coevo_fc16_pairwise_distance, include/coevo_sharing16.h)."""
 from __future__ import annotations
 
 import numpy as np
@@ -37,10 +40,16 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
     _perturb_job = "Perturb16Job"
     _perturb_multi_entry = "coevo_fc16_perturb_dist_multi"
     _finalize_multi_entry = "coevo_fc16_distance_finalize_multi"
+    _pairwise_entry = "coevo_fc16_pairwise_distance"
+    _pairwise_scratch_entry = "coevo_fc16_pairwise_scratch_doubles"
 
     def __init__(self, pop, hof, elites, limit_train=None, limit_eval=None, max_cycles=25, device="cuda",
                  env_seed=ENV_SEED, philox_seed=0, first_ordinal=1, *, adaptive=False, shard=(0, 1), env="device",
-                 rng="device_philox", multi_breed=False):
+                 rng="device_philox", multi_breed=False, hof_mean=False, population_sharing=False):
+        # the two Co-GA extension modes (NOT the reference's algorithm), as GAEngine has them: fitness over every
+        # Hall-of-Fame game, and sharing by a niche count per individual over all pairwise fp16 distances.  Off: nothing changes.
+        # (Their limit, COEVO_SHARING_MAX_POP, is the fused tail's FUSED_MAX_POP, refused below.)
+        self.hof_mean, self.population_sharing = bool(hof_mean), bool(population_sharing)
         # what float16 does not cover is refused before the library is loaded
         if adaptive:
             raise ValueError("HalfGAEngine: adaptive mutation power is not built for precision float16")
@@ -83,6 +92,8 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
         self.dist_partial = {r: torch.zeros(pop * self.pblocks[r], dtype=torch.float64, device=device) for r in ROLES}
         self.parent_idx = torch.tensor([c % elites for c in range(pop - 1)], dtype=torch.int32, device=device)
         self._dist_current = False
+        if self.population_sharing:
+            self._sharing_buffers()
         self.multi_breed = bool(multi_breed)   # breed(): one launch each for the three roles' children and distances
         self.steps_per_generation = 3 * pop * hof * self.T_train + N_EVAL * self.T_eval
 
@@ -97,16 +108,27 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
         super().rollout(gen, gen > 0)
 
     def select(self):
-        """fitness sharing + fitness + ranking of the three roles in one launch; the elite ids stay on the device"""
+        """fitness sharing + fitness + ranking of the three roles in one launch; the elite ids stay on the device.  Under
+        hof_mean / population_sharing: GAEngine's launch-per-step sequence per role (CoGATail._select_shared), the pairwise
+        distances in the float16 contract"""
         self.ro.check_status()
-        if not self._dist_current:   # generation 0, or a population loaded from the host
-            for r in ROLES:
-                L.call("coevo_fc16_distance", self._ptr(r, "stale"), self._ptr(r, "pop"), self.pop, ROLE_D[r],
-                       L._p(self.dist_partial[r]))
-                L.call("coevo_fc16_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop,
-                       L._p(self.dist[r]), 0, None)
-            self._dist_current = True
-        self._select_roles(lambda ri: L._p(self.ro.rewards), lambda ri: ri * self.pop * self.hof, self.hof)
+        if self.hof_mean or self.population_sharing:
+            self._select_shared(L._p(self.ro.rewards), self.pop * self.hof)
+        else:
+            self._stale_distances(ROLES)
+            self._select_roles(lambda ri: L._p(self.ro.rewards), lambda ri: ri * self.pop * self.hof, self.hof)
+        self._dist_current = True
+
+    def _stale_distances(self, roles):
+        """dist of `roles`: the distances of the population to the stale agent (Q3) in the float16 contract - unless breed()
+        left them current (generation 0, or a population loaded from the host: not)"""
+        if self._dist_current:
+            return
+        for r in roles:
+            L.call("coevo_fc16_distance", self._ptr(r, "stale"), self._ptr(r, "pop"), self.pop, ROLE_D[r],
+                   L._p(self.dist_partial[r]))
+            L.call("coevo_fc16_distance_finalize", L._p(self.dist_partial[r]), self.pblocks[r], self.pop,
+                   L._p(self.dist[r]), 0, None)
 
     def breed(self, gen, sigmas):
         """elites -> elite buffer, HoF FIFO, population := [best] + (pop - 1) mutated clones (child c at pop[1 + c] from
@@ -128,7 +150,8 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
 
     def run(self, generations, sigmas):
         """`generations` whole generations with fixed mutation powers `sigmas` {role: sigma} -> {"elite_ids": [per generation
-        {role: ids}], "eval_rewards": [per generation mean triple], "diversity": [per generation {role: float32}]}"""
+        {role: ids}], "eval_rewards": [per generation mean triple], "diversity": [per generation {role: float32}, under
+        population_sharing {role: mean_niche()}]}"""
         out = {"elite_ids": [], "eval_rewards": [], "diversity": []}
         for gen in range(generations):
             self.rollout(gen)
@@ -136,7 +159,7 @@ class HalfGAEngine(SlabIO, CoGASchedule, CoGATail):
                 out["eval_rewards"].append(self.eval_rewards())
             self.select()
             out["elite_ids"].append(self.elite_ids())
-            out["diversity"].append(self.diversity())
+            out["diversity"].append(dict(zip(ROLES, self.mean_niche())) if self.population_sharing else self.diversity())
             self.breed(gen, sigmas)
         if generations > 0:
             out["eval_rewards"].append(self.eval_only(generations - 1))

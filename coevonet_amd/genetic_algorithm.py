@@ -271,11 +271,8 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         # the rollout's closing launch, and the all-gathered [rank][role][j][4] buffer the selection reads as it is
         self.pack_local = torch.zeros(3, self.n_local, 4, dtype=torch.float64, device=device)
         self.pack_all = torch.zeros(self.world, 3, self.n_local, 4, dtype=torch.float64, device=device)
-        if self.population_sharing:   # all pairwise distances [pop][pop] and the niche counts [pop] of every role: this mode's only
-            self.pair_dist = {r: torch.zeros(pop, pop, **f32) for r in ROLES}
-            self.niche = {r: torch.zeros(pop, **f32) for r in ROLES}
-            n_scratch = max(int(L.load().coevo_fc_pairwise_scratch_doubles(pop, ROLE_D[r])) for r in ROLES)
-            self.pair_scratch = torch.zeros(n_scratch, dtype=torch.float64, device=device)
+        if self.population_sharing:
+            self._sharing_buffers()
         self.parent_idx = torch.tensor([c % elites for c in range(max(pop - 1, 1))], dtype=torch.int32, device=device)
         self.hof_shift_idx = torch.arange(1, max(hof, 2), dtype=torch.int32, device=device)
         self.iota = torch.arange(max(hof, elites, 2), dtype=torch.int32, device=device)
@@ -356,7 +353,7 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
             dev_rewards = self._rewards_dev
         per_phase = self.n_local * self.hof
         if self.hof_mean or self.population_sharing:
-            self._select_shared(dev_rewards, per_phase)
+            self._select_shared(L._p(dev_rewards), per_phase)
             return
         if self._fused_host_tail():
             self._stale_distances(ROLES)  # (generation 0, or a population loaded from the host)
@@ -380,33 +377,6 @@ class GAEngine(SlabIO, CoGASchedule, CoGATail):
         for r in roles:
             L.call("coevo_fc_distance", self._ptr(r, "stale"), self._ptr(r, "pop", first), self.pop if n is None else n,
                    ROLE_D[r], self.dist[r].data_ptr() + 4 * first)
-
-    def _select_shared(self, dev_rewards, per_phase):
-        """select() under hof_mean / population_sharing (one rank, the whole population here), launch per step and role:
-        the share - niche counts over all pairwise distances, or today's score against the stale agent -, the fitness with
-        the mode's switches, the ranking, and the best individual's stale-agent distance, which breed_device's fused promotion
-        hands to the children's distances: the stale-agent chain stays valid in either mode"""
-        flags =((L.K_SH["COEVO_FIT_HOF_MEAN"] if self.hof_mean else 0)
-                 | (L.K_SH["COEVO_FIT_PER_INDIVIDUAL"] if self.population_sharing else 0))
-        for ri, r in enumerate(ROLES):
-            D = ROLE_D[r]
-            self._stale_distances((r,))
-            if self.population_sharing:
-                L.call("coevo_fc_pairwise_distance", self._ptr(r, "pop"), self.pop, D, L._p(self.pair_scratch),
-                       L._p(self.pair_dist[r]))
-                L.call("coevo_niche_counts", L._p(self.pair_dist[r]), self.pop, L._p(self.niche[r]))
-                share = self.niche[r]
-            else:
-                L.call("coevo_sharing_score", L._p(self.dist[r]), self.pop, L._p(self.div[r]))
-                share = self.div[r]
-            L.call("coevo_ga_fitness_shared", L._p(dev_rewards), ri * per_phase, self.pop, self.hof, self.hof, RET_SLOT[r], flags,
-                   L._p(share), L._p(self.fitness[r]))
-            L.call("coevo_rank_desc", L._p(self.fitness[r]), self.pop, L._p(self.order[r]))
-            L.call("coevo_gather_f32", L._p(self.best_dist[r]), L._p(self.dist[r]), L._p(self.order[r]), 1)
-
-    def mean_niche(self):
-        """per role the fp64 mean of the niche counts, computed on the host (population_sharing)"""
-        return [float(np.mean(self.niche[r].cpu().numpy().astype(np.float64))) for r in ROLES]
 
     def breed_device(self, gen, sigmas):
         """elites -> elite buffer, HoF FIFO, population := [best] + (pop-1) mutated clones, all on the device.

@@ -22,6 +22,7 @@ HEADER_PATH = os.path.join(HERE, "..", "include", "coevo.h")
 EXT_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_ext.h")   # additions that are not yet part of the pinned ABI
 CROSSPLAY_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_crossplay.h")   # the cross-play entry points, likewise
 SHARING_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_sharing.h")   # the Co-GA population-sharing entry points, likewise
+SHARING16_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_sharing16.h")   # ... and their float16 pairwise distance
 
 
 class CoevoError(RuntimeError):
@@ -171,6 +172,20 @@ def _parse_sharing_header(text):
 
 K_SH, _SH_SIGS = _parse_sharing_header(_header_text(SHARING_HEADER_PATH))
 
+
+def _parse_sharing16_header(text):
+    """include/coevo_sharing16.h -> its entry points, read like coevo_sharing.h: prototypes and constants only, and no name
+    that one of the four other headers declares"""
+    consts, structs, sigs = parse_header(text, known=STRUCTS)
+    if (set(structs) != set(STRUCTS) or set(sigs) & (set(_SIGS) | set(_EXT_SIGS) | set(_XP_SIGS) | set(_SH_SIGS))
+            or set(consts) & (set(K) | set(K_EXT) | set(K_XP) | set(K_SH))):
+        raise CoevoError("include/coevo_sharing16.h: declares a struct or repeats a name of include/coevo.h, "
+                         "include/coevo_ext.h, include/coevo_crossplay.h or include/coevo_sharing.h")
+    return sigs
+
+
+_SH16_SIGS = _parse_sharing16_header(_header_text(SHARING16_HEADER_PATH))
+
 OBS_STRIDE, LOGIT_STRIDE, FC_MAX_ROWS = K["COEVO_OBS_STRIDE"], K["COEVO_LOGIT_STRIDE"], K["COEVO_FC_MAX_ROWS"]
 MPE_STATE_DOUBLES, STAMP_SLOTS = K["COEVO_MPE_STATE_DOUBLES"], K["COEVO_STAMP_SLOTS"]
 ST_NAMES = {K["COEVO_ST_BAD_INPUT"]: "input contains inf or NaN",
@@ -239,6 +254,11 @@ def sharing_symbols():
     return sorted(_SH_SIGS)
 
 
+def sharing16_symbols():
+    """the entry points of include/coevo_sharing16.h, bound by load() beside the four other tables"""
+    return sorted(_SH16_SIGS)
+
+
 def load():
     """dlopen libcoevo.so; raises CoevoError when it has not been built (python -m coevonet_amd.build)."""
     global _lib
@@ -247,7 +267,7 @@ def load():
             raise CoevoError(f"{LIB_PATH} is missing: build the HIP extension first "
                              "(python -m coevonet_amd.build); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_EXT_SIGS, **_XP_SIGS, **_SH_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_EXT_SIGS, **_XP_SIGS, **_SH_SIGS, **_SH16_SIGS}.items():
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

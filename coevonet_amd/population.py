@@ -323,13 +323,15 @@ class CoGATail:
     the three roles: fused_tail_fits) and its launch-per-step form.  A class names its promotion, child and distance-reduction
     entry points and the job struct and entry points of the multi-role breeding.  Needs pop, hof, E, philox_seed, slab / base /
     stride (SlabIO._ptr), dist, div, fitness, order, best_dist, dist_partial, pblocks, parent_idx and, for the launch-per-step
-    forms, iota and hof_shift_idx."""
+    forms, iota and hof_shift_idx; for the extension modes hof_mean / population_sharing, device and _stale_distances(roles)."""
     _promote_entry = "coevo_ga_promote"
     _perturb_dist_entry = "coevo_fc_perturb_dist"
     _finalize_entry = "coevo_fc_distance_finalize"
     _perturb_job = "PerturbJob"
     _perturb_multi_entry = "coevo_fc_perturb_dist_multi"
     _finalize_multi_entry = "coevo_fc_distance_finalize_multi"
+    _pairwise_entry = "coevo_fc_pairwise_distance"                  # population_sharing: all pairwise distances
+    _pairwise_scratch_entry = "coevo_fc_pairwise_scratch_doubles"
     _hof_tiled = False   # (GAEngine may turn it on: the Hall of Fame then has tile-major W2 twins that the rollout reads)
 
     def _select_role_block(self, rewards_ptr_of, game_first_of, gathered=False):
@@ -435,6 +437,42 @@ class CoGATail:
             L.call(self._finalize_multi_entry + "_tick", ct.cast(fj, ct.c_void_p), 3, tick)
         else:
             L.call(self._finalize_multi_entry, ct.cast(fj, ct.c_void_p), 3)
+
+    # ---- the Co-GA extension modes hof_mean / population_sharing: one rank, the whole population here
+    def _sharing_buffers(self):
+        """population_sharing: all pairwise distances [pop][pop] and the niche counts [pop] of every role and the scratch
+        of the pairwise launch - this mode's only buffers"""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.pair_dist = {r: torch.zeros(self.pop, self.pop, **f32) for r in ROLES}
+        self.niche = {r: torch.zeros(self.pop, **f32) for r in ROLES}
+        n_scratch = max(int(getattr(L.load(), self._pairwise_scratch_entry)(self.pop, ROLE_D[r])) for r in ROLES)
+        self.pair_scratch = torch.zeros(n_scratch, dtype=torch.float64, device=self.device)
+
+    def _select_shared(self, rewards_ptr, per_phase):
+        """select() under hof_mean / population_sharing, launch per step and role: the stale-agent distances where they are
+        not current (_stale_distances), the share - niche counts over all pairwise distances, or today's score against the
+        stale agent -, the fitness with the mode's switches, the ranking, and the best individual's stale-agent distance,
+        which the promotion hands to the children's distances: the stale-agent chain stays valid in either mode"""
+        flags =((L.K_SH["COEVO_FIT_HOF_MEAN"] if self.hof_mean else 0)
+                 | (L.K_SH["COEVO_FIT_PER_INDIVIDUAL"] if self.population_sharing else 0))
+        for ri, r in enumerate(ROLES):
+            D = ROLE_D[r]
+            self._stale_distances((r,))
+            if self.population_sharing:
+                L.call(self._pairwise_entry, self._ptr(r, "pop"), self.pop, D, L._p(self.pair_scratch), L._p(self.pair_dist[r]))
+                L.call("coevo_niche_counts", L._p(self.pair_dist[r]), self.pop, L._p(self.niche[r]))
+                share = self.niche[r]
+            else:
+                L.call("coevo_sharing_score", L._p(self.dist[r]), self.pop, L._p(self.div[r]))
+                share = self.div[r]
+            L.call("coevo_ga_fitness_shared", rewards_ptr, ri * per_phase, self.pop, self.hof, self.hof, RET_SLOT[r], flags,
+                   L._p(share), L._p(self.fitness[r]))
+            L.call("coevo_rank_desc", L._p(self.fitness[r]), self.pop, L._p(self.order[r]))
+            L.call("coevo_gather_f32", L._p(self.best_dist[r]), L._p(self.dist[r]), L._p(self.order[r]), 1)
+
+    def mean_niche(self):
+        """per role the fp64 mean of the niche counts, computed on the host (population_sharing)"""
+        return [float(np.mean(self.niche[r].cpu().numpy().astype(np.float64))) for r in ROLES]
 
 
 class CoESSchedule:
