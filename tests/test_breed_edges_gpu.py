@@ -11,7 +11,7 @@ import torch
 
 from coevonet_amd import lib as L
 from oracle import ref_port as rp
-from tests import breed_cases as bc
+from tests import breed_cases as bc, tile_major_cases as tm
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -405,10 +405,14 @@ def test_promote_rebuild_in_place_vs_numpy(E, hof, n_roles, gen):
 
 
 # ------------------------------------------------------------------------------------------- 6. promotion
-def promote_case(E, hof, n_roles, tick, variant):
+def promote_roles_of(E, hof, n_roles, variant, raw_w2=False):
+    """n_roles roles of mixed width with random nets in pop / hof / elite (raw_w2: tm.raw_words in the fc2.weight block of
+    every net - NaN payloads, infinities, -0.0, subnormals) -> (roles, per role: ids, from_pop, to_pop0, the three slabs, their
+    rows before the launch, the order tensor)"""
     n_pop = 10
     g = torch.Generator(device=DEV).manual_seed(1000 * E + 10 * hof + n_roles)
     rng = np.random.default_rng(E + hof)
+    raw = np.random.Generator(np.random.PCG64([E, hof, n_roles, variant]))
     roles, checks = (L.GaPromoteRole * n_roles)(), []
     for r in range(n_roles):
         D = ROLE_D[r]
@@ -416,6 +420,9 @@ def promote_case(E, hof, n_roles, tick, variant):
         pop, hofs, elite = Slab(n_pop, D), Slab(hof, D), Slab(E, D)
         for s in (pop, hofs, elite):
             s.t.copy_(torch.randn(s.t.shape, generator=g, device=DEV))
+            if raw_w2:
+                o = tm.w2_offset(D)
+                s.t[:, o:o + L.W2_FLOATS] = dev(tm.raw_words(raw, s.n * L.W2_FLOATS).reshape(s.n, -1))
         pop.t[0, 5], pop.t[n_pop - 1, 7], elite.t[0, 9] = float("nan"), float("inf"), -0.0
         if kind == 0:      # the best already sits in pop[0] and is written back onto itself; the rest distinct
             ids, from_pop, to_pop0 = [0] + list(1 + rng.permutation(n_pop - 1)[:E - 1]), 1, 1
@@ -428,6 +435,18 @@ def promote_case(E, hof, n_roles, tick, variant):
         order = dev(np.array(ids, dtype=np.int32)) if ids is not None else None
         roles[r] = L.GaPromoteRole(pop.p, hofs.p, elite.p, L._p(order), D, from_pop, to_pop0, 0)
         checks.append((ids, from_pop, to_pop0, pop, hofs, elite, pop.rows().copy(), hofs.rows().copy(), elite.rows().copy(), order))
+    return roles, checks
+
+
+def assert_regions(r, slabs, want):
+    for name, got, rows in zip(("pop", "hof", "elite"), (s.rows() for s in slabs), want):
+        assert len(got) == len(rows)
+        for k in range(len(rows)):
+            assert bc.same_bits(got[k], rows[k]), (r, name, k)
+
+
+def promote_case(E, hof, n_roles, tick, variant):
+    roles, checks = promote_roles_of(E, hof, n_roles, variant)
     cnt = Words(1, torch.int32, fill=41)
     if tick:
         L.call("coevo_ga_promote_tick", roles, n_roles, E, hof, cnt.p)
@@ -436,11 +455,7 @@ def promote_case(E, hof, n_roles, tick, variant):
     torch.cuda.synchronize()
     assert cnt.get()[0] == (42 if tick else 41)
     for r, (ids, from_pop, to_pop0, pop, hofs, elite, pop0, hof0, elite0, _) in enumerate(checks):
-        want_p, want_h, want_e = bc.promote(list(pop0), list(hof0), list(elite0), ids, E, from_pop, to_pop0)
-        for name, got, want in (("pop", pop.rows(), want_p), ("hof", hofs.rows(), want_h), ("elite", elite.rows(), want_e)):
-            assert len(got) == len(want)
-            for k in range(len(want)):
-                assert bc.same_bits(got[k], want[k]), (r, name, k)
+        assert_regions(r, (pop, hofs, elite), bc.promote(list(pop0), list(hof0), list(elite0), ids, E, from_pop, to_pop0))
 
 
 @pytest.mark.parametrize("n_roles", [1, 2, 3])
@@ -450,6 +465,105 @@ def test_promote_vs_list_operations(E, hof, n_roles):
     workgroups leave without writing: its regions end in guard rows), with and without the tick"""
     for variant in range(3 if n_roles == 1 else 2):
         promote_case(E, hof, n_roles, tick=(variant + n_roles) % 2 == 1, variant=variant)
+
+
+# ------------------------------------------------------------------------------------------- 6b. promotion with the twins
+class Twins:
+    """[n_roles][hof][W2_FLOATS] twin slots between PAD guard words (16 bytes: the slots stay 16-byte aligned), one further
+    role's worth of words behind the last role, all of it tm.raw_words: every slot distinct random bits with NaN payloads,
+    -0.0 and subnormals - NOT the twins of the Hall of Fame's nets, so that a slot that was recomputed instead of moved, or
+    moved the wrong way, shows"""
+
+    def __init__(self, n_roles, hof, seed):
+        self.n_roles, self.hof = n_roles, hof
+        n = (n_roles + 1) * hof * L.W2_FLOATS
+        self.before = tm.raw_words(np.random.Generator(np.random.PCG64([seed, n_roles, hof])), n + 2 * PAD)
+        self.buf = dev(self.before)
+        self.p = self.buf.data_ptr() + 4 * PAD
+        assert self.p % 16 == 0
+
+    def slots(self, a=None):
+        """-> [n_roles + 1][hof][W2_FLOATS] uint32 (of `a`, or of the device buffer after asserting its guard words)"""
+        if a is None:
+            a = self.buf.cpu().numpy()
+            assert bc.same_bits(a[:PAD], self.before[:PAD]) and bc.same_bits(a[-PAD:], self.before[-PAD:]), "a guard word was written"
+        return a[PAD:-PAD].view(np.uint32).reshape(self.n_roles + 1, self.hof, L.W2_FLOATS)
+
+    def untouched(self):
+        return bc.same_bits(self.buf.cpu().numpy(), self.before)
+
+
+def promote_tiled_case(E, hof, n_roles, variant, launches=1):
+    """coevo_ga_promote_tick_tiled, `launches` times back to back on the same buffers: pop / hof / elite and the counter as
+    coevo_ga_promote_tick leaves them (bc.promote), the twins as tm.promote_tiled's FIFO - the old slots moved as the words
+    they are, the last one twin_of the best's fc2.weight as it was before that launch"""
+    roles, checks = promote_roles_of(E, hof, n_roles, variant, raw_w2=True)
+    twins, cnt = Twins(n_roles, hof, seed=7 + variant), Words(1, torch.int32, fill=41)
+    old = twins.slots(twins.before.copy())
+    for _ in range(launches):
+        L.call("coevo_ga_promote_tick_tiled", roles, n_roles, E, hof, cnt.p, twins.p)
+    torch.cuda.synchronize()
+    assert cnt.get()[0] == 41 + launches
+    got = twins.slots()
+    for r, (ids, from_pop, to_pop0, pop, hofs, elite, pop0, hof0, elite0, _) in enumerate(checks):
+        D = ROLE_D[r]
+        state = (list(pop0), list(hof0), list(elite0), [old[r, j] for j in range(hof)])
+        for _ in range(launches):
+            state = tm.promote_tiled(*state, ids, E, from_pop, to_pop0, lambda row: tm.w2_of_slab_row(row, D))
+        assert_regions(r, (pop, hofs, elite), state[:3])
+        for j, want in enumerate(state[3]):
+            bad = np.flatnonzero(got[r, j] != want.view(np.uint32))
+            assert not len(bad), (r, "twin slot", j, "of", hof, len(bad), bad[:4])
+    assert np.array_equal(got[n_roles], old[n_roles]), "words behind the last role's twins were written"
+
+
+@pytest.mark.parametrize("n_roles", [1, 2, 3])
+@pytest.mark.parametrize("E,hof", [(1, 1), (1, 16), (8, 1), (8, 16), (3, 2)])
+def test_promote_tiled_vs_list_operations(E, hof, n_roles):
+    """the corners of test_promote_vs_list_operations through ga_promote_tiled_kernel: promote_twin_shift<1..15> at hof 1 (no
+    level stores), 2 and 16 (every level does), the clamped loads of the surplus levels, the D = 8 role's surplus workgroups
+    beside a D = 10 role, the best in pop[0] written onto itself, elites_from_pop = 0"""
+    for variant in range(3 if n_roles == 1 else 2):
+        promote_tiled_case(E, hof, n_roles, variant)
+
+
+@pytest.mark.parametrize("E,hof,n_roles", [(3, 2, 3), (1, 1, 2), (8, 16, 1)])
+def test_promote_tiled_twice_is_the_two_step_fifo(E, hof, n_roles):
+    for variant in range(2):
+        promote_tiled_case(E, hof, n_roles, variant, launches=2)
+
+
+def test_promote_tiled_refusals_write_nothing():
+    E, hof, n_roles = 2, 2, 2
+    roles, checks = promote_roles_of(E, hof, n_roles, 0, raw_w2=True)
+    twins, cnt = Twins(n_roles, hof, seed=3), Words(1, torch.int32, fill=41)
+    lib, st = L.load(), L._stream()
+
+    def call(roles=roles, n_roles=n_roles, E=E, hof=hof, counter=cnt.p, tw=twins.p):
+        return lib.coevo_ga_promote_tick_tiled(roles, n_roles, E, hof, counter, tw, st)
+
+    def edited(**fields):
+        """the roles with fields of role 1 replaced (a region moved 4 bytes: still inside its slab's allocation)"""
+        out = (L.GaPromoteRole * n_roles)()
+        for r in range(n_roles):
+            out[r] = L.GaPromoteRole(*(getattr(roles[r], f) for f, _ in L.GaPromoteRole._fields_))
+        for f, v in fields.items():
+            setattr(out[1], f, v(getattr(roles[1], f)) if callable(v) else v)
+        return out
+
+    assert call(counter=None) == ERR_ARG and call(tw=None) == ERR_ARG
+    assert call(tw=twins.p + 4) == ERR_ARG                                   # 4 bytes off 16-byte alignment
+    for region in ("pop", "hof", "elite"):
+        assert call(roles=edited(**{region: lambda p: p + 4})) == ERR_ARG, region
+    assert call(hof=17) == ERR_ARG and call(hof=0) == ERR_ARG
+    assert call(E=9) == ERR_ARG and call(E=0) == ERR_ARG
+    assert call(n_roles=0) == ERR_ARG and call(n_roles=4) == ERR_ARG
+    assert call(roles=edited(D=9)) == ERR_ARG
+    assert call(roles=edited(order=None, elites_from_pop=1)) == ERR_ARG       # elites_from_pop without an order
+    torch.cuda.synchronize()
+    assert cnt.get()[0] == 41 and twins.untouched()
+    for r, (_, _, _, pop, hofs, elite, pop0, hof0, elite0, _) in enumerate(checks):
+        assert_regions(r, (pop, hofs, elite), (pop0, hof0, elite0))
 
 
 # ------------------------------------------------------------------------------------------- 7. the ES update

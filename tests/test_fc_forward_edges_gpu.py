@@ -16,17 +16,31 @@ Cells (entry point, kernel form, row-count instantiation R) and where each is la
     coevo_fc_forward_argmax   fc_policy_mfma_body<MODE_OBS>             32-row tiles (tasks of 32, 17, 9, 29, 1, 24 rows)
     coevo_fc_forward_merged   fc_policy_mfma16_body<MODE_OBS>           16-row tiles: tasks of 9..16 rows and of 5 / 1 rows
     coevo_fc_forward_merged   fc_policy_body_c<R, MODE_OBS, FC2_MFMA>   R = 1, 2, 5, 8
+    merged_tiled              ... the 16-row table through the TILED branch of fc_policy_mfma16_body: every task of it carries
+                              COEVO_TASK_TILED and reads its net's tile-major twin (coevo_fc_w2_tile_major, behind the nets in
+                              the slab's allocation), the net's canonical fc2.weight is NaN in the slab - healthy, fault
+                              (heavy16 and heavy_few, every class), per-row and padding sections
+    merged_tiled_res          ... with COEVO_TASK_RESIDENT or-ed into those tasks: the same words (healthy section)
   state driven (whole games through RolloutPlan / DeviceRollout; the form is asserted, never assumed)
     persistent1 / persistent2 coevo_mpe_rollout_persistent, fc_rollout_small_kernel<8>, one / two cohorts
     small                     fc_cycle_small_kernel<8>: fc_policy_body_c<8, MODE_FUSED, FC2_DPP> for every task
     lean16                    fc_cycle16_kernel<5>: fc_policy_mfma16_body<MODE_FUSED> + fc_policy_body_c<5, MODE_FUSED>
     lean16_resident           ... with COEVO_TASK_RESIDENT on every other per-individual task (the RES = true twin)
+    lean16_tiled              ... with COEVO_TASK_TILED on every shared-opponent task, as GAEngine._enable_hof_tiled sets it:
+                              fc_policy_mfma16_body<MODE_FUSED>'s TILED branch; the shared opponents' canonical fc2.weight is
+                              NaN in the slab, their twins are rebuilt after every packing (the oracle's games are lean16's)
     tile32                    fc_cycle_kernel<5, 1>: fc_policy_mfma_body<MODE_FUSED> + fc_policy_body<5, MODE_FUSED, 1>
     paired                    fc_cycle_kernel<1, 2>: 523 one-row nets, two per workgroup, the last workgroup with one
     two_launch                merged=False: coevo_mpe_policy_cycle_fused twice per cycle, fc_policy_mfma_kernel<MODE_FUSED>
                               beside fc_policy_kernel<5, MODE_FUSED> (fc_policy_body_c)
     plain                     coevo_mpe_policy_cycle + coevo_mpe_step: fc_policy_mfma_body<MODE_STATE> and
                               fc_policy_body<5, MODE_STATE, 1>
+  COEVO_TASK_TILED where it must be ignored (include/coevo.h: "Every other launch and every per-individual task ignores it"):
+  the bit names an in-allocation twin region that is NaN throughout, the nets are healthy and whole - status 0, the oracle's words
+    coevo_fc_forward_merged   the light table, R = 1, 2, 5, 8, TILED and RESIDENT | TILED
+    coevo_fc_forward_argmax   R = 1, 2, 5, 8, 32
+    *_flagged                 persistent1, small, tile32, paired, two_launch, plain: every heavy and light task flagged;
+                              lean16_light / lean16_light_resident: the per-individual tasks of the lean16 form
 
 The non-finite STATE case runs on every form, the persistent one included: its launch reads the reset state from a buffer
 the caller owns (DeviceRollout.state), so the test seeds it between reset() and run() without touching product code.
@@ -73,18 +87,55 @@ def cast(g, names, D, R):
 
 
 # =============================================================================== observations given
-def launch(entry, D, tables, poison_padding=False):
+def slab_with_twins(flat, D, recs, marked):
+    """the nets packed at the slab's start; behind them, at a multiple of TASK_TWIN_UNIT and inside the same allocation, one
+    twin slot per marked task (table, task index, net index, how, further bits), and the task's TILED word naming it:
+      "twin"   the slot is the net's twin (coevo_fc_w2_tile_major), and the canonical fc2.weight of the net - which only this
+               task reads - is overwritten with NaN afterwards: the oracle's words come out only if the twin is what was read
+      "decoy"  the slot is NaN throughout and the net stays whole: the oracle's words come out only if the bit is ignored"""
+    if not marked:
+        return to_slab(flat, D)
+    n, stride, o_w2 = len(flat), L.fc_slab_stride(D), D * 512 + 3 * 512
+    assert len(marked) <= 16
+    twin0 = -(-n * stride // L.TASK_TWIN_UNIT) * L.TASK_TWIN_UNIT
+    slab = torch.zeros(twin0 + len(marked) * L.W2_FLOATS, dtype=torch.float32, device=DEV)
+    L.call("coevo_fc_pack", L._p(torch.from_numpy(flat).to(DEV)), L._p(slab), n, D)
+    for slot, (tname, t, net, how, bits) in enumerate(marked):
+        off = twin0 + slot * L.W2_FLOATS
+        if how == "twin":
+            L.call("coevo_fc_w2_tile_major", slab.data_ptr() + 4 * net * stride, slab.data_ptr() + 4 * off, 1, D)
+        else:
+            assert how == "decoy"
+            slab[off:off + L.W2_FLOATS] = float("nan")
+        recs[tname]["reserved"][t] = L.task_tiled_flags(off) | bits
+        assert ((int(recs[tname]["reserved"][t]) >> L.TASK_TWIN_SHIFT) * L.TASK_TWIN_UNIT + L.W2_FLOATS) <= slab.numel()
+    for tname, t, net, how, bits in marked:   # (after every twin is built)
+        if how == "twin":
+            slab[net * stride + o_w2:net * stride + o_w2 + L.W2_FLOATS] = float("nan")
+    return slab
+
+
+# entry -> marks of launch(): the merged launch with its 16-row table through twins, and with COEVO_TASK_RESIDENT on top
+MARKS = {"merged_tiled": {"heavy": ("twin", 0)}, "merged_tiled_res": {"heavy": ("twin", L.TASK_RESIDENT)}}
+
+
+def launch(entry, D, tables, poison_padding=False, marks=None):
     """one launch of `entry`; tables = {"tasks": (R, [task ...])} for coevo_fc_forward_argmax, {"heavy": (16, ...), "light":
     (R, ...)} for coevo_fc_forward_merged.  Every task is followed by R - n_rows + 1 rows that belong to no task (what an
     instantiation that ignored n_rows would read and write); actions / logits start as sentinels; the status word starts
     at FOREIGN.  poison_padding: NaN / inf in the observation columns >= D of every row and in the rows of no task.
+    marks = {table: ("twin" | "decoy", further COEVO_TASK_* bits)}: every task of that table carries COEVO_TASK_TILED
+    (slab_with_twins); MARKS[entry] when None.
     -> (actions, logits, status word, [(table, task index, first row)])"""
-    nets, recs, where, r0 = [], {}, [], 0
+    marks = MARKS.get(entry, {}) if marks is None else marks
+    nets, recs, where, r0, marked = [], {}, [], 0, []
     for tname, (R, tasks) in tables.items():
         rec = np.zeros(len(tasks), dtype=L.TASK_DTYPE)
         for t, (name, w, obs) in enumerate(tasks):
             assert 1 <= len(obs) <= R and obs.shape[1] == D
             rec[t] = (len(nets) * L.fc_slab_stride(D), r0, len(obs), D, 0)
+            if tname in marks:
+                marked.append((tname, t, len(nets)) + tuple(marks[tname]))
             nets.append(w)
             where.append((tname, t, r0))
             r0 += R + 1
@@ -99,7 +150,7 @@ def launch(entry, D, tables, poison_padding=False):
         if not poison_padding:
             obs_all[first:first + len(obs), D:] = 0.0
         is_task_row[first:first + len(obs)] = True
-    slab = to_slab(np.stack(nets), D)
+    slab = slab_with_twins(np.stack(nets), D, recs, marked)
     d_obs = torch.from_numpy(obs_all).to(DEV)
     actions = torch.full((n_rows,), SENT_A, dtype=torch.int32, device=DEV)
     logits = torch.full((n_rows, L.LOGIT_STRIDE), float(SENT_L), dtype=torch.float32, device=DEV)
@@ -121,10 +172,11 @@ def launch(entry, D, tables, poison_padding=False):
     return got_a, got_l, int(status.item()), where
 
 
-def check(entry, D, tables, poison_padding=False):
-    """launch, then every row of every task against the oracle: logits bits (NaN by class), action (-1 -> 0, as the kernels
-    and oracle_play_game have it), and the exact status word.  -> the oracle's status OR (without FOREIGN)"""
-    got_a, got_l, status, where = launch(entry, D, tables, poison_padding)
+def check(entry, D, tables, poison_padding=False, marks=None):
+    """launch, then every row of every task against the oracle ON THE NET AS GIVEN (launch() poisons only the slab): logits
+    bits (NaN by class), action (-1 -> 0, as the kernels and oracle_play_game have it), and the exact status word.
+    -> the oracle's status OR (without FOREIGN)"""
+    got_a, got_l, status, where = launch(entry, D, tables, poison_padding, marks)
     want_status, flat_tasks = 0, [x for _, ts in tables.values() for x in ts]
     for (tname, t, first), (name, w, obs) in zip(where, flat_tasks):
         for r, o in enumerate(obs):
@@ -139,14 +191,16 @@ def check(entry, D, tables, poison_padding=False):
 
 
 OBS_CELLS = [("argmax", 1), ("argmax", 2), ("argmax", 5), ("argmax", 8), ("argmax", 32),
-             ("merged", 1), ("merged", 2), ("merged", 5), ("merged", 8)]
+             ("merged", 1), ("merged", 2), ("merged", 5), ("merged", 8), ("merged_tiled", 5), ("merged_tiled", 8),
+             ("merged_tiled_res", 5)]
 
 
 @pytest.mark.parametrize("D", [10, 8])
 @pytest.mark.parametrize("entry,R", OBS_CELLS)
 def test_healthy_classes_bit_exact(entry, R, D):
     """ties (two- and five-way), signed zeros, variance 0 and both subnormal nets beside ordinary nets in one launch: status
-    exactly 0, logits bit-equal, the FIRST maximum taken.  merged: the whole cast in the 16-row table and in the R table"""
+    exactly 0, logits bit-equal, the FIRST maximum taken.  merged: the whole cast in the 16-row table and in the R table;
+    merged_tiled: the 16-row table through its nets' twins (MARKS), the subnormal fc2 net with its teeth among them"""
     g = rng(1, R, D)
     if entry == "argmax":
         tables = {"tasks": (R, cast(g, HEALTHY_CAST, D, R))}
@@ -157,7 +211,8 @@ def test_healthy_classes_bit_exact(entry, R, D):
 
 FAULT_CELLS = [("argmax", 1, "tasks"), ("argmax", 2, "tasks"), ("argmax", 5, "tasks"), ("argmax", 8, "tasks"),
                ("argmax", 32, "tasks"), ("merged", 5, "heavy16"), ("merged", 5, "heavy_few"), ("merged", 1, "light"),
-               ("merged", 2, "light"), ("merged", 5, "light"), ("merged", 8, "light")]
+               ("merged", 2, "light"), ("merged", 5, "light"), ("merged", 8, "light"),
+               ("merged_tiled", 5, "heavy16"), ("merged_tiled", 5, "heavy_few")]
 FAULTS = sorted(E.FAULTY) + ["obs_inf", "obs_nan"]
 
 
@@ -222,7 +277,8 @@ def test_non_finite_observation_in_one_row(entry, R, where, bad):
 @pytest.mark.parametrize("D", [8, 10])
 @pytest.mark.parametrize("entry,R,n,where", [("argmax", 2, 1, "tasks"), ("argmax", 5, 3, "tasks"), ("argmax", 8, 6, "tasks"),
                                              ("argmax", 32, 17, "tasks"), ("merged", 5, 9, "heavy"), ("merged", 2, 1, "light"),
-                                             ("merged", 5, 3, "light"), ("merged", 8, 6, "light")])
+                                             ("merged", 5, 3, "light"), ("merged", 8, 6, "light"),
+                                             ("merged_tiled", 5, 9, "heavy")])
 def test_padding_stays_silent(entry, R, n, where, D):
     """tasks with fewer rows than the instantiation (1 of 2, 3 of 5, 6 of 8, 9 of 16, 17 of 32), NaN / inf in the observation
     columns >= D of every row (an 8-wide net: columns 8 .. 11) and in the rows of no task right after each task's last row;
@@ -239,30 +295,117 @@ def test_padding_stays_silent(entry, R, n, where, D):
     assert check(entry, D, tables, poison_padding=True) == 0
 
 
+# ---- include/coevo.h on COEVO_TASK_TILED: "Every other launch and every per-individual task ignores it."  The bit names an
+#      in-allocation twin region that is NaN throughout ("decoy"): a body that followed it would raise BAD_FC2 on healthy nets
+@pytest.mark.parametrize("bits", [0, L.TASK_RESIDENT], ids=["tiled", "resident_tiled"])
+@pytest.mark.parametrize("R", [1, 2, 5, 8])
+def test_tiled_bit_is_ignored_by_per_individual_tasks(R, bits):
+    """the light table of coevo_fc_forward_merged (fc_policy_body_c<R, MODE_OBS, FC2_MFMA>), every task flagged, the healthy
+    cast: status 0 and the oracle's bits; the 16-row table beside it unflagged"""
+    for D in (10, 8):
+        g = rng(5, R, D)
+        tables = {"heavy": (16, cast(g, ["plain", "tie2_04"], D, 16)), "light": (R, cast(g, HEALTHY_CAST, D, R))}
+        assert check("merged", D, tables, marks={"light": ("decoy", bits)}) == 0
+
+
+@pytest.mark.parametrize("R", [1, 2, 5, 8, 32])
+def test_tiled_bit_is_ignored_by_the_argmax_launch(R):
+    """coevo_fc_forward_argmax, every task flagged: fc_policy_body<R> and, at R = 32, fc_policy_mfma_body (shared-opponent
+    tasks of more than 16 rows have no twin path)"""
+    for D in (10, 8):
+        assert check("argmax", D, {"tasks": (R, cast(rng(6, R, D), HEALTHY_CAST, D, R))}, marks={"tasks": ("decoy", 0)}) == 0
+
+
 # =============================================================================== state driven: whole games
-FORMS = ["persistent1", "persistent2", "small", "lean16", "lean16_resident", "tile32", "paired", "two_launch", "plain"]
+FORMS = ["persistent1", "persistent2", "small", "lean16", "lean16_resident", "lean16_tiled", "tile32", "paired", "two_launch",
+         "plain"]
+# forms whose tasks carry COEVO_TASK_TILED although no body of theirs may follow it -> the form they are otherwise
+# (every heavy and every light task flagged; lean16: the per-individual tasks only, without and with COEVO_TASK_RESIDENT)
+FLAGGED = {"persistent1_flagged": "persistent1", "small_flagged": "small", "tile32_flagged": "tile32",
+           "paired_flagged": "paired", "two_launch_flagged": "two_launch", "plain_flagged": "plain",
+           "lean16_light_flagged": "lean16", "lean16_light_resident_flagged": "lean16"}
+SHAPES = {"persistent1": (20, 4, 8, 1, True), "persistent2": (20, 4, 8, 2, True), "small": (20, 4, 8, 1, False),
+          "lean16": (20, 4, 16, 2, False), "lean16_resident": (20, 4, 16, 2, False), "lean16_tiled": (20, 4, 16, 2, False),
+          "tile32": (40, 4, 32, 2, False), "paired": (523, 1, 32, 1, False), "two_launch": (40, 4, 32, 1, False),
+          "plain": (20, 4, 16, 1, False)}
+O_W2 = {D: D * 512 + 3 * 512 for D in (8, 10)}   # fc2.weight's first slab position
 _SETUPS = {}
+
+
+def twin_room(s, n_twins, merged, persistent):
+    """the Setup's slab reallocated with room for n_twins twins behind the nets, at a multiple of TASK_TWIN_UNIT and inside
+    the same allocation, and its DeviceRollout rebuilt on it (as two_launch rebuilds it) -> float offset of the first twin"""
+    twin0 = -(-s.slab.numel() // L.TASK_TWIN_UNIT) * L.TASK_TWIN_UNIT
+    s.slab = torch.zeros(twin0 + n_twins * L.W2_FLOATS, dtype=torch.float32, device=DEV)
+    s.ro = DeviceRollout(s.plan, s.slab, merged=merged)
+    if not persistent:
+        s.ro.sync_words, s.ro.desc.sync_words = None, None
+    return twin0
+
+
+def set_task_words(plan, table, words):
+    """`reserved` of every task of plan.heavy / plan.light, in the host table and - in place, the rollout points to it - in
+    the device table: exactly what GAEngine._enable_hof_tiled does"""
+    tasks = getattr(plan, table + "_np").copy()
+    tasks["reserved"] = words
+    setattr(plan, table + "_np", tasks)
+    getattr(plan, table).copy_(L.tasks_to_device(tasks))
+
+
+def assert_task_words(s, table, bits):
+    """the device table is the host table, every task of it carries `bits`, every twin it names lies inside the slab"""
+    p = s.plan
+    tnp = getattr(p, table + "_np")
+    assert torch.equal(getattr(p, table).cpu(), L.tasks_to_device(tnp).cpu())
+    words = tnp["reserved"].astype(np.int64)
+    assert len(words) and ((words & (L.TASK_TILED | L.TASK_RESIDENT)) == bits).all()
+    assert ((words >> L.TASK_TWIN_SHIFT) * L.TASK_TWIN_UNIT + L.W2_FLOATS <= s.slab.numel()).all()
 
 
 def setup(form):
     """one Setup (tests/test_rollout_reuse_gpu.py) per form, kept for the module; the kernel form is asserted on every use"""
     s = _SETUPS.get(form)
+    base = FLAGGED.get(form, form)
     if s is None:
-        npop, nh, heavy_rows, K, persistent = {
-            "persistent1": (20, 4, 8, 1, True), "persistent2": (20, 4, 8, 2, True), "small": (20, 4, 8, 1, False),
-            "lean16": (20, 4, 16, 2, False), "lean16_resident": (20, 4, 16, 2, False), "tile32": (40, 4, 32, 2, False),
-            "paired": (523, 1, 32, 1, False), "two_launch": (40, 4, 32, 1, False), "plain": (20, 4, 16, 1, False)}[form]
+        npop, nh, heavy_rows, K, persistent = SHAPES[base]
         s = Setup(npop, nh, heavy_rows, K, persistent=persistent)
-        if form == "two_launch":
+        if base == "two_launch" and form == base:
             s.ro = DeviceRollout(s.plan, s.slab, merged=False)
         if form == "lean16_resident":   # the flag in the task table the rollout already points to (same device buffer)
             s.plan.light_np["reserved"][::2] = L.TASK_RESIDENT
             s.plan.light.copy_(L.tasks_to_device(s.plan.light_np))
+        if form == "lean16_tiled":
+            # a twin slot per shared opponent - in Setup these nets (agent_1: D = 10, adversary: D = 8) play heavy tasks only
+            # and the heavy tasks play only them - and every heavy task pointed at its net's slot
+            n10 = npop + nh
+            twin0 = twin_room(s, 2 * nh, merged=True, persistent=False)
+            s.twin_nets = [(npop * s.s10, 10, nh, twin0), (n10 * s.s10, 8, nh, twin0 + nh * L.W2_FLOATS)]
+            slot = {first + k * L.fc_slab_stride(D): t0 + k * L.W2_FLOATS for first, D, n, t0 in s.twin_nets for k in range(n)}
+            assert sorted(set(s.plan.heavy_np["net_off"].tolist())) == sorted(slot)
+            assert not set(s.plan.light_np["net_off"].tolist()) & set(slot)
+            set_task_words(s.plan, "heavy", [L.task_tiled_flags(slot[off]) for off in s.plan.heavy_np["net_off"].tolist()])
+        if form in FLAGGED:   # one twin slot, NaN throughout and never written again, named by every flagged task
+            twin0 = twin_room(s, 1, merged=base != "two_launch", persistent=persistent)
+            s.slab[twin0:] = float("nan")
+            word = L.task_tiled_flags(twin0) | (L.TASK_RESIDENT if "resident" in form else 0)
+            for table in (("light",) if base == "lean16" else ("heavy", "light")):
+                set_task_words(s.plan, table, word)
         s.load_nets(seed=77)
         s.base10, s.base8 = s.nets10, s.nets8
-        s.n_cycles = 3 if form == "paired" else 5
+        s.n_cycles = 3 if base == "paired" else 5
         _SETUPS[form] = s
     lib, p, ro = L.load(), s.plan, s.ro
+    if form == "lean16_tiled":
+        assert_task_words(s, "heavy", L.TASK_TILED)
+        assert not p.light_np["reserved"].any()
+    elif form in FLAGGED:
+        assert torch.isnan(s.slab[-L.W2_FLOATS:]).all()
+        assert_task_words(s, "light", L.TASK_TILED | (L.TASK_RESIDENT if "resident" in form else 0))
+        if base == "lean16":
+            assert not p.heavy_np["reserved"].any()
+        else:
+            assert_task_words(s, "heavy", L.TASK_TILED)
+    form = "lean16" if form == "lean16_tiled" else base
     if form.startswith("persistent"):
         s.assert_form("persistent")
         assert p.n_cohorts == int(form[-1]) and ro.desc.merged == 1
@@ -300,6 +443,12 @@ def install(s, edits10=None, edits8=None, flush=False):
         for flat, D, first in ((s.nets10, 10, 0), (s.nets8, 8, len(s.nets10) * s.s10)):
             src = torch.from_numpy(np.ascontiguousarray(flat)).to(DEV)
             L.call("coevo_fc_pack", L._p(src), s.slab.data_ptr() + 4 * first, len(flat), D)
+        # lean16_tiled: the shared opponents' twins rebuilt from the nets just packed, then the canonical fc2.weight of those
+        # nets - which only twin-reading tasks play - NaN: the oracle's games come out only if the twins are what is read
+        for first, D, n, twin0 in getattr(s, "twin_nets", ()):
+            L.call("coevo_fc_w2_tile_major", s.slab.data_ptr() + 4 * first, s.slab.data_ptr() + 4 * twin0, n, D)
+            nets_view = s.slab[first:first + n * L.fc_slab_stride(D)].view(n, L.fc_slab_stride(D))
+            nets_view[:, O_W2[D]:O_W2[D] + L.W2_FLOATS] = float("nan")
 
 
 def seats(s, form):
@@ -493,3 +642,23 @@ def test_games_with_a_non_finite_state(form):
     assert status == want_status, f"{form}: status word {status:#x}, the oracle's steps OR to {want_status:#x}"
     assert_games(got, want, f"{form} non-finite state", poisoned=(gp,))
     assert_last_actions(last, acts, f"{form} non-finite state")
+
+
+@pytest.mark.parametrize("form", sorted(FLAGGED))
+def test_tiled_bit_is_ignored_outside_the_lean_shared_opponent_body(form):
+    """include/coevo.h on COEVO_TASK_TILED: "Every other launch and every per-individual task ignores it."  The games of
+    test_games_of_tie_nets (healthy nets; the oracle's games are the unflagged form's) with the bit on every task that must
+    not follow it, naming an in-allocation twin region that is NaN throughout: status 0, rewards and last actions the oracle's
+    - a body that honoured the bit would read NaN weights and raise BAD_FC2"""
+    s, base = setup(form), FLAGGED[form]
+    ind, a1s, advs = seats(s, base)
+    install(s, dict(zip(ind + a1s[:2], ["tie2", "tie5", "tie2_04", "tie2_23", "tie2", "tie2_23", "tie5"])),
+            dict(zip(advs[:2], ["tie2", "tie5"])))
+    first, limits = 11, limits_of(s, ragged=False)
+    want, st, acts = oracle_games(s, first, limits, s.n_cycles)
+    assert st == 0
+    got, status, last = run(s, base, first, limits)
+    assert status == 0, f"{form}: status {status:#x}"
+    s.ro.check_status()
+    assert_games(got, want, f"{form} tie nets")
+    assert_last_actions(last, acts, f"{form} tie nets")

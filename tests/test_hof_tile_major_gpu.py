@@ -1,5 +1,6 @@
-"""Tile-major twins of the Hall of Fame's second layer (COEVO_TASK_TILED): the stand-alone builder against its index formula,
-the lean cycle launch through twins against the oracle and against the canonical path, the pipelined one-GPU Co-GA loop with
+"""Tile-major twins of the Hall of Fame's second layer (COEVO_TASK_TILED): the stand-alone builder against its index formula
+(tests/tile_major_cases.py, proven on the CPU by tests/test_hof_tile_major_cpu.py) and at its edges - raw words bit for bit,
+16 nets, no nets, refusals -, the lean cycle launch through twins against the oracle and against the canonical path, the pipelined one-GPU Co-GA loop with
 COEVO_HOF_TILED 1 against 0, and an upload into the Hall of Fame between generations.  Everything bit for bit."""
 import numpy as np
 import pytest
@@ -8,18 +9,13 @@ import torch
 from coevonet_amd import genetic_algorithm as ga, lib as L
 from coevonet_amd.game_logic import initialize_env
 from oracle import ref_port as rp
-from tests import fc_edge_nets as en
+from tests import fc_edge_nets as en, tile_major_cases as tm
+from tests.tile_major_cases import twin_of
 from tests.util import Bag
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 H1, H2 = 512, 256
-
-
-def twin_of(W2):
-    """fc2.weight [256][512] -> its tile-major twin: piece (w, q, l = 16 lg + lc), element T = W2[64 w + 16 T + lc][4 q + lg]"""
-    assert W2.shape == (H2, H1)
-    return np.ascontiguousarray(W2.reshape(4, 4, 16, 128, 4).transpose(0, 3, 4, 2, 1)).reshape(-1)   # [w][q][lg][lc][T]
 
 
 def test_twin_of_is_the_index_formula():
@@ -56,6 +52,62 @@ def test_twin_builder_equals_the_index_formula(D, n_nets):
     back = torch.zeros(n_nets, L.fc_param_count(D), dtype=torch.float32, device=DEV)
     L.call("coevo_fc_unpack", L._p(slab), L._p(back), n_nets, D)
     assert np.array_equal(back.cpu().numpy(), flat)   # ... and the nets are what they were
+
+
+# ---------------------------------------------------------------------------------------------- the builder's edges
+SENT = np.float32(-7.25)
+
+
+class RawCase:
+    """n_nets raw-word nets of width D (tm.raw_words: random bits, NaN payloads, infinities, -0.0, subnormals - in fc2.weight
+    as everywhere else) between a guard net on each side, and a twin buffer of n_twins + 1 sentinel slots between guard words:
+    the last slot is what a launch that wrote one twin too many would hit"""
+    PAD = 4   # (16 bytes: the twins stay 16-byte aligned behind the guard words)
+
+    def __init__(self, D, n_nets, n_twins, seed):
+        self.D, self.n, self.stride = D, n_nets, L.fc_slab_stride(D)
+        g = np.random.Generator(np.random.PCG64([seed, D, n_nets]))
+        self.src_np = tm.raw_words(g, (n_nets + 2) * self.stride).reshape(n_nets + 2, self.stride)
+        self.src = torch.from_numpy(self.src_np).to(DEV)
+        self.dst = torch.full((2 * self.PAD + (n_twins + 1) * L.W2_FLOATS,), float(SENT), dtype=torch.float32, device=DEV)
+        self.src_p = self.src.data_ptr() + 4 * self.stride
+        self.dst_p = self.dst.data_ptr() + 4 * self.PAD
+
+    def twins(self):
+        """-> [n_twins + 1][W2_FLOATS] after asserting the guard words and that the source is bit for bit what it was"""
+        torch.cuda.synchronize()
+        a = self.dst.cpu().numpy()
+        assert (a[:self.PAD] == SENT).all() and (a[-self.PAD:] == SENT).all(), "a guard word of the twin buffer was written"
+        assert np.array_equal(self.src.cpu().numpy().view(np.uint32), self.src_np.view(np.uint32)), "the source nets changed"
+        return a[self.PAD:-self.PAD].reshape(-1, L.W2_FLOATS)
+
+
+@pytest.mark.parametrize("D,n_nets", [(8, 16), (10, 3), (8, 1)])
+def test_twin_builder_copies_raw_words_bit_for_bit(D, n_nets):
+    """NaN (payloads kept), inf, -0.0 and subnormals in fc2.weight come out at their permuted places as the words they are;
+    nothing behind the last twin (16 nets of D = 8: the largest launch the engines make), the source left as it was"""
+    c = RawCase(D, n_nets, n_nets, seed=21)
+    w2 = c.src_np[1:1 + n_nets, tm.w2_offset(D):tm.w2_offset(D) + L.W2_FLOATS]
+    assert np.isnan(w2).any() and np.isinf(w2).any() and (w2.view(np.uint32) == 0x80000000).any() \
+        and ((w2 != 0) & (np.abs(w2) < en.MIN_NORMAL)).any()
+    L.call("coevo_fc_w2_tile_major", c.src_p, c.dst_p, n_nets, D)
+    got = c.twins()
+    for i in range(n_nets):
+        want = twin_of(tm.w2_of_slab_row(c.src_np[1 + i], D))
+        assert np.array_equal(got[i].view(np.uint32), want.view(np.uint32)), (i, np.flatnonzero(got[i].view(np.uint32) != want.view(np.uint32))[:4])
+    assert (got[n_nets] == SENT).all(), "written behind the last twin"
+
+
+def test_twin_builder_no_nets_and_refusals_write_nothing():
+    D = 8
+    c = RawCase(D, 2, 2, seed=22)
+    lib, st = L.load(), L._stream()
+    assert lib.coevo_fc_w2_tile_major(c.src_p, c.dst_p, 0, D, st) == 0            # no nets: fine, and nothing to do
+    for what, args in (("unaligned src", (c.src_p + 4, c.dst_p, 2, D)), ("unaligned dst", (c.src_p, c.dst_p + 4, 2, D)),
+                       ("D = 9", (c.src_p, c.dst_p, 2, 9)), ("negative n_nets", (c.src_p, c.dst_p, -1, D)),
+                       ("no src", (None, c.dst_p, 2, D)), ("no dst", (c.src_p, None, 2, D))):
+        assert lib.coevo_fc_w2_tile_major(*args, st) == L.K["COEVO_ERR_ARG"], what
+    assert (c.twins() == SENT).all()
 
 
 # (net, rows, through its twin?): tasks of 16, 15, 5, 4 and 1 rows, two tasks of net 4, net 0 once through its twin and once not
