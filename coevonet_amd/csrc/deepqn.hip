@@ -41,18 +41,8 @@ namespace coevo {
 #ifndef DQ_FC1_NARROW_MAX_TASKS
 #define DQ_FC1_NARROW_MAX_TASKS 16   // launches of at most this many tasks take the 32-waves-per-task kernel
 #endif
-#ifndef DQ_FC1_ALLNT
-#define DQ_FC1_ALLNT 0   // 1: non-temporal weight loads for every task (A/B)
-#endif
-#ifndef DQ_FC1_HALF
-#define DQ_FC1_HALF 0    // 1 (A/B, measured and not shipped): launches of <= 1024 waves as 32-output waves, two per SIMD - 104 vs
-                         // 92 us at cfg 4: a wave's time is its 3136-step dependent 4x4x1 chain, whatever its width (r04_experiments.md)
-#endif
-#ifndef DQ_FC1_NB_HALF
-#define DQ_FC1_NB_HALF 4   // ... and their ring depth (<= 256 registers)
-#endif
 #ifndef DQ_FC1_NB_MANY
-#define DQ_FC1_NB_MANY 2   // ... of a launch with more waves than the chip has SIMDs (fewer registers: several waves per SIMD)
+#define DQ_FC1_NB_MANY 2   // fc1: ring depth of a launch with more waves than the chip has SIMDs (fewer registers: several waves per SIMD)
 #endif
 #ifndef DQ_FC1_TQ
 #define DQ_FC1_TQ 2    // tiled fc1: super-quads (16 k: four 16-byte loads per lane, one per 16-output tile) per chunk of the ring
@@ -73,17 +63,6 @@ __global__ __launch_bounds__(256) void dqn_pack_kernel(const float *flat, float 
 }
 
 
-#ifdef COEVO_PHASE_STAMPS
-// diagnostic build only (tools/dqn_conv_phases.py): wave 0's arrival at each phase boundary, 100 MHz constant clock
-__device__ unsigned long long g_dqn_stamps[2048 * 16];
-#define DQ_STAMP(i)                                                                                   \
-    do {                                                                                              \
-        if (threadIdx.x == 0 && blockIdx.x < 2048) g_dqn_stamps[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#else
-#define DQ_STAMP(i) do { } while (0)
-#endif
-
 // CT: the channel count as a compile-time constant (4 or 6: the gather offsets become instruction immediates), 0 = run time
 template <int CMAX, int CT>
 __global__ __launch_bounds__(512, DQ_WPE) void dqn_conv_kernel(const float *slab, const coevo_dqn_task *tasks, int n_tasks,
@@ -93,48 +72,35 @@ __global__ __launch_bounds__(512, DQ_WPE) void dqn_conv_kernel(const float *slab
     // one workgroup per frame; its task by binary search (tasks ascend in row_begin).  Workgroups are dealt to the 8 XCDs
     // round robin: XCD x takes the contiguous rows [x * per, (x + 1) * per), so the frames of one net meet in ONE L2 (and,
     // dispatched back to back, on one CU's L1) instead of pulling every net's conv weights into all eight.
-#ifdef DQ_NO_XCD_MAP
-    const int row = blockIdx.x;
-#else
     const int per = gridDim.x >> 3;
     const int row = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-#endif
     if (row >= n_rows) return;   // workgroup-uniform (the grid is rounded up to a multiple of 8)
     const coevo_dqn_task task = tasks[task_of_row(tasks, n_tasks, row)];
     const int t = threadIdx.x, w = __builtin_amdgcn_readfirstlane(t >> 6), l = t & 63;   // w: scalar (wave-uniform branches)
     const float *net = slab + task.net_off;
     const DqnLayout L = dqn_layout(C, n_actions);
     // stage the frame (84*84*C bytes, a multiple of 16)
-    DQ_STAMP(0);
     const int nbytes = 84 * 84 * C;
     const uint4 *src = reinterpret_cast<const uint4 *>(frames + (size_t)row * nbytes);
     uint4 *dst = reinterpret_cast<uint4 *>(sm.frame);
     for (int i = t; i < nbytes / 16; i += 512) dst[i] = src[i];
     if (DQ_LUT && t < 256) sm.lut[t] = (float)t / 255.0f;
     __syncthreads();
-    DQ_STAMP(1);
     conv16_mfma<8, 4, 84, 20, 32, true, 0, DQ_P1, CT, DQ_QU1, true>(sm.frame, sm.lut, C, C * 64, net + L.w1, net + L.b1, sm.a1, w, l);
     __syncthreads();
-    DQ_STAMP(2);
     bn_relu_rows<400, DQ_P1, 32>(sm.a1, net + L.b1 + 32, net + L.b1 + 64, w, l);
     __syncthreads();
-    DQ_STAMP(3);
     conv16_mfma<4, 2, 20, 9, 64, false, DQ_P1, DQ_P2, 0, DQ_QU2, true>(sm.a1, nullptr, 32, 512, net + L.w2, net + L.b2, sm.a2, w, l);
     __syncthreads();
-    DQ_STAMP(4);
     bn_relu_rows<81, DQ_P2, 64>(sm.a2, net + L.b2 + 64, net + L.b2 + 128, w, l);
     __syncthreads();
-    DQ_STAMP(5);
     conv16_mfma<3, 1, 9, 7, 64, false, DQ_P2, DQ_P3, 0, DQ_QU3, false>(sm.a2, nullptr, 64, 576, net + L.w3, net + L.b3, sm.a3, w, l);
     __syncthreads();
-    DQ_STAMP(6);
     bn_relu_rows<49, DQ_P3, 64>(sm.a3, net + L.b3 + 64, net + L.b3 + 128, w, l);
     __syncthreads();
-    DQ_STAMP(7);
     // flatten in CHW order (Atari/deepqn.py:45): channel pitch 49 = the flat layout itself
     float *dsta = act + (size_t)row * DQ_FC1_IN;
     for (int i = t; i < DQ_FC1_IN; i += 512) dsta[i] = sm.a3[i];
-    DQ_STAMP(8);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -234,25 +200,16 @@ constexpr int DQ_RMAX = 16;
 // MFMAs.  One launch serves tasks of every size: the kernel picks the instantiation by the task's own row count.
 // NB = chunks of the weight stream in the wave's register ring: NB - 1 of them (14 KiB each) are in flight while one feeds
 // the matrix pipe.
-// HALF: a wave owns 32 outputs instead of 64 (`ob` then counts 32-output blocks): lanes l and l + 32 hold the SAME output
-// column l % 32 and different row groups - the sixteen 4x4 blocks of an MFMA are 8 column quads x 2 row groups - so a 16-row
-// task issues two matrix instructions per k and wave instead of four, and has 16 waves instead of 8.  For launches with fewer
-// waves than the chip has SIMDs (a Co-GA shard: 90 tasks): a lone wave on a SIMD cannot hide its own LDS round trips and MFMA
-// chain (100 k matrix-pipe cycles for 64 outputs x 16 rows); two half-size waves per SIMD overlap each other's.  The two
-// lanes of a column request the same 16-byte piece (one 512-byte segment per wave-load): no extra bytes leave the L2.
-// NG counts the MFMA groups of the wave (HALF: 8 rows each, else 4).  Same sequential-k chain per (row, output): same bits.
-template <int NG, int NB, bool SHARED_NET, bool HALF = false>
+template <int NG, int NB, bool SHARED_NET>
 __device__ __forceinline__ void dqn_fc1_body(const float *net, const DqnLayout &L, const coevo_dqn_task &task,
                                              const float *act, float *hid, float (*xs)[DQ_RMAX][DQ_FC1_U * 4], int ob, int l)
 {
     constexpr int U = DQ_FC1_U;  // k-quads per chunk; 784 = 56 * 14
     constexpr int NCHUNK = 784 / U;
     static_assert(784 % U == 0 && NCHUNK % NB == 0 && NB >= 2, "whole rounds of the ring");
-    constexpr int RG = HALF ? 2 * NG : NG;          // row groups of four staged per chunk
-    static_assert(4 * RG <= DQ_RMAX, "rows of one task");
+    static_assert(4 * NG <= DQ_RMAX, "rows of one task");
     const int nrows = task.n_rows;
-    const int col = HALF ? 32 * ob + (l & 31) : 64 * ob + l;   // the lane's output
-    const int hrow = HALF ? (l >> 5) : 0;                       // which of a group's two row quads this lane accumulates
+    const int col = 64 * ob + l;   // the lane's output
     const float bb = net[L.bf + col];
     // rows in groups of four on v_mfma_f32_4x4x1_16B_f32 (16 blocks x 4 columns = the wave's 64 outputs, one k per
     // instruction; bit-identical to the fmaf chain, tools/mfma4_chain_probe.hip): the lane's streamed 16-byte piece is
@@ -267,7 +224,7 @@ __device__ __forceinline__ void dqn_fc1_body(const float *net, const DqnLayout &
         for (int i = 0; i < 4; ++i) acc[g][i] = bb;
     const float4 *wp = reinterpret_cast<const float4 *>(net + L.wf) + (size_t)(col >> 6) * 784 * 64 + (col & 63);
     const float *arow = act + (size_t)task.row_begin * DQ_FC1_IN;
-    constexpr int XI = (4 * RG * U + 63) / 64;
+    constexpr int XI = (4 * NG * U + 63) / 64;
     float4 wv[NB][U], xr[NB][XI];
     // a chunk's weight pieces (read once per launch: non-temporal, keeps the conv weights / activations in L2 - unless the
     // neighbouring task streams the same net: then plain loads, so that the siblings' requests meet in the XCD's L2.
@@ -286,7 +243,7 @@ __device__ __forceinline__ void dqn_fc1_body(const float *net, const DqnLayout &
 #pragma unroll
         for (int j = 0; j < XI; ++j) {
             const int i = l + 64 * j, r = i / U, q = i % U;
-            x[j] = (i < 4 * RG * U && r < nrows)
+            x[j] = (i < 4 * NG * U && r < nrows)
                        ? *reinterpret_cast<const float4 *>(arow + (size_t)r * DQ_FC1_IN + 4 * (kq + q))
                        : make_float4(0.f, 0.f, 0.f, 0.f);
         }
@@ -295,7 +252,7 @@ __device__ __forceinline__ void dqn_fc1_body(const float *net, const DqnLayout &
 #pragma unroll
         for (int j = 0; j < XI; ++j) {
             const int i = l + 64 * j;
-            if (i < 4 * RG * U) *reinterpret_cast<float4 *>(&x_lds[i / U][4 * (i % U)]) = xin[j];
+            if (i < 4 * NG * U) *reinterpret_cast<float4 *>(&x_lds[i / U][4 * (i % U)]) = xin[j];
         }
         __syncthreads();   // one wave per workgroup: orders the LDS round trip
         // The broadcast reads of k-quad u + 1 are requested BEFORE the matrix instructions of k-quad u are issued (two
@@ -306,7 +263,7 @@ __device__ __forceinline__ void dqn_fc1_body(const float *net, const DqnLayout &
         auto read_x = [&](float4 (&dst)[NG], int u) {
 #pragma unroll
             for (int g = 0; g < NG; ++g)
-                dst[g] = *reinterpret_cast<const float4 *>(&x_lds[4 * ((HALF ? 2 * g : g) + hrow) + (l & 3)][4 * u]);
+                dst[g] = *reinterpret_cast<const float4 *>(&x_lds[4 * g + (l & 3)][4 * u]);
         };
         read_x(x[0], 0);
 #pragma unroll
@@ -345,7 +302,7 @@ __device__ __forceinline__ void dqn_fc1_body(const float *net, const DqnLayout &
     for (int g = 0; g < NG; ++g)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int r = 4 * ((HALF ? 2 * g : g) + hrow) + i;
+            const int r = 4 * g + i;
             if (r < nrows) hid[(size_t)(task.row_begin + r) * DQ_FC1_OUT + col] = relu_keep_nan(acc[g][i]);
         }
 }
@@ -358,45 +315,25 @@ __device__ __forceinline__ void dqn_fc1_body(const float *net, const DqnLayout &
 // of 7 KiB (~300 registers, nothing else would hide a lone wave's round trips); a launch with more waves than SIMDs (a
 // Co-ES cohort: 133 tasks = 1064 waves) keeps two (< 256 registers: every wave resident; with the deep ring its last 40
 // waves ran as a second round, 171 against 141 us).  Chunks of 7 instead of 14 pieces: 170 -> 141 us for that launch.
-template <int NB, bool HALF = false>
-__global__ __launch_bounds__(64, (HALF || NB <= DQ_FC1_NB_MANY) ? 2 : 1) void dqn_fc1_kernel(const float *slab, const coevo_dqn_task *tasks, int n_tasks, int C,
+template <int NB>
+__global__ __launch_bounds__(64, NB <= DQ_FC1_NB_MANY ? 2 : 1) void dqn_fc1_kernel(const float *slab, const coevo_dqn_task *tasks, int n_tasks, int C,
                                                       int n_actions, const float *act, float *hid)
 {
     __shared__ __attribute__((aligned(16))) float xs[2][DQ_RMAX][DQ_FC1_U * 4];
     // XCD x takes a contiguous range of tasks (gridDim.x is a multiple of 8, so the output block blockIdx.y does not change
     // the XCD): the several <= 16-row tasks of a net that acts in many games stream the same matrix block through ONE L2
-#ifdef DQ_NO_XCD_MAP
-    const int ti = blockIdx.x;
-#else
     const int ti = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-#endif
     if (ti >= n_tasks) return;
     const coevo_dqn_task task = tasks[ti];
     // a net that acts in more than 16 games owns several tasks, adjacent in the table (workgroup-uniform)
-    const bool shared_net = !DQ_FC1_ALLNT && ((ti > 0 && tasks[ti - 1].net_off == task.net_off) ||
-                                              (ti + 1 < n_tasks && tasks[ti + 1].net_off == task.net_off));
+    const bool shared_net = (ti > 0 && tasks[ti - 1].net_off == task.net_off) ||
+                            (ti + 1 < n_tasks && tasks[ti + 1].net_off == task.net_off);
     const float *net = slab + task.net_off;
     const DqnLayout L = dqn_layout(C, n_actions);
     const int ob = blockIdx.y, l = threadIdx.x;
-#ifdef COEVO_PHASE_STAMPS
-    // diagnostic build only (round 4: tools/dqn_fc1_clock.py, retired - profiles/r04_experiments.md): shader-clock and 100 MHz stamps of wave (task ti, block 0) -> the clock
-    // the chip holds during this launch
-    if (ob == 0 && l == 0 && ti < 1024) {
-        g_dqn_stamps[ti * 16 + 10] = __builtin_amdgcn_s_memrealtime();
-        g_dqn_stamps[ti * 16 + 11] = __builtin_amdgcn_s_memtime();
-    }
-#endif
     // MFMA groups of this wave (workgroup-uniform, as is shared_net: one straight-line instantiation each)
-    const int ng = HALF ? (task.n_rows + 7) >> 3 : (task.n_rows + 3) >> 2;
-    if constexpr (HALF) {
-        if (shared_net) {
-            if (ng == 1) dqn_fc1_body<1, NB, true, true>(net, L, task, act, hid, xs, ob, l);
-            else dqn_fc1_body<2, NB, true, true>(net, L, task, act, hid, xs, ob, l);
-        } else {
-            if (ng == 1) dqn_fc1_body<1, NB, false, true>(net, L, task, act, hid, xs, ob, l);
-            else dqn_fc1_body<2, NB, false, true>(net, L, task, act, hid, xs, ob, l);
-        }
-    } else if (shared_net) {
+    const int ng = (task.n_rows + 3) >> 2;
+    if (shared_net) {
         if (ng == 1) dqn_fc1_body<1, NB, true>(net, L, task, act, hid, xs, ob, l);
         else if (ng == 2) dqn_fc1_body<2, NB, true>(net, L, task, act, hid, xs, ob, l);
         else if (ng == 3) dqn_fc1_body<3, NB, true>(net, L, task, act, hid, xs, ob, l);
@@ -407,12 +344,6 @@ __global__ __launch_bounds__(64, (HALF || NB <= DQ_FC1_NB_MANY) ? 2 : 1) void dq
         else if (ng == 3) dqn_fc1_body<3, NB, false>(net, L, task, act, hid, xs, ob, l);
         else dqn_fc1_body<4, NB, false>(net, L, task, act, hid, xs, ob, l);
     }
-#ifdef COEVO_PHASE_STAMPS
-    if (ob == 0 && l == 0 && ti < 1024) {
-        g_dqn_stamps[ti * 16 + 12] = __builtin_amdgcn_s_memrealtime();
-        g_dqn_stamps[ti * 16 + 13] = __builtin_amdgcn_s_memtime();
-    }
-#endif
 }
 
 // fc1 + ReLU over the TILED fc1 block (dqn_common.hip.h: the layout of a Co-GA engine, whose tasks carry 10 / 16 rows): grid
@@ -518,15 +449,11 @@ __global__ __launch_bounds__(64, 1) void dqn_fc1_tiled_kernel(const float *slab,
                                                               int n_actions, const float *act, float *hid)
 {
     __shared__ __attribute__((aligned(16))) float xs[2][DQ_FC1_TQ][4][16][4];
-#ifdef DQ_NO_XCD_MAP
-    const int ti = blockIdx.x;
-#else
     const int ti = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);   // as dqn_fc1_kernel: a net's tasks meet in one L2
-#endif
     if (ti >= n_tasks) return;
     const coevo_dqn_task task = tasks[ti];
-    const bool shared_net = !DQ_FC1_ALLNT && ((ti > 0 && tasks[ti - 1].net_off == task.net_off) ||
-                                              (ti + 1 < n_tasks && tasks[ti + 1].net_off == task.net_off));
+    const bool shared_net = (ti > 0 && tasks[ti - 1].net_off == task.net_off) ||
+                            (ti + 1 < n_tasks && tasks[ti + 1].net_off == task.net_off);
     const float *net = slab + task.net_off;
     const DqnLayout L = dqn_layout(C, n_actions);
     if (shared_net) dqn_fc1_tiled_body<NB, true>(net, L, task, act, hid, xs, blockIdx.y, threadIdx.x);
@@ -805,9 +732,6 @@ static int dqn_forward_launch(const float *slab, const coevo_dqn_task *tasks, in
     else if (n_tasks <= DQ_FC1_NARROW_MAX_TASKS)
         hipLaunchKernelGGL(dqn_fc1_narrow_kernel<DQ_FC1_NBN>, dim3(n_tasks, 32), dim3(64), 0, s, slab, tasks, n_tasks, C, n_actions,
                            act, hid);
-    else if (DQ_FC1_HALF && n_tasks * 8 <= 1024)
-        hipLaunchKernelGGL((dqn_fc1_kernel<DQ_FC1_NB_HALF, true>), dim3(fg.x, 16), dim3(64), 0, s, slab, tasks, n_tasks, C, n_actions,
-                           act, hid);
     else if (n_tasks * 8 <= 1024) hipLaunchKernelGGL(dqn_fc1_kernel<DQ_FC1_NB>, fg, dim3(64), 0, s, slab, tasks, n_tasks, C, n_actions, act, hid);
     else hipLaunchKernelGGL(dqn_fc1_kernel<DQ_FC1_NB_MANY>, fg, dim3(64), 0, s, slab, tasks, n_tasks, C, n_actions, act, hid);
     if (timing_ctx && timed_kernel == 1 && coevo_timing_end(timing_ctx, stream) != COEVO_OK) return COEVO_ERR_HIP;
@@ -836,13 +760,5 @@ extern "C" int coevo_dqn_forward_hidden_timed(const float *slab, const coevo_dqn
     return dqn_forward_launch(slab, tasks, n_tasks, max_rows_per_task, n_rows_total, C, n_actions, frames, nullptr, nullptr,
                               nullptr, workspace, timing_ctx, timed_kernel, stream);
 }
-
-#ifdef COEVO_PHASE_STAMPS
-extern "C" int coevo_debug_read_dqn_stamps(unsigned long long *host_out, int n_words)
-{
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(coevo::g_dqn_stamps), sizeof(unsigned long long) * n_words) ==
-                   hipSuccess ? 0 : -2;
-}
-#endif
 
 COEVO_DEFINE_TU_FLAGS(deepqn)

@@ -1,4 +1,6 @@
-"""Fault bits, ties, signed zeros and subnormals in EVERY fp32 policy-forward body of csrc/fc_forward.hip, against the oracle.
+"""Fault bits, ties, signed zeros and subnormals in EVERY fp32 policy-forward body of csrc/fc_forward.hip (fc_policy_body:
+csrc/fc_body_unrolled.hip.h, fc_policy_body_c: fc_body_compact.hip.h, fc_policy_mfma_body: fc_body_mfma32.hip.h, fc_policy_mfma16_body:
+fc_body_mfma16.hip.h, fc_rollout_small_kernel: fc_rollout_persistent.hip.h; the helpers: fc_forward_common.hip.h), against the oracle.
 
 The bodies share the output chain, the first-maximum argmax with its BAD_OUT / NO_ACTION bits, the action store and (the two
 lean forms) most of the packed LayerNorm passes as helpers; the observation entry, fc1, fc2 and the BAD_INPUT / BAD_FC1 /

@@ -1,4 +1,4 @@
-"""The two LayerNorms of the lean shared-opponent body (fc_policy_mfma16_body, csrc/fc_forward.hip) against the oracle, bit for bit.
+"""The two LayerNorms of the lean shared-opponent body (fc_policy_mfma16_body, csrc/fc_body_mfma16.hip.h) against the oracle, bit for bit.
 
 The body takes its row sums from packed butterflies over the 16x16 accumulator tiles and computes a row's mean / rstd in one
 lane per row.  Whatever order it adds in must be the canonical one (lane xor 1, 2, 4, 8 inside a 16-lane row, then
