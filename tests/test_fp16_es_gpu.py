@@ -206,6 +206,66 @@ def test_apply_every_word_and_nothing_else(D, chunks):
     assert np.array_equal(bits(part.cpu().numpy()), bits(words)) and float(sig.item()) == np.float32(sigma)
 
 
+def apply_in_a_poisoned_slab(theta, flat, D, n, sigma, lr, rng):
+    """coevo_es16_apply on `theta` packed between two nets' worth of random words, from the chunk sums `flat` [chunks][P]
+    (canonical order; the LayerNorm and padding floats of the partials are NaN: never used) -> the updated net, unpacked;
+    the words around the net and its stride's padding are checked here"""
+    m = gk.linear_mask(D)
+    stride = L.fc16_slab_stride(D)
+    slab = torch.from_numpy(rng.integers(-2 ** 31, 2 ** 31, size=3 * stride, dtype=np.int64).astype(np.int32)).to(DEV)
+    L.call("coevo_fc16_pack", L._p(torch.from_numpy(theta[None].copy()).to(DEV)), slab.data_ptr() + 4 * stride, 1, D)
+    before = slab.cpu().numpy().copy()
+    words = to_partial_layout(flat, D)
+    canon = partial_map(D)
+    words[:, ~((canon >= 0) & m[np.maximum(canon, 0)])] = np.float32("nan")
+    part = torch.from_numpy(words).to(DEV)
+    L.call("coevo_es16_apply", slab.data_ptr() + 4 * stride, L._p(part), len(flat), D, n, L._p(dev_f32(sigma)), lr)
+    torch.cuda.synchronize()
+    after = slab.cpu().numpy()
+    assert np.array_equal(after[:stride], before[:stride]) and np.array_equal(after[2 * stride:], before[2 * stride:])
+    assert np.array_equal(after[stride + used_words(D):2 * stride], before[stride + used_words(D):2 * stride])
+    return unpack16(slab, 1, 1, D)[0]
+
+
+@pytest.mark.parametrize("D", [10, 8])
+def test_apply_edges_overflow_to_inf_and_subnormals_are_kept(D):
+    """the twin of tests/test_fp16_dqn_es_gpu.py's test of the same name for the FC nets: every word against
+    tests/es16_checker.py, bit for bit, and the LayerNorm entries untouched"""
+    rng = np.random.default_rng(50 + D)
+    P = L.fc_param_count(D)
+    m = gk.linear_mask(D)
+    even = np.arange(P) % 2 == 0
+    n, sigma, lr = 16, 0.05, 0.1
+    assert ek.scale16(lr, n, sigma) == np.float32(0.125)
+    # theta at +-65504, a finite update of 500 in its direction: past the last finite half
+    big = np.where(even, np.float32(65504.0), np.float32(-65504.0))
+    flat = np.where(even, np.float32(4000.0), np.float32(-4000.0))[None]
+    got = apply_in_a_poisoned_slab(big, flat, D, n, sigma, lr, rng)
+    want, upd = ek.apply(big, D, ek.dot16(np.where(m, flat, np.float32(0))), lr, n, sigma)
+    assert np.array_equal(bits(got), bits(want)) and (np.abs(upd[m]) == 500).all()
+    assert np.isposinf(got[m & even]).all() and np.isneginf(got[m & ~even]).all()
+    assert np.array_equal(bits(got[~m]), bits(big[~m])), "LayerNorm gamma / beta changed"
+    # an all-subnormal theta and a subnormal update (dot16 = f16(4e-6), upd16 = 8 * 2^-24): moved, never flushed
+    sub = (np.arange(P) % 1015 + 1).astype(np.uint16).view(np.float16).astype(np.float32)
+    sub[~even] *= -1
+    flat = np.full((1, P), 4e-6, dtype=np.float32)
+    got = apply_in_a_poisoned_slab(sub, flat, D, n, sigma, lr, rng)
+    want, upd = ek.apply(sub, D, ek.dot16(np.where(m, flat, np.float32(0))), lr, n, sigma)
+    assert (upd[m] == np.float32(8 * 2.0 ** -24)).all()
+    assert np.array_equal(bits(got), bits(want)) and (got[m] != sub[m]).all() and np.array_equal(bits(got[~m]), bits(sub[~m]))
+    assert (np.abs(got) < 6.2e-5).all() and (got[m] != 0).mean() > 0.99
+    # chunk sums whose total passes 65504 only together: dot16 is inf, and so is the entry (theta finite)
+    theta = random_flat(rng, D)
+    flat = np.where(even, np.float32(30000.0), np.float32(-30000.0))[None].repeat(3, axis=0)
+    got = apply_in_a_poisoned_slab(theta, flat, D, n, sigma, lr, rng)
+    dot = ek.dot16(np.where(m, flat, np.float32(0)))
+    want, _ = ek.apply(theta, D, dot, lr, n, sigma)
+    assert np.isfinite(flat[0] + flat[1]).all() and np.abs(flat[0] + flat[1]).max() < 65504 and np.isinf(dot[m]).all()
+    assert np.array_equal(bits(got), bits(want))
+    assert np.isposinf(got[m & even]).all() and np.isneginf(got[m & ~even]).all()
+    assert np.array_equal(bits(got[~m]), bits(theta[~m])), "LayerNorm gamma / beta changed"
+
+
 def test_apply_scale_is_rounded_once_from_the_fp64_quotient():
     """lr / (n sigma) = 1 + 2^-11 + 2^-30 in fp64 (n = 1, sigma = 1): through an fp32 quotient scale16 would be 1.0"""
     D = 8

@@ -1,38 +1,21 @@
 """float16 nets on the GPU, bit for bit against the C checker (tests/checker16/fc16_checker.c): the slab's pack / unpack,
 coevo_fc16_forward_argmax on thousands of (net, observation) pairs with crafted overflow and exact logit ties, and the
-float16 play_game façade."""
+float16 play_game façade.  The nets (random_flat, the three-way tie, the two overflow nets) are tests/fc16_edge_nets.py's; the
+full edge suite of this kernel and of the rollout's is tests/test_fc16_forward_edges_gpu.py."""
 import numpy as np
 import pytest
 import torch
 
 from coevonet_amd import lib as L
-from coevonet_amd.fcnetwork import FCNetworkHalf, LINEAR_KEYS, param_shapes
+from coevonet_amd.fcnetwork import FCNetworkHalf
 from oracle import ref_port as rp
+from tests import fc16_edge_nets as E
 from tests import fp16_checker as ck
+from tests.fc16_edge_nets import linear_mask, random_flat   # (re-exported: the other fp16 test files import them from here)
 from tests.util import Bag, load_golden
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def linear_mask(D):
-    return np.concatenate([np.full(int(np.prod(s)), k in LINEAR_KEYS) for k, s in param_shapes(D)])
-
-
-def random_flat(rng, D, scale=0.05, ln_noise=0.05):
-    """a GA-like fp16 net: torch-like init magnitudes, fp16 Linear entries, perturbed fp32 LayerNorm affine"""
-    P = L.fc_param_count(D)
-    flat = rng.uniform(-0.3, 0.3, P).astype(np.float32) * np.float32(scale / 0.05)
-    off = 0
-    for k, s in param_shapes(D):
-        n = int(np.prod(s))
-        if k.startswith("ln"):
-            base = 1.0 if k.endswith("weight") else 0.0
-            flat[off:off + n] = np.float32(base) + rng.normal(0, ln_noise, n).astype(np.float32)
-        off += n
-    m = linear_mask(D)
-    flat[m] = flat[m].astype(np.float16).astype(np.float32)
-    return flat
 
 
 def pack(flats, D):
@@ -120,14 +103,8 @@ def test_forward_exact_ties_take_the_first_maximum():
     rng = np.random.default_rng(3)
     D = 10
     flat = random_flat(rng, D)
-    P = L.fc_param_count(D)
-    w3 = P - 5 - 5 * 256
-    # actions 1, 3 and 4 get identical output rows and biases: exact logit ties, the strict '>' scan keeps action 1
-    for o in (3, 4):
-        flat[w3 + o * 256:w3 + (o + 1) * 256] = flat[w3 + 256:w3 + 512]
-        flat[P - 5 + o] = flat[P - 5 + 1]
-    flat[P - 5 + 1] = np.float16(flat[P - 5 + 1] + np.float32(64.0))   # the tied actions are the maximum
-    flat[P - 5 + 3] = flat[P - 5 + 4] = flat[P - 5 + 1]
+    # actions 1, 3 and 4 get identical output rows and biases, the maximum: exact logit ties, the strict '>' scan keeps action 1
+    E.tie3(flat, D)
     obs = rng.uniform(-2, 2, size=(16, D)).astype(np.float32)
     act, lg, st = check_pairs(flat[None], D, obs, 16)
     assert st == 0
@@ -139,8 +116,7 @@ def test_forward_fp16_overflow_sets_status():
     D = 10
     # fc2 outputs past 65504 become inf, the LayerNorm then makes NaN: status BAD_FC2 (and the logits follow)
     flat = random_flat(rng, D)
-    o_w2 = D * 512 + 3 * 512
-    flat[o_w2:o_w2 + 256 * 512] = np.float32(60000.0)
+    E.fc2_overflow(flat, D)
     obs = rng.uniform(-2, 2, size=(4, D)).astype(np.float32)
     _, _, st = check_pairs(flat[None], D, obs, 4)
     assert st & 4
@@ -152,9 +128,7 @@ def test_forward_fp16_overflow_sets_status():
     assert st & 1
     # fc1 overflow (huge fc1 bias): BAD_FC1
     flat = random_flat(rng, D)
-    flat[D * 512:D * 512 + 512] = np.float32(65504.0)
-    flat[D * 512] = np.float32(-65504.0)
-    flat[:D * 512] = np.float32(8000.0)
+    E.fc1_overflow(flat, D)
     _, _, st = check_pairs(flat[None], D, obs[:2], 2)
     assert st & 2
 

@@ -1,7 +1,9 @@
 """The float16 device rollout against the C checker (tests/checker16/fc16_checker.c through tests/fp16_checker.py): the
 env-cycle launch coevo_mpe16_policy_cycle stepped cycle by cycle, DeviceRollout(precision="float16") through every entry
 point the trainers use, the full cfg 2 shape, the numerical edges inside launches of healthy games, and play_game's device
-route.  Every comparison is an equality: rewards fp64 bit for bit, actions exact, status words equal."""
+route.  The edge nets are tests/fc16_edge_nets.py's; the full edge suite of fc16_cycle_kernel (every class, both cache-policy
+instantiations, one to four passes) is tests/test_fc16_forward_edges_gpu.py, which drives this file's Stepper.  Every
+comparison is an equality: rewards fp64 bit for bit, actions exact, status words equal."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +14,7 @@ from coevonet_amd import lib as L
 from coevonet_amd.rollout import DeviceRollout, RolloutPlan, effective_steps
 from oracle import ref_port as rp
 from tests import fp16_checker as ck
+from tests.fc16_edge_nets import edge_nets
 from tests.test_fp16_gpu import random_flat
 from tests.util import Bag, load_golden
 
@@ -52,15 +55,16 @@ def eq_bits(got, want):
 class Stepper:
     """games stepped cycle by cycle with coevo_mpe16_policy_cycle on hand-built task / row tables.  tasks: list of
     (net id, [(game, slot), ...]); every task's rows are followed by padding rows that name the canary game (one game past
-    the real ones, NaN state, never reset): a launch that touched a padding row would write the canary's words."""
+    the real ones, NaN state, never reset): a launch that touched a padding row would write the canary's words.
+    reserved: {task index: the task's `reserved` word (COEVO_TASK_RESIDENT)}, 0 elsewhere."""
 
-    def __init__(self, slab, off, Ds, tasks, n_real, limits, first, pos_first=1, net_off_shift=None, status0=0):
+    def __init__(self, slab, off, Ds, tasks, n_real, limits, first, pos_first=1, net_off_shift=None, status0=0, reserved=None):
         self.n = n = n_real + 1
         self.n_real, self.pos_first, self.slab = n_real, pos_first, slab
         row_game, row_slot, tab = [], [], []
         for i, (net, rows) in enumerate(tasks):
             shift = (net_off_shift or {}).get(i, 0)
-            tab.append((off[net] + shift, len(row_game), len(rows), Ds[net], 0))
+            tab.append((off[net] + shift, len(row_game), len(rows), Ds[net], (reserved or {}).get(i, 0)))
             for g, s in rows:
                 row_game.append(g)
                 row_slot.append(s)
@@ -329,44 +333,6 @@ def test_full_size_cfg2():
 
 
 # ---------------------------------------------------------------------------------------------- edges
-def tie_net(rng, D=10):
-    """actions 1, 3 and 4 share their output row and bias and carry the maximum: exact three-way logit ties"""
-    flat = random_flat(rng, D)
-    P = L.fc_param_count(D)
-    w3 = P - 5 - 5 * 256
-    for o in (3, 4):
-        flat[w3 + o * 256:w3 + (o + 1) * 256] = flat[w3 + 256:w3 + 512]
-    flat[P - 5 + 1] = np.float32(np.float16(flat[P - 5 + 1] + np.float32(64.0)))
-    flat[P - 5 + 3] = flat[P - 5 + 4] = flat[P - 5 + 1]
-    return flat
-
-
-def subnormal_values(rng, n):
-    k = rng.integers(1, 1024, n) * rng.choice([-1, 1], n)
-    return (k.astype(np.float64) * 2.0 ** -24).astype(np.float32)   # every one an fp16 subnormal, exactly
-
-
-def edge_nets(rng):
-    """-> {name: (flat, D)}"""
-    out = {"ties": (tie_net(rng), 10)}
-    f = random_flat(rng, 10)
-    o_w2 = 10 * 512 + 3 * 512
-    f[o_w2:o_w2 + 256 * 512] = subnormal_values(rng, 256 * 512)
-    out["fc2_subnormal"] = (f, 10)
-    f = random_flat(rng, 8)
-    f[:8 * 512] = subnormal_values(rng, 8 * 512)
-    out["fc1_subnormal"] = (f, 8)
-    f = random_flat(rng, 10)
-    f[o_w2:o_w2 + 256 * 512] = np.float32(60000.0)
-    out["fc2_overflow"] = (f, 10)
-    f = random_flat(rng, 10)
-    f[10 * 512:10 * 512 + 512] = np.float32(65504.0)
-    f[10 * 512] = np.float32(-65504.0)
-    f[:10 * 512] = np.float32(8000.0)
-    out["fc1_overflow"] = (f, 10)
-    return out
-
-
 def edge_batch(seed, names):
     """12 healthy games plus, per named edge net, two games it plays in (full-length games: every forward the launch runs is
     one the checker runs, so the status words can be compared)"""
