@@ -26,7 +26,9 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 # what bench.py does - run the host-cores mode in a process of its own.
 
 __all__ = ["HalfGAEngine", "HalfESEngine", "DeepQNHalf", "HalfDQNGAEngine", "HalfSynthRollout", "HalfDQNESEngine",
-           "CrossPlay", "DQNCrossPlay", "test_agents", "cross_play_checkpoints"]
+           "CrossPlay", "DQNCrossPlay", "test_agents", "cross_play_checkpoints", "BaselineCrossPlay", "DQNBaselineCrossPlay",
+           "RandomBaseline", "PeriodicBaseline", "ConstantBaseline", "AlwaysFire", "MLPBaseline", "load_ppo_baseline"]
+_BASELINE_NAMES = frozenset(__all__[__all__.index("BaselineCrossPlay"):])
 
 
 def __getattr__(name):
@@ -49,4 +51,7 @@ def __getattr__(name):
     if name in ("CrossPlay", "DQNCrossPlay", "test_agents", "cross_play_checkpoints"):
         from . import crossplay
         return getattr(crossplay, name)
+    if name in _BASELINE_NAMES:
+        from . import baselines
+        return getattr(baselines, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

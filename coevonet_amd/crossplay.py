@@ -274,22 +274,37 @@ def _precision_of(nets, half_cls, float_cls):
     raise ValueError("cross-play needs nets of one precision: all float32 or all float16")
 
 
-def test_agents(env, args, episodes=10):
+def test_agents(env, args, episodes=10, opponent=None):
     """main.py:193-249 on this package's envs: ``load_agent_for_testing``, then the mean rewards of `episodes` evaluation games
     (``play_game(..., eval=True)``) - played as ONE rollout, under the reset ordinals the `episodes` play_game calls would have
     taken from `env`, whose ``n_resets`` moves on by `episodes`.  simple_adversary: -> the mean (agent_0, agent_1, adversary)
     triple.  Atari games: ``args.play_against_yourself`` only (the reference's random dummy opponent is not built); the agent
     loaded for agent_0 plays both seats -> the mean (first_0, second_0) pair.  Bit for bit the sums and the division of
-    main.py's loop over play_game."""
+    main.py's loop over play_game.
+
+    ``opponent`` (coevonet_amd/baselines.py; None: everything above, to the letter).  Atari games: a scripted baseline that
+    plays second_0 against the loaded agent - ``RandomBaseline()`` is main.py's default test path.  simple_adversary: a
+    {role: baseline} dict whose baselines replace the loaded agents of those roles."""
     from .game_logic import ATARI_GAMES
     from .io_utils import load_agent_for_testing
     if args.game == "simple_adversary_v3":
         _mpe_env_or_raise(env)
         from .fcnetwork import FCNetwork, FCNetworkHalf
+        if opponent is not None:
+            from .baselines import BaselineCrossPlay, _is_baseline
+            if not isinstance(opponent, dict) or not opponent or set(opponent) - set(ROLES) or \
+                    not all(_is_baseline(b) for b in opponent.values()):
+                raise ValueError(f"test_agents: for simple_adversary `opponent` is a {{role: baseline}} dict over {ROLES}")
         loaded = load_agent_for_testing(args, env)
         if loaded is None:
             raise ValueError(f"Unsupported algorithm for testing: {args.algorithm}")
         a0, a1, adv = (a.model for a in loaded)
+        if opponent is not None:
+            seat = {r: [opponent.get(r, m)] for r, m in zip(ROLES, (a0, a1, adv))}
+            cp = BaselineCrossPlay(seat["agent_0"], seat["agent_1"], seat["adversary_0"], episodes=episodes,
+                                   limit=_eval_limit(args), max_cycles=env.max_cycles, env_seed=env.seed_value)
+            res = cp.run(_take_ordinals(env, episodes))
+            return tuple(float(v) for v in res.payoff[0, 0, 0])
         precision = _precision_of((a0, a1, adv), FCNetworkHalf, FCNetwork)
         cp = CrossPlay([a0], [a1], [adv], episodes=episodes, limit=_eval_limit(args), max_cycles=env.max_cycles,
                        precision=precision, env_seed=env.seed_value)
@@ -297,6 +312,19 @@ def test_agents(env, args, episodes=10):
         return tuple(float(v) for v in res.payoff[0, 0, 0])
     if args.game in ATARI_GAMES:
         _atari_env_or_raise(env)
+        if opponent is not None:
+            from .baselines import DQNBaselineCrossPlay, ScriptedBaseline
+            if not isinstance(opponent, ScriptedBaseline):
+                raise ValueError("test_agents: for the Atari games `opponent` is a scripted baseline (RandomBaseline, "
+                                 "PeriodicBaseline, ConstantBaseline)")
+            loaded = load_agent_for_testing(args, env)
+            if loaded is None:
+                raise ValueError(f"Unsupported algorithm for testing: {args.algorithm}")
+            net = (loaded[0] if isinstance(loaded, (tuple, list)) else loaded).model
+            cp = DQNBaselineCrossPlay([net], [opponent], env.C, env.n_actions, episodes=episodes, limit=_eval_limit(args),
+                                      env_seed=env.seed_value)
+            res = cp.run(_take_ordinals(env, episodes))
+            return tuple(float(v) for v in res.payoff[0, 0])
         if not getattr(args, "play_against_yourself", False):
             raise ValueError("test_agents: the Atari games are tested with args.play_against_yourself only (the random dummy "
                              "opponent is not built)")
