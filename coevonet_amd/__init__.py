@@ -29,6 +29,8 @@ __all__ = ["HalfGAEngine", "HalfESEngine", "DeepQNHalf", "HalfDQNGAEngine", "Hal
            "CrossPlay", "DQNCrossPlay", "test_agents", "cross_play_checkpoints", "BaselineCrossPlay", "DQNBaselineCrossPlay",
            "RandomBaseline", "PeriodicBaseline", "ConstantBaseline", "AlwaysFire", "MLPBaseline", "load_ppo_baseline"]
 _BASELINE_NAMES = frozenset(__all__[__all__.index("BaselineCrossPlay"):])
+_GAUNTLET_NAMES = ("Gauntlet", "Champion", "GauntletResult", "GauntletSpec")
+__all__ += list(_GAUNTLET_NAMES)
 
 
 def __getattr__(name):
@@ -54,4 +56,7 @@ def __getattr__(name):
     if name in _BASELINE_NAMES:
         from . import baselines
         return getattr(baselines, name)
+    if name in _GAUNTLET_NAMES:
+        from . import gauntlet
+        return getattr(gauntlet, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -11,17 +11,9 @@
 // over them are unrolled); a value of the second hidden layer is folded into the five logit chains as soon as it exists - the
 // chains still run over k ascending - so the second layer is never stored.  No matrix cores: they would change the summation
 // order for no gain at this size.
-#include "coevo_common.hip.h"
-#include "philox.hip.h"
-
-#include "../../include/coevo_baseline.h"
+#include "baseline_pieces.hip.h"
 
 namespace coevo {
-
-constexpr int MLP_H = COEVO_MLP_H, MLP_NACT = COEVO_MLP_NACT, MLP_TILE = COEVO_MLP_ROW_TILE;
-__host__ __device__ constexpr int mlp_params(int D) { return MLP_H * D + MLP_H + MLP_H * MLP_H + MLP_H + MLP_NACT * MLP_H + MLP_NACT; }
-__host__ __device__ constexpr int mlp_stride(int D) { return (mlp_params(D) + 3) / 4 * 4; }
-constexpr int MLP_LDS_FLOATS = mlp_stride(10);
 
 // ---- scripted seats --------------------------------------------------------------------------------------------------
 __global__ void baseline_actions_kernel(const int32_t *seats, int n_seats, const int64_t *game_ordinal, uint64_t ordinal_add,
@@ -33,36 +25,13 @@ __global__ void baseline_actions_kernel(const int32_t *seats, int n_seats, const
     const int game = s[0], row = s[1], kind = s[2], arg = s[3], slot = s[6];
     if (game < 0 || game >= n_games || row < 0 || row >= n_rows) return;
     int action;
-    if (kind == COEVO_BL_RANDOM) {
-        const uint64_t ordinal = (uint64_t)game_ordinal[game] + ordinal_add;
-        const u32x4 o = philox4x32_10((uint32_t)ordinal, (uint32_t)(ordinal >> 32), k, (uint32_t)slot, (uint32_t)s[4],
-                                      (uint32_t)s[5]);
-        action = (int)(((uint64_t)o.v[0] * (uint64_t)n_actions) >> 32);
-    } else if (kind == COEVO_BL_PERIODIC) {
-        if (arg < 0) return;
-        action = (int)(((uint64_t)arg + (uint64_t)k) % (uint64_t)n_actions);
-    } else if (kind == COEVO_BL_CONSTANT) {
-        if (arg < 0 || arg >= n_actions) return;
-        action = arg;
-    } else {
+    if (!scripted_action(kind, arg, (uint32_t)s[4], (uint32_t)s[5], [=] { return (uint64_t)game_ordinal[game] + ordinal_add; }, slot, k,
+                         n_actions, action))
         return;
-    }
     actions[row] = action;
 }
 
 // ---- the policy net --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool not_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-// the largest |bits| of a layer's outputs, taken as each output appears (the empty asm pins the running maximum there:
-// left to itself the compiler gathers the 64 tests at the end of the layer and keeps every pre-ReLU value alive for them)
-__device__ __forceinline__ void track_magnitude(uint32_t &m, float v)
-{
-    const uint32_t b = __float_as_uint(v) & 0x7fffffffu;
-    m = b > m ? b : m;
-    asm volatile("" : "+v"(m));
-}
-__device__ __forceinline__ bool magnitude_not_finite(uint32_t m) { return m >= 0x7f800000u; }
-__device__ __forceinline__ float relu_plus_zero(float v) { return v > 0.0f ? v : 0.0f; }   // NaN and -0 give +0
-
 // one row on one thread: w = the net in LDS (flat order), x = the observation -> the five logits and the status bits
 template <int D>
 __device__ __forceinline__ int mlp_row(const float *w, const float (&x)[10], float (&logit)[MLP_NACT])
@@ -108,16 +77,6 @@ __device__ __forceinline__ int mlp_row(const float *w, const float (&x)[10], flo
     for (int c = 0; c < MLP_NACT; ++c) bad |= not_finite(logit[c]);
     if (bad) st |= COEVO_ST_BAD_OUT;
     return st;
-}
-
-__device__ __forceinline__ int first_max(const float (&logit)[MLP_NACT])
-{
-    int best = 0;
-    float cur = logit[0];
-#pragma unroll
-    for (int c = 1; c < MLP_NACT; ++c)
-        if (logit[c] > cur) { cur = logit[c]; best = c; }
-    return best;
 }
 
 // SEATS: the rows are seats of simple_adversary games (observe from `state`); else rows of `obs`.  One workgroup per task.

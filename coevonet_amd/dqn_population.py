@@ -34,7 +34,7 @@ from . import lib as L
 from .atari_synthetic import SYNTH_SEED
 from .deepqn import DeepQN
 from .population import (ES_CHUNKS, N_EVAL, ROLES2, CoESUpdate, NetTable, SlabIO, adapt_mutation_power2, captured, co_es_games2,
-                         co_ga_games2, dqn_half_route, eval_gate_limits, mean_eval, refuse_ga_sharing_modes,
+                         co_ga_games2, dqn_half_route, eval_gate_limits, mean_eval, refuse_ga_sharing_modes, refuse_gauntlet,
                          shard_and_gather, slab_layout)
 
 SIGMA2 = ("mutation_power_agent_0", "mutation_power_agent_1")
@@ -573,6 +573,7 @@ class DQNGATrainer:
     loaded); ``step`` / ``finish`` / ``close`` and ``collect=False`` are the same code over either engine."""
 
     def __init__(self, env, args, collect=True, dist_ctx=None):
+        refuse_gauntlet(args, "the DeepQN trainers")
         refuse_ga_sharing_modes(args, "DeepQN Co-GA training")
         self.half = dqn_half_route(args, "DeepQN Co-GA training with precision", frames_mode, dist_ctx, "gather_ga2")
         self.env, self.args, self.collect = env, args, collect
@@ -770,6 +771,7 @@ class DQNESTrainer:
     ValueError before anything is read or loaded); the host's sigma rule sits on top of either engine's ``generation``."""
 
     def __init__(self, env, args, collect=True, dist_ctx=None):
+        refuse_gauntlet(args, "the DeepQN trainers")
         refuse_ga_sharing_modes(args, "DeepQN Co-ES training")
         self.half = dqn_half_route(args, "DeepQN Co-ES with precision", frames_mode, dist_ctx, "gather_es",
                                    extensions=("coevo_antithetic", "coevo_centered_rank"))

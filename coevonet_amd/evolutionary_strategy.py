@@ -36,7 +36,8 @@ from .es_half import HalfESEngine
 from .game_logic import create_agent
 from .mpe.simple_adversary import ENV_SEED
 from .population import (ES_CHUNKS, N_EVAL, RET_SLOT, ROLE_D, ROLES, SIGMA_ATTR, CoESSchedule, CoESUpdate, NetTable, SlabIO,
-                         adapt_mutation_power, co_es_games, half_route, shard_and_gather, slab_layout)
+                         adapt_mutation_power, co_es_games, half_route, refuse_gauntlet, shard_and_gather,
+                         slab_layout)
 from .rollout import DeviceRollout, HostEnvRollout, effective_steps
 
 
@@ -162,6 +163,7 @@ def _linear_mask(D):
 
 class ESTrainer:
     def __init__(self, env, args, rng=None, env_mode=None, collect=True, dist_ctx=None):
+        refuse_gauntlet(args, "the Co-ES trainers")
         # float16: rng "device_philox" + the device env on one rank, no extension mode, or a ValueError before anything else
         self.half = half_route(args, "Co-ES with precision", rng, env_mode, dist_ctx, "gather_es",
                                extensions=("coevo_antithetic", "coevo_centered_rank"))

@@ -738,6 +738,8 @@ class GAResult:
         self.fitness, self.elite_ids, self.diversity, self.sigma_after = [], [], [], []
         self.game_rewards = []   # per generation: play_game triples of the 3*pop*hof training games, reference order
         self.seconds = []
+        # with a baseline gauntlet (gauntlet.py): per generation the mean (agent_0, agent_1, adversary_0) triple of every match
+        self.gauntlet, self.gauntlet_matches = None, None
 
 
 def initial_population(env, args):
@@ -762,7 +764,10 @@ class GATrainer:
     """The generation loop of genetic_algorithm_train as an object, one ``step()`` per generation (bench.py times
     exactly these steps)."""
 
-    def __init__(self, env, args, rng=None, env_mode=None, collect=True, dist_ctx=None):
+    def __init__(self, env, args, rng=None, env_mode=None, collect=True, dist_ctx=None, gauntlet=None):
+        # the baseline gauntlet (gauntlet.py): what it does not cover is refused first, before the GPU is touched
+        self.gauntlet_spec = _gauntlet_spec_or_raise(args, gauntlet, rng, env_mode, dist_ctx)
+        self.gauntlet, self._gauntlet_pending = None, None
         # float16: rng "device_philox" + the device env on one rank, or a ValueError before anything else happens
         self.half = half_route(args, "Co-GA training with precision", rng, env_mode, dist_ctx, "gather_ga",
                                extensions=GA_SHARING_MODES)
@@ -820,6 +825,28 @@ class GATrainer:
         self.res.engine = self.eng
         if self.device_loop or self.sharded_loop:
             self.eng.setup_device_loop(args, capacity=max(getattr(args, "generations", 0), 1) + 64)
+        if self.gauntlet_spec is not None:
+            from .gauntlet import Gauntlet
+            spec = self.gauntlet_spec
+            self.gauntlet = Gauntlet(spec.matches(), episodes=spec.episodes, limit=args.max_evaluation_steps,
+                                     max_cycles=getattr(env, "max_cycles", 25),
+                                     env_seed=getattr(env, "seed_value", ENV_SEED) or ENV_SEED)
+            self.res.gauntlet, self.res.gauntlet_matches = [], spec.names()
+
+    def _enqueue_gauntlet(self):
+        """generation self.gen's champions - the Hall of Fame's newest members, after this generation's promotion - copied slab
+        to slab and scored behind the generation on the same stream; nothing is read back here"""
+        gt, eng = self.gauntlet, self.eng
+        for r in self.gauntlet_spec.champion_roles():
+            gt.set_champion(r, eng._ptr(r, "hof", eng.hof - 1))
+        gt.enqueue(self.gauntlet_spec.first_ordinal)
+        self._gauntlet_pending = self.gen
+
+    def _harvest_gauntlet(self):
+        """the result of the generation enqueued last, read no earlier than the next step (or finish())"""
+        if self._gauntlet_pending is not None:
+            self.res.gauntlet.append(self.gauntlet.result().mean.tolist())
+            self._gauntlet_pending = None
 
     def step(self):
         """generation self.gen: play its games (+ the previous generation's 10 evaluation games), select, breed"""
@@ -852,6 +879,7 @@ class GATrainer:
             eng.rollout(gen, with_prev_eval=gen > 0)
         if gen > 0:
             _finish_generation(args, gen - 1, eng.eval_rewards(), res)
+            self._harvest_gauntlet()   # (eval_rewards synchronised: generation gen - 1's gauntlet is long complete)
         eng.select()
         sigmas = {r: getattr(args, SIGMA_ATTR[r]) for r in ROLES}
         if self.half:
@@ -860,6 +888,8 @@ class GATrainer:
             eng.breed_host_reference(self.env, args, sigmas)
         else:
             eng.breed_device(gen, sigmas)
+        if self.gauntlet is not None:
+            self._enqueue_gauntlet()
         if self.collect:
             res.game_rewards.append(eng.rewards_host()[:eng.n_main].copy())
             res.fitness.append([eng.fitness[r].cpu().numpy().tolist() for r in ROLES])
@@ -932,12 +962,14 @@ class GATrainer:
                 self.eng.ro.collect_stamps()
                 self._sync_history_from_device(upto=self.gen - 1)
             _finish_generation(self.args, self.gen - 1, self.eng.eval_only(self.gen - 1), self.res)
+            self._harvest_gauntlet()
         if hasattr(self.env, "n_resets"):
             self.env.n_resets = self.first_ordinal + self.gen * (3 * self.args.population * self.args.hof_size + N_EVAL)
         return self.res
 
 
-def genetic_algorithm_train(env, agent, args, output_dir, rng=None, env_mode=None, collect=True, dist_ctx=None):
+def genetic_algorithm_train(env, agent, args, output_dir, rng=None, env_mode=None, collect=True, dist_ctx=None,
+                            gauntlet=None):
     """Drop-in for genetic_algorithm.py:51 (``agent`` is unused there too).  Returns a GAResult (the reference returns
     None and plots instead).
 
@@ -946,12 +978,16 @@ def genetic_algorithm_train(env, agent, args, output_dir, rng=None, env_mode=Non
     args.precision "float16" trains half nets through HalfGAEngine: device_philox, device env and one rank only; anything
     else raises ValueError before the GPU is touched (DESIGN 6a "Float16 trainers").  With args.game pong_v3 / boxing_v2 the
     DeepQN trainer takes over (dqn_population.dqn_genetic_algorithm_train); there "float16" trains half DeepQN nets through
-    HalfDQNGAEngine on one rank with the frames synthesised on the device (DESIGN 6a "Float16 DeepQN trainers")."""
+    HalfDQNGAEngine on one rank with the frames synthesised on the device (DESIGN 6a "Float16 DeepQN trainers").
+    gauntlet / args.coevo_gauntlet (a gauntlet.GauntletSpec or its dict): every generation's champions are scored against fixed
+    baselines -> GAResult.gauntlet, GAResult.gauntlet_matches and a "gauntlet" key in every metrics line."""
     if getattr(args, "game", "simple_adversary_v3") != "simple_adversary_v3":   # the two-player Atari games
+        if gauntlet is not None:
+            raise ValueError("gauntlet: the baseline gauntlet is not built for the DeepQN trainers")
         from .dqn_population import dqn_genetic_algorithm_train
         return dqn_genetic_algorithm_train(env, agent, args, output_dir, collect=collect, dist_ctx=dist_ctx)
     from .io_utils import GA_FILES, MetricsWriter, agents_from_flat, save_model, save_state_dicts
-    tr = GATrainer(env, args, rng=rng, env_mode=env_mode, collect=collect, dist_ctx=dist_ctx)
+    tr = GATrainer(env, args, rng=rng, env_mode=env_mode, collect=collect, dist_ctx=dist_ctx, gauntlet=gauntlet)
     save = bool(getattr(args, "save", False)) and output_dir is not None
     mw = MetricsWriter(output_dir)
     written = 0
@@ -968,7 +1004,7 @@ def genetic_algorithm_train(env, agent, args, output_dir, rng=None, env_mode=Non
                      eval_rewards={r: res.rewards[r][g] for r in ROLES} if g < len(res.rewards["agent_0"]) else None,
                      mutation_power=have(res.sigma_after), diversity=have(res.diversity), elite_ids=have(res.elite_ids),
                      fitness_best=[max(f) for f in res.fitness[g]] if g < len(res.fitness) else None,
-                     seconds=have(res.seconds))
+                     seconds=have(res.seconds), **({"gauntlet": have(res.gauntlet)} if tr.gauntlet is not None else {}))
             written += 1
 
     for _ in range(args.generations):
@@ -990,6 +1026,30 @@ def genetic_algorithm_train(env, agent, args, output_dir, rng=None, env_mode=Non
         written = 0
     flush_metrics(res, len(res.rewards["agent_0"]))
     return res
+
+
+def _gauntlet_spec_or_raise(args, given, rng, env_mode, dist_ctx):
+    """the GauntletSpec of args.coevo_gauntlet / GATrainer(gauntlet=...) or None; what the gauntlet does not cover is a ValueError
+    that names the option, raised before the library is loaded.  There is no silent switch of loop."""
+    spec = given if given is not None else getattr(args, "coevo_gauntlet", None)
+    if spec is None:
+        return None
+    what = "coevo_gauntlet"
+    precision = getattr(args, "precision", "float32")
+    if precision != "float32":
+        raise ValueError(f"{what}: float32 training only, not args.precision {precision!r}")
+    if dist_ctx is not None:
+        raise ValueError(f"{what}: one rank only, not a sharded population (dist_ctx)")
+    env_mode = env_mode or getattr(args, "coevo_env", "device")
+    if env_mode != "device":
+        raise ValueError(f'{what}: the device env only, not env "{env_mode}" (args.coevo_env)')
+    rng = rng or getattr(args, "coevo_rng", "host_reference")
+    sharing = bool(getattr(args, "coevo_hof_mean", False)) or bool(getattr(args, "coevo_population_sharing", False))
+    if rng == "device_philox" and getattr(args, "coevo_device_loop", True) and not sharing:
+        raise ValueError(f"{what}: the host-driven generation loop only - with rng \"device_philox\" set "
+                         "args.coevo_device_loop = False (the host-free device loop does not carry the gauntlet)")
+    from .gauntlet import GauntletSpec
+    return GauntletSpec.of(spec)
 
 
 def _finish_generation(args, gen, eval_triple, res):

@@ -24,6 +24,7 @@ CROSSPLAY_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_crossplay.h")
 SHARING_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_sharing.h")   # the Co-GA population-sharing entry points, likewise
 SHARING16_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_sharing16.h")   # ... and their float16 pairwise distance
 BASELINE_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_baseline.h")   # the baseline-opponent entry points, likewise
+GAUNTLET_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_gauntlet.h")   # the baseline-gauntlet entry points, likewise
 
 
 class CoevoError(RuntimeError):
@@ -200,6 +201,20 @@ def _parse_baseline_header(text):
 
 K_BL, _BL_SIGS = _parse_baseline_header(_header_text(BASELINE_HEADER_PATH))
 
+
+def _parse_gauntlet_header(text):
+    """include/coevo_gauntlet.h -> (its constants, its entry points), read like coevo_baseline.h: prototypes and constants
+    only, and no name that one of the six other headers declares"""
+    consts, structs, sigs = parse_header(text, known=STRUCTS)
+    if (set(structs) != set(STRUCTS)
+            or set(sigs) & (set(_SIGS) | set(_EXT_SIGS) | set(_XP_SIGS) | set(_SH_SIGS) | set(_SH16_SIGS) | set(_BL_SIGS))
+            or set(consts) & (set(K) | set(K_EXT) | set(K_XP) | set(K_SH) | set(K_BL))):
+        raise CoevoError("include/coevo_gauntlet.h: declares a struct or repeats a name of another header")
+    return consts, sigs
+
+
+K_GT, _GT_SIGS = _parse_gauntlet_header(_header_text(GAUNTLET_HEADER_PATH))
+
 OBS_STRIDE, LOGIT_STRIDE, FC_MAX_ROWS = K["COEVO_OBS_STRIDE"], K["COEVO_LOGIT_STRIDE"], K["COEVO_FC_MAX_ROWS"]
 MPE_STATE_DOUBLES, STAMP_SLOTS = K["COEVO_MPE_STATE_DOUBLES"], K["COEVO_STAMP_SLOTS"]
 ST_NAMES = {K["COEVO_ST_BAD_INPUT"]: "input contains inf or NaN",
@@ -278,6 +293,11 @@ def baseline_symbols():
     return sorted(_BL_SIGS)
 
 
+def gauntlet_symbols():
+    """the entry points of include/coevo_gauntlet.h, bound by load() beside the six other tables"""
+    return sorted(_GT_SIGS)
+
+
 def load():
     """dlopen libcoevo.so; raises CoevoError when it has not been built (python -m coevonet_amd.build)."""
     global _lib
@@ -286,7 +306,8 @@ def load():
             raise CoevoError(f"{LIB_PATH} is missing: build the HIP extension first "
                              "(python -m coevonet_amd.build); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGS, **_EXT_SIGS, **_XP_SIGS, **_SH_SIGS, **_SH16_SIGS, **_BL_SIGS}.items():
+        for name, (res, args) in {**_SIGS, **_EXT_SIGS, **_XP_SIGS, **_SH_SIGS, **_SH16_SIGS, **_BL_SIGS,
+                                  **_GT_SIGS}.items():
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -656,6 +656,14 @@ def refuse_ga_sharing_modes(args, what):
             raise ValueError(f"{what} is not built with args.{attr}")
 
 
+def refuse_gauntlet(args, what):
+    """args.coevo_gauntlet (gauntlet.py) is served by the float32 Co-GA trainer of simple_adversary alone; the first thing the
+    other trainers do"""
+    if getattr(args, "coevo_gauntlet", None) is not None:
+        raise ValueError(f"args.coevo_gauntlet: the baseline gauntlet is not built for {what} (only for GATrainer in float32 on "
+                         "one rank, in the host-driven loop, with the device env)")
+
+
 def half_route(args, what, rng, env_mode, dist_ctx, gather_name, extensions=()):
     """Which engines a trainer of the fully connected nets builds: False = the float32 ones, True = the float16 ones
     (HalfGAEngine / HalfESEngine).  What float16 does not cover is refused here with "`what` float16 ...", the first thing a
