@@ -36,7 +36,8 @@ class HalfDQNESEngine(_DQNSlabIO):
     _pack_unpack = ("coevo_dqn16_pack", "coevo_dqn16_unpack")   # flat arrays carry fp16 values in float32
 
     def __init__(self, pop, C, n_actions, T_train, T_eval, device="cuda", env_seed=SYNTH_SEED, philox_seed=0, first_ordinal=1,
-                 chunks=ES_CHUNKS, *, shard=(0, 1), gather=None, frames="device", antithetic=False, centered_rank=False):
+                 chunks=ES_CHUNKS, *, shard=(0, 1), gather=None, frames="device", antithetic=False, centered_rank=False,
+                 env="synthetic", duel_points=21, duel_credit="next"):
         # what float16 does not cover is refused before the library is loaded
         if tuple(shard) != (0, 1):
             raise ValueError(f"HalfDQNESEngine: precision float16 runs on one rank only, not shard {tuple(shard)}")
@@ -50,6 +51,8 @@ class HalfDQNESEngine(_DQNSlabIO):
             raise ValueError("HalfDQNESEngine: the centered-rank transform is not built for precision float16")
         if not (1 <= int(pop) <= 65535 and 1 <= int(chunks) <= 64):
             raise ValueError(f"HalfDQNESEngine: population {pop} (1 .. 65535) or update chunks {chunks} (1 .. 64) out of range")
+        from .duel_rollout import duel_env_option   # (imports this module's imports)
+        self.duel = duel_env_option("HalfDQNESEngine", env, duel_points, duel_credit, C, frames, shard)
         self.pop, self.chunks = int(pop), int(chunks)
         self.C, self.n_actions, self.device = C, n_actions, device
         self.Cw = C   # (the fp16 slab has one fc1 layout)
@@ -70,10 +73,14 @@ class HalfDQNESEngine(_DQNSlabIO):
         net = NetTable(self.base, strides)
         games, ordinal0, eval_games, eval_ordinal0 = co_es_games2(net, 0, self.pop, first_ordinal, self.pop)
         self.n_main = len(games)
-        self.ro = HalfSynthRollout(games, net.net_off, ordinal0, C, n_actions, self.slab, env_seed, self.per_gen, device)
+        rollout = HalfSynthRollout
+        if self.duel is not None:   # the same tables and forward launches; the env-step launches are the duel's
+            import functools
+            from .duel_rollout import HalfDuelRollout   # (imports this module)
+            rollout = functools.partial(HalfDuelRollout, **self.duel)
+        self.ro = rollout(games, net.net_off, ordinal0, C, n_actions, self.slab, env_seed, self.per_gen, device)
         self.ro.set_limits(np.full(self.n_main, self.T_train, dtype=np.int32))
-        self.eval_ro = HalfSynthRollout(eval_games, net.net_off, eval_ordinal0, C, n_actions, self.slab, env_seed, self.per_gen,
-                                        device)
+        self.eval_ro = rollout(eval_games, net.net_off, eval_ordinal0, C, n_actions, self.slab, env_seed, self.per_gen, device)
         self.eval_ro.set_limits(np.full(N_EVAL, self.T_eval, dtype=np.int32))
         # ---- small device buffers ----------------------------------------------------------------------------------
         f32 = dict(dtype=torch.float32, device=device)

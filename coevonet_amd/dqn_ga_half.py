@@ -99,7 +99,8 @@ class HalfDQNGAEngine(DQNGAEngine):
 
     def __init__(self, pop, hof, elites, C, n_actions, T_train, T_eval, device="cuda", env_seed=SYNTH_SEED, philox_seed=0,
                  first_ordinal=1, capacity=1024, sigmas=(0.05, 0.05), sig_min=0.001, sig_max=0.2, adaptive=True, *,
-                 shard=(0, 1), gather=None, frames="device", fc1_layout="streamed"):
+                 shard=(0, 1), gather=None, frames="device", fc1_layout="streamed", env="synthetic", duel_points=21,
+                 duel_credit="next"):
         # what float16 does not cover is refused before the library is loaded
         if tuple(shard) != (0, 1):
             raise ValueError(f"HalfDQNGAEngine: precision float16 runs on one rank only, not shard {tuple(shard)}")
@@ -116,10 +117,15 @@ class HalfDQNGAEngine(DQNGAEngine):
             self._pack_unpack = ("coevo_dqn16_pack_tiled", "coevo_dqn16_unpack_tiled")
         super().__init__(pop, hof, elites, C, n_actions, T_train, T_eval, device=device, env_seed=env_seed,
                          philox_seed=philox_seed, first_ordinal=first_ordinal, capacity=capacity, sigmas=sigmas,
-                         sig_min=sig_min, sig_max=sig_max, adaptive=adaptive)
+                         sig_min=sig_min, sig_max=sig_max, adaptive=adaptive, env=env, duel_points=duel_points,
+                         duel_credit=duel_credit)
         self.fc1_tiled = self._half_tiled   # (self.Cw stays the plain channel count)
 
     def _rollout(self, games, net_off, ordinal0, env_seed):
+        if self.duel is not None:
+            from .duel_rollout import HalfDuelRollout   # (imports this module)
+            return HalfDuelRollout(games, net_off, ordinal0, self.C, self.n_actions, self.slab, env_seed, self.per_gen,
+                                   self.device, fc1_tiled=self._half_tiled, **self.duel)
         return HalfSynthRollout(games, net_off, ordinal0, self.C, self.n_actions, self.slab, env_seed, self.per_gen, self.device,
                                 fc1_tiled=self._half_tiled)
 

@@ -356,8 +356,11 @@ class DQNGAEngine(_DQNSlabIO):
 
     def __init__(self, pop, hof, elites, C, n_actions, T_train, T_eval, device="cuda", env_seed=SYNTH_SEED,
                  philox_seed=0, shard=(0, 1), gather=None, first_ordinal=1, capacity=1024, sigmas=(0.05, 0.05),
-                 sig_min=0.001, sig_max=0.2, adaptive=True, frames="device"):
+                 sig_min=0.001, sig_max=0.2, adaptive=True, frames="device", env="synthetic", duel_points=21,
+                 duel_credit="next"):
         assert 1 <= elites <= pop and hof >= 1 and frames in ("device", "host")
+        from .duel_rollout import duel_env_option   # (imports this module)
+        self.duel = duel_env_option(type(self).__name__, env, duel_points, duel_credit, C, frames, shard)
         self.frames = frames
         self.pop, self.hof, self.E, self.C, self.n_actions = pop, hof, elites, C, n_actions
         # the float32 slab keeps fc1 TILED for v_mfma_f32_16x16x4 (its tasks carry 10 / 16 frames; include/coevo.h
@@ -426,6 +429,10 @@ class DQNGAEngine(_DQNSlabIO):
         bounds = [0, self.n_main // 2, len(games)] if (K > 1 and self.n_main >= 2) else None
         if self.frames == "host":   # env in host memory: the cohorts alternate between the host cores and the GPU
             bounds = even_bounds(len(games), int(os.environ.get("COEVO_FRAME_COHORTS", "3")))
+        if self.duel is not None:   # the same tables and forward launches; the env-step launches are the duel's
+            from .duel_rollout import DuelRollout
+            return DuelRollout(games, net_off, ordinal0, self.C, self.n_actions, self.slab, env_seed, self.per_gen, self.device,
+                               bounds=bounds, fc1_tiled=self.fc1_tiled, **self.duel)
         return (HostFrameRollout if self.frames == "host" else SynthRollout)(
             games, net_off, ordinal0, self.C, self.n_actions, self.slab, env_seed, self.per_gen, self.device, bounds=bounds,
             fc1_tiled=self.fc1_tiled)
@@ -585,16 +592,18 @@ class DQNGATrainer:
                       first_ordinal=self.first_ordinal, capacity=max(getattr(args, "generations", 0), 1) + 64,
                       sigmas=(args.mutation_power_agent_0, args.mutation_power_agent_1),
                       sig_min=args.min_mutation_power, sig_max=args.max_mutation_power, adaptive=args.adaptive)
+        from .duel_rollout import env_option_of   # (imports this module)
+        env_kw = env_option_of(env)   # a DuelAEC: the engine plays the duel, with the env object's points and credit rule
         if self.half:   # the creation order and generator consumption of float32; the nets rounded as .to(float16) rounds
             from .dqn_ga_half import HalfDQNGAEngine   # (imports this module)
             pop_flat, hof_flat = ({r: half_values(f[r]) for r in ROLES2} for f in (pop_flat, hof_flat))
             self.eng = HalfDQNGAEngine(args.population, args.hof_size, args.elites_number, C, n,
                                        args.max_timesteps_per_episode, args.max_evaluation_steps,
-                                       fc1_layout=getattr(args, "coevo_fc1_layout", "streamed"), **common)
+                                       fc1_layout=getattr(args, "coevo_fc1_layout", "streamed"), **common, **env_kw)
         else:
             self.eng = DQNGAEngine(args.population, args.hof_size, args.elites_number, C, n,
                                    args.max_timesteps_per_episode, args.max_evaluation_steps, shard=shard, gather=gather,
-                                   frames=frames_mode(args), **common)
+                                   frames=frames_mode(args), **common, **env_kw)
         self.eng.load_initial(pop_flat, hof_flat)
         self.res = DQNResult()
         self.res.engine = self.eng
@@ -653,7 +662,8 @@ def dqn_genetic_algorithm_train(env, agent, args, output_dir, collect=True, dist
     for g in range(len(res.rewards["first_0"])):
         mw.write(generation=g, eval_rewards={r: res.rewards[r][g] for r in ROLES2},
                  mutation_power=res.sigma_after[g] if g < len(res.sigma_after) else None,
-                 elite_ids=res.elite_ids[g] if g < len(res.elite_ids) else None, data="synthetic env")
+                 elite_ids=res.elite_ids[g] if g < len(res.elite_ids) else None,
+                 data="duel env" if tr.eng.duel is not None else "synthetic env")
     return res
 
 
@@ -671,8 +681,10 @@ class DQNESEngine(_DQNSlabIO, CoESUpdate):
 
     def __init__(self, pop, C, n_actions, T_train, T_eval, device="cuda", env_seed=SYNTH_SEED, philox_seed=0,
                  shard=(0, 1), gather=None, first_ordinal=1, antithetic=False, centered_rank=False, chunks=ES_CHUNKS,
-                 frames="device"):
+                 frames="device", env="synthetic", duel_points=21, duel_credit="next"):
         assert frames in ("device", "host")
+        from .duel_rollout import duel_env_option   # (imports this module)
+        self.duel = duel_env_option(type(self).__name__, env, duel_points, duel_credit, C, frames, shard)
         self.frames = frames
         self.C, self.n_actions, self.device = C, n_actions, device
         self.Cw = C   # the streamed fc1 layout (one frame per task: v_mfma_f32_4x4x1, lane = output)
@@ -697,6 +709,10 @@ class DQNESEngine(_DQNSlabIO, CoESUpdate):
         if frames == "host":
             bounds = even_bounds(len(games), int(os.environ.get("COEVO_FRAME_COHORTS", "3")))
             bounds = [b - (b & 1) for b in bounds[:-1]] + [bounds[-1]]   # an individual's two games stay in one cohort
+        if self.duel is not None:   # the same tables and forward launches; the env-step launches are the duel's
+            import functools
+            from .duel_rollout import DuelRollout
+            cls = functools.partial(DuelRollout, **self.duel)
         self.ro = cls(games, net.net_off, ordinal0, C, n_actions, self.slab, env_seed, self.per_gen, device, bounds=bounds)
         self.ro.set_limits(np.full(self.n_main, self.T_train, dtype=np.int32))
         # the ten evaluation games of the updated base nets (one 10-frame task per agent-step) play on TILED twins of the two
@@ -782,16 +798,18 @@ class DQNESTrainer:
         self.first_ordinal = getattr(env, "n_resets", 1)
         common = dict(env_seed=getattr(env, "seed_value", None) or SYNTH_SEED, philox_seed=getattr(args, "coevo_seed", 0),
                       first_ordinal=self.first_ordinal, chunks=getattr(args, "coevo_es_chunks", ES_CHUNKS))
+        from .duel_rollout import env_option_of   # (imports this module)
+        env_kw = env_option_of(env)   # a DuelAEC: the engine plays the duel, with the env object's points and credit rule
         if self.half:   # the two float32 initialisations, rounded as .to(float16) rounds
             from .dqn_es_half import HalfDQNESEngine   # (imports this module)
             base = {r: half_values(base[r]) for r in ROLES2}
             self.eng = HalfDQNESEngine(args.population, C, n, args.max_timesteps_per_episode, args.max_evaluation_steps,
-                                       **common)
+                                       **common, **env_kw)
         else:
             self.eng = DQNESEngine(args.population, C, n, args.max_timesteps_per_episode, args.max_evaluation_steps,
                                    shard=shard, gather=gather, antithetic=getattr(args, "coevo_antithetic", False),
                                    centered_rank=getattr(args, "coevo_centered_rank", False), frames=frames_mode(args),
-                                   **common)
+                                   **common, **env_kw)
         for r in ROLES2:
             self.eng.upload(r, "base", 0, base[r][None])
         self.res = DQNResult()
@@ -838,5 +856,5 @@ def dqn_evolution_strategy_train(env, args, output_dir, collect=True, dist_ctx=N
     mw = MetricsWriter(output_dir)
     for g in range(len(res.rewards["first_0"])):
         mw.write(generation=g, eval_rewards={r: res.rewards[r][g] for r in ROLES2}, mutation_power=res.sigma_after[g],
-                 data="synthetic env")
+                 data="duel env" if tr.eng.duel is not None else "synthetic env")
     return [tr.eng.download(r, "base", 0, 1)[0] for r in ROLES2], res

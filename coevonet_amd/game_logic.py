@@ -26,7 +26,16 @@ def initialize_env(args):
         # ALE / its ROMs are not part of this build (and the reference's Atari loop does not run): the
         # two-player games are served by a SYNTHETIC env of the same AEC shape (coevonet_amd.atari_synthetic).
         # channels: 4 = BASELINE.json's 84x84x4 frames; the reference's wrapper stack (:50-52) would yield 6.
-        env = SyntheticAtariAEC(args.game, channels=getattr(args, "coevo_channels", 4))
+        # args.coevo_atari_env = "duel": the paddle duel (coevonet_amd.atari_duel), a game WITH dynamics - not ALE Pong either
+        kind = getattr(args, "coevo_atari_env", "synthetic")
+        if kind == "duel":
+            from .atari_duel import DuelAEC
+            env = DuelAEC(args.game, channels=getattr(args, "coevo_channels", 4),
+                          points_to_win=getattr(args, "coevo_duel_points", 21), credit=getattr(args, "coevo_duel_credit", "next"))
+        elif kind == "synthetic":
+            env = SyntheticAtariAEC(args.game, channels=getattr(args, "coevo_channels", 4))
+        else:
+            raise ValueError(f'args.coevo_atari_env is "synthetic" or "duel", not {kind!r}')
     else:
         raise ValueError(f"Unsupported game type: {args.game}")
     env.reset(seed=ENV_SEED)
@@ -187,6 +196,34 @@ def _play_atari_device(env, player1, player2, args, eval, half=False):
     return float(r[0]), float(r[1])
 
 
+def _play_duel_device(env, player1, player2, args, eval, half=False):
+    """one whole duel episode on the device, as _play_atari_device plays the synthetic env: a two-net slab and a one-game
+    DuelRollout / HalfDuelRollout.  The env object is left as the host loop leaves it: state, books, agent_selection."""
+    from .duel_rollout import DuelRollout, HalfDuelRollout
+    dev = "cuda"
+    C, n = env.C, env.n_actions
+    limit = args.max_evaluation_steps if eval else args.max_timesteps_per_episode
+    if limit is None:
+        raise ValueError("the device route of the duel env plays a fixed number of launches: a step limit is required")
+    sym = "coevo_dqn16" if half else "coevo_dqn"
+    stride = int(getattr(L.load(), sym + "_slab_stride")(C, n))
+    slab = torch.zeros(2 * stride, dtype=torch.int32 if half else torch.float32, device=dev)
+    flat = torch.from_numpy(np.ascontiguousarray(np.stack([player1.flat(), player2.flat()]), dtype=np.float32)).to(dev)
+    L.call(sym + "_pack", L._p(flat), L._p(slab), 2, C, n)
+    ro = (HalfDuelRollout if half else DuelRollout)([(0, 1)], [0, stride], [env.ordinal], C, n, slab, env.seed_value, 0, dev,
+                                                    points_to_win=env.points_to_win, credit=env.credit)
+    ro.set_limits([int(limit)])
+    ro.enqueue(int(limit), None)
+    torch.cuda.synchronize()
+    L.raise_on_status(ro.status)
+    r = ro.acc.cpu().numpy()[0]
+    words = ro.dstate.cpu().numpy()[0]
+    env.state.load_words(words)
+    env.state.t = int(words[11]) if words[11] else max(int(limit), 0)   # ended: the agent-steps booked when the game ended
+    env.agent_selection = env.possible_agents[env.state.t & 1]
+    return float(r[0]), float(r[1])
+
+
 def _leave_env_stepped(env, T, actions):
     """Two half players walked the AEC loop before their device route existed, and their callers saw the env object stepped:
     leave it where T calls of env.step leave it.  actions[p]: the last action of the player of parity p"""
@@ -218,11 +255,14 @@ def play_atari(env, player1, player2, args, eval=False):
     one, so it is accepted here and selects the step limit as for MPE).  On this package's synthetic env two DeepQN players, or
     two DeepQNHalf players, play the whole episode on the device (float16: an fp16 slab and a HalfSynthRollout); a mixed pair,
     another env or args.coevo_host_aec walk the AEC loop, one forward per agent-step"""
+    from .atari_duel import DuelAEC
     from .deepqn import DeepQN, DeepQNHalf
-    if isinstance(env, SyntheticAtariAEC) and not getattr(args, "coevo_host_aec", False):
+    ours = isinstance(env, SyntheticAtariAEC) or (isinstance(env, DuelAEC) and env.seed_value is not None)
+    if ours and not getattr(args, "coevo_host_aec", False):
+        device = _play_duel_device if isinstance(env, DuelAEC) else _play_atari_device
         for net in (DeepQN, DeepQNHalf):   # (DeepQNHalf is DeepQN's sibling, not a subclass)
             if isinstance(player1, net) and isinstance(player2, net):
-                return _play_atari_device(env, player1, player2, args, eval, half=net is DeepQNHalf)
+                return device(env, player1, player2, args, eval, half=net is DeepQNHalf)
     return _play_atari_aec(env, player1, player2, args, eval)
 
 
