@@ -31,6 +31,9 @@ __all__ = ["HalfGAEngine", "HalfESEngine", "DeepQNHalf", "HalfDQNGAEngine", "Hal
 _BASELINE_NAMES = frozenset(__all__[__all__.index("BaselineCrossPlay"):])
 _GAUNTLET_NAMES = ("Gauntlet", "Champion", "GauntletResult", "GauntletSpec")
 __all__ += list(_GAUNTLET_NAMES)
+_DUEL_CROSSPLAY_NAMES = ("DuelCrossPlay", "DuelCrossPlayResult", "DuelSeatRollout", "HalfDuelSeatRollout", "TrackerSeat",
+                         "duel_seat_action", "duel_tracker_word", "duel_test_agents", "duel_cross_play_checkpoints")
+__all__ += list(_DUEL_CROSSPLAY_NAMES)
 
 
 def __getattr__(name):
@@ -59,4 +62,7 @@ def __getattr__(name):
     if name in _GAUNTLET_NAMES:
         from . import gauntlet
         return getattr(gauntlet, name)
+    if name in _DUEL_CROSSPLAY_NAMES:
+        from . import duel_crossplay
+        return getattr(duel_crossplay, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -366,6 +366,23 @@ class BaselineCrossPlay(_CrossBase):
 
 
 # ------------------------------------------------------------------------------------------------------ synthetic Atari
+def one_side_tasks(side_nets, net_off):
+    """the DeepQN task table of games in which ONE parity is played by nets - game g's net is ``side_nets[g]``, an id into
+    net_off - with the rows grouped by net into tasks of <= COEVO_DQN_MAX_ROWS frames -> (tasks [DQN_TASK_DTYPE], the row of
+    every game [n] int32)"""
+    by_net = {}
+    for g, net in enumerate(side_nets):
+        by_net.setdefault(int(net), []).append(g)
+    tasks, row_of_game, row = [], np.zeros(len(side_nets), dtype=np.int32), 0
+    for net, games in by_net.items():
+        for i in range(0, len(games), L.DQN_MAX_ROWS):
+            chunk = games[i:i + L.DQN_MAX_ROWS]
+            tasks.append((int(net_off[net]), row, len(chunk)))
+            row_of_game[chunk] = np.arange(row, row + len(chunk))
+            row += len(chunk)
+    return np.array(tasks, dtype=L.DQN_TASK_DTYPE), row_of_game
+
+
 class BaselineSynthRollout:
     """``SynthRollout`` (dqn_population.py) for games in which one parity is scripted: game g seats net ``side_nets[g]`` (a net
     id into net_off) on parity `net_parity` and scripted baseline ``seats`` on the other.  On the scripted parity the conv
@@ -374,7 +391,7 @@ class BaselineSynthRollout:
 
     def __init__(self, side_nets, net_off, net_parity, script_seats, ordinal0, C, n_actions, slab, env_seed, device="cuda",
                  fc1_tiled=False):
-        from .dqn_population import FRAME, TASK_ROWS
+        from .dqn_population import FRAME
         self.n_games = n = len(side_nets)
         self.C, self.n_actions, self.slab, self.env_seed, self.device = C, n_actions, slab, int(env_seed), device
         self.Cw = C | (L.DQN_FC1_TILED if fc1_tiled else 0)
@@ -384,18 +401,9 @@ class BaselineSynthRollout:
         self.acc = torch.zeros(n, 3, dtype=torch.float64, device=device)
         self.limit = torch.zeros(n, dtype=torch.int32, device=device)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
-        by_net = {}
-        for g, net in enumerate(side_nets):
-            by_net.setdefault(int(net), []).append(g)
-        tasks, row_of_game, row = [], np.zeros(n, dtype=np.int32), 0
-        for net, games in by_net.items():
-            for i in range(0, len(games), TASK_ROWS):
-                chunk = games[i:i + TASK_ROWS]
-                tasks.append((int(net_off[net]), row, len(chunk)))
-                row_of_game[chunk] = np.arange(row, row + len(chunk))
-                row += len(chunk)
-        self.tasks_np = np.array(tasks, dtype=L.DQN_TASK_DTYPE)
-        self.tasks, self.n_tasks, self.max_rows = L.tasks_to_device(self.tasks_np, device), len(tasks), max(t[2] for t in tasks)
+        self.tasks_np, row_of_game = one_side_tasks(side_nets, net_off)
+        self.tasks, self.n_tasks = L.tasks_to_device(self.tasks_np, device), len(self.tasks_np)
+        self.max_rows = int(self.tasks_np["n_rows"].max())
         # the net parity's rows are its tasks' rows; the scripted parity's action row is indexed by game
         identity = np.arange(n, dtype=np.int32)
         self.rows = [torch.from_numpy(row_of_game if p == self.net_parity else identity).to(device) for p in range(2)]

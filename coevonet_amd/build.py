@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libcoevo.so")
 SOURCES = ["fc_forward.hip", "mpe_env.hip", "offspring.hip", "select.hip", "rollout_api.hip", "deepqn.hip",
            "dqn_engine.hip", "host_rollout.hip", "host_placement.hip", "fc16.hip", "fc16_rollout.hip", "fc16_offspring.hip",
            "fc16_es.hip", "dqn16.hip", "dqn16_offspring.hip", "dqn16_es.hip", "dqn16_tiled.hip", "crossplay.hip",
-           "sharing.hip", "fc16_sharing.hip", "baseline.hip", "gauntlet.hip", "duel_env.hip"]
+           "sharing.hip", "fc16_sharing.hip", "baseline.hip", "gauntlet.hip", "duel_env.hip", "duel_seats.hip"]
 # -ffp-contract=off: only explicit fmaf fuses (the canonical arithmetic contract with the oracle)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
          "-Wno-unused-function"]
@@ -27,7 +27,7 @@ def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     return hs + [os.path.join(HERE, "..", "include", h) for h in ("coevo.h", "coevo_ext.h", "coevo_crossplay.h",
                                                                    "coevo_sharing.h", "coevo_sharing16.h", "coevo_baseline.h",
-                                                                   "coevo_gauntlet.h", "coevo_duel.h")]
+                                                                   "coevo_gauntlet.h", "coevo_duel.h", "coevo_duel_seats.h")]
 
 
 def _stale(target, deps):

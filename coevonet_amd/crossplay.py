@@ -263,8 +263,9 @@ def _mpe_env_or_raise(env):
 def _atari_env_or_raise(env):
     from .atari_duel import DuelAEC
     if isinstance(env, DuelAEC):
-        raise ValueError("cross-play over the duel env (DuelAEC) is not built: DQNCrossPlay, DQNBaselineCrossPlay and test_agents "
-                         "play the synthetic Atari env only")
+        raise ValueError("cross-play over the duel env (DuelAEC) is not built into DQNCrossPlay, DQNBaselineCrossPlay and "
+                         "test_agents, which play the synthetic Atari env only: use duel_crossplay.DuelCrossPlay, "
+                         "duel_test_agents or duel_cross_play_checkpoints")
     if not isinstance(env, SyntheticAtariAEC) or env.seed_value is None:
         raise ValueError("cross-play runs on this package's seeded synthetic Atari env (initialize_env), not on a foreign AEC env")
 

@@ -26,6 +26,7 @@ SHARING16_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_sharing16.h")
 BASELINE_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_baseline.h")   # the baseline-opponent entry points, likewise
 GAUNTLET_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_gauntlet.h")   # the baseline-gauntlet entry points, likewise
 DUEL_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_duel.h")   # the paddle-duel env-step entry points, likewise
+DUEL_SEATS_HEADER_PATH = os.path.join(HERE, "..", "include", "coevo_duel_seats.h")   # ... with a scripted seat in the launch
 
 
 class CoevoError(RuntimeError):
@@ -231,6 +232,21 @@ def _parse_duel_header(text):
 
 K_DUEL, _DUEL_SIGS = _parse_duel_header(_header_text(DUEL_HEADER_PATH))
 
+
+def _parse_duel_seats_header(text):
+    """include/coevo_duel_seats.h -> (its constants, its entry points), read like coevo_duel.h: prototypes and constants only,
+    and no name that one of the eight other headers declares"""
+    consts, structs, sigs = parse_header(text, known=STRUCTS)
+    if (set(structs) != set(STRUCTS)
+            or set(sigs) & (set(_SIGS) | set(_EXT_SIGS) | set(_XP_SIGS) | set(_SH_SIGS) | set(_SH16_SIGS) | set(_BL_SIGS)
+                            | set(_GT_SIGS) | set(_DUEL_SIGS))
+            or set(consts) & (set(K) | set(K_EXT) | set(K_XP) | set(K_SH) | set(K_BL) | set(K_GT) | set(K_DUEL))):
+        raise CoevoError("include/coevo_duel_seats.h: declares a struct or repeats a name of another header")
+    return consts, sigs
+
+
+K_DUEL_SEATS, _DUEL_SEATS_SIGS = _parse_duel_seats_header(_header_text(DUEL_SEATS_HEADER_PATH))
+
 OBS_STRIDE, LOGIT_STRIDE, FC_MAX_ROWS = K["COEVO_OBS_STRIDE"], K["COEVO_LOGIT_STRIDE"], K["COEVO_FC_MAX_ROWS"]
 MPE_STATE_DOUBLES, STAMP_SLOTS = K["COEVO_MPE_STATE_DOUBLES"], K["COEVO_STAMP_SLOTS"]
 ST_NAMES = {K["COEVO_ST_BAD_INPUT"]: "input contains inf or NaN",
@@ -319,6 +335,11 @@ def duel_symbols():
     return sorted(_DUEL_SIGS)
 
 
+def duel_seats_symbols():
+    """the entry points of include/coevo_duel_seats.h, bound by load() beside the eight other tables"""
+    return sorted(_DUEL_SEATS_SIGS)
+
+
 def load():
     """dlopen libcoevo.so; raises CoevoError when it has not been built (python -m coevonet_amd.build)."""
     global _lib
@@ -328,7 +349,7 @@ def load():
                              "(python -m coevonet_amd.build); there is no CPU fallback")
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in {**_SIGS, **_EXT_SIGS, **_XP_SIGS, **_SH_SIGS, **_SH16_SIGS, **_BL_SIGS,
-                                  **_GT_SIGS, **_DUEL_SIGS}.items():
+                                  **_GT_SIGS, **_DUEL_SIGS, **_DUEL_SEATS_SIGS}.items():
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
