@@ -11,6 +11,7 @@ from coevonet_amd import game_logic as gl
 from coevonet_amd import lib as L
 from coevonet_amd.atari_synthetic import SyntheticAtariAEC
 from tests import dqn16_checker as ck
+from tests.dqn16_edge_nets import edge_nets   # noqa: F401  (tests/test_fp16_dqn_tiled_gpu.py imports it from here)
 from tests.test_fp16_dqn_cpu import fixture_net, offsets
 from tests.util import DQN_FRAME_KINDS, Bag, dqn_golden_frames, load_golden
 
@@ -151,29 +152,6 @@ def test_pack_rounds_to_half_and_unpack_returns_it():
                  (L._p(back), L._p(slab.slab), 1, 7, n), (L._p(back), L._p(slab.slab), 1, C | L.DQN_FC1_TILED, n),
                  (L._p(back), L._p(slab.slab), 1, C, 33)):
         assert lib.coevo_dqn16_pack(*args, L._stream()) == -1
-
-
-def edge_nets(C, n):
-    torch.manual_seed(9)
-    base = ck.half_net(C, n, 0.02)
-    off = offsets(C, n)
-    g = np.random.default_rng(4)
-    sub = base.copy()                                           # fc1 weights all fp16-subnormal
-    o, m = off["fc1.weight"]
-    sub[o:o + m] = (g.integers(1, 1024, m) * g.choice([-1.0, 1.0], m) * 2.0 ** -24).astype(np.float32)
-    zero = sub.copy()
-    zero[o:o + m] = 0.0
-    big = base.copy()                                           # fc1 outputs past 65504 -> inf
-    big[o:o + 3136] = 60000.0                                   # ... of output 0
-    tie = base.copy()
-    o, m = off["output.weight"]
-    tie[o:o + m] = 0.0
-    o, m = off["output.bias"]
-    tie[o:o + m] = np.array([0.125, 0.25, 0.5, 0.375, 0.5, 0.125], dtype=np.float32)
-    over = base.copy()                                          # conv1 sums past 65504 -> inf -> BatchNorm NaN
-    o, m = off["conv1.weight"]
-    over[o:o + m] = 60000.0
-    return sub, zero, big, tie, over
 
 
 def test_edge_nets_through_the_abi():
